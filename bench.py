@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the hot path's headline benchmark on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--check]
+    python bench.py --gpus N --steps K --warmup W [--check] [--dump-outputs DIR]
 
 N > 1 runs one process per GPU. Started by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) each
 process is one rank; started plainly (`python bench.py --gpus 8`) this process touches no GPU: it starts the N rank
@@ -279,6 +279,32 @@ def spot_check(H, wl, check_dw=True):
     return out
 
 
+DUMP_SEED = 2024          # which rows / heads --dump-outputs samples: fixed, so that two builds dump the same elements
+DUMP_GEMM_ROWS = 256      # of the 4096 rows of C, dA and dW: 4 MiB each as float32
+DUMP_ATTN_HEADS = 4       # of the B * H = 256 (b, h) pairs of O, dQ, dK and dV, each in full: 8 MiB per output as float32
+
+
+def snapshot_outputs(H, wl) -> dict:
+    """--dump-outputs: what one step hands its caller, as the step that just ran left it, in float32 (48 MiB in all). A fixed seeded
+    sample of each large output: the same DUMP_GEMM_ROWS rows of C = A W, dA = dC W^T and dW = A^T dC, the same DUMP_ATTN_HEADS (b, h)
+    heads of the attention outputs O, dQ, dK, dV; the whole LSE [B, H, S]. Host copies only: no kernel runs."""
+    n = GEMM_N
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(n, DUMP_GEMM_ROWS, replace=False))
+    heads = np.sort(rng.choice(AB * AH, DUMP_ATTN_HEADS, replace=False))
+    f32 = lambda u16: (u16.astype(np.uint32) << 16).view(np.float32)   # bf16 -> float32, exact
+    out = {"C": f32(wl.Cc.to_numpy((n, n), np.uint16)[rows]), "dA": f32(wl.dA.to_numpy((n, n), np.uint16)[rows]),
+           "dW": wl.dW.to_numpy((n, n), np.float32)[rows] if wl.grad_f32 else f32(wl.dW.to_numpy((n, n), np.uint16)[rows])}
+    per_head = AS * AD * 2
+    for name, buf in (("o", wl.o), ("dq", wl.dq), ("dk", wl.dk), ("dv", wl.dv)):
+        got = np.empty((DUMP_ATTN_HEADS, AS, AD), dtype=np.uint16)
+        for i, bh in enumerate(heads):
+            H.check(H.lib().kf_memcpy_d2h(got[i].ctypes.data, buf.ptr + int(bh) * per_head, per_head, None))
+        out[name] = f32(got)
+    out["lse"] = wl.lse.to_numpy((AB, AH, AS), np.float32)
+    return out
+
+
 def check_allreduce(H, wl, pg, stream):
     """Section 8e's parity sentence on the live buffers: the RCCL-reduced dW must equal the sum over ranks of each rank's own
     dW = A_r^T dC_r (recomputed here without the collective, summed in f32 over gloo on the host). RCCL adds bf16 values, so
@@ -451,8 +477,12 @@ def main():
     ap.add_argument("--check", action="store_true", help="after timing, verify outputs (oracle spot checks; all-reduced dW vs the gloo sum)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ceiling", action="store_true", help="skip the bare-MFMA ceiling probe (roofline.frac_of_capped_mfma)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after timing, write what the last timed step computed to DIR/<name>.npy "
+                    "(float32; a fixed seeded sample of each large output, 48 MiB in all: snapshot_outputs)")
     ap.add_argument("--dry-run-cpu", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -523,6 +553,8 @@ def main():
     # THE measured loop runs with per-launch profiling OFF (the event records were 1.6 % of `value`); the per-kernel
     # table comes from a SECOND loop of the same length with profiling on, reported as `ms_per_step_profiled`.
     elapsed = timed(args.steps)
+    # the outputs of the headline loop's last step, copied before any later loop runs (host copies after the barrier: outside the timing)
+    dumped = snapshot_outputs(H, wl) if args.dump_outputs and rank == 0 else None
     H.profile_reset()
     H.profile_enable(True)
     comm_events = [] if (pg and not no_comm_env) else None
@@ -627,6 +659,12 @@ def main():
             out["overlap_efficiency"] = (max(0.0, min(1.0, 1.0 - max(0.0, exposed) / ar)) if ar else None)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
+        if dumped is not None:
+            ddir = Path(args.dump_outputs)
+            ddir.mkdir(parents=True, exist_ok=True)
+            for name, arr in dumped.items():
+                np.save(ddir / f"{name}.npy", arr)
+            out["dumped_outputs"] = {name: list(arr.shape) for name, arr in dumped.items()}
         if not all(checks.values()):
             rc = 1
     if pg is not None and rank != 0 and not all(checks.values()):

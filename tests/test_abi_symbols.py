@@ -27,21 +27,14 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_struct_layout_matches_c():
-    src = r'''
-    #include <stdio.h>
-    #include <stddef.h>
-    #include "kfunca_hip.h"
-    int main(void) {
-        printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(kf_iter_desc), offsetof(kf_iter_desc, dtype), offsetof(kf_iter_desc, shape),
-               offsetof(kf_iter_desc, stride_bytes), offsetof(kf_iter_desc, data), sizeof(kf_device_props), offsetof(kf_device_props, total_mem));
-        return 0;
-    }'''
-    exe = Path("/tmp/kf_layout_probe")
-    subprocess.run(["gcc", "-x", "c", "-", f"-I{ROOT / 'include'}", "-o", str(exe)], input=src, text=True, check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    want = [C.sizeof(H.IterDesc), H.IterDesc.dtype.offset, H.IterDesc.shape.offset, H.IterDesc.stride_bytes.offset,
-            H.IterDesc.data.offset, C.sizeof(H.DeviceProps), H.DeviceProps.total_mem.offset]
-    assert got == want
+    # the C compiler checks every size / offset against the ctypes mirror at compile time: nothing is written or run
+    want = {"sizeof(kf_iter_desc)": C.sizeof(H.IterDesc), "offsetof(kf_iter_desc, dtype)": H.IterDesc.dtype.offset,
+            "offsetof(kf_iter_desc, shape)": H.IterDesc.shape.offset, "offsetof(kf_iter_desc, stride_bytes)": H.IterDesc.stride_bytes.offset,
+            "offsetof(kf_iter_desc, data)": H.IterDesc.data.offset, "sizeof(kf_device_props)": C.sizeof(H.DeviceProps),
+            "offsetof(kf_device_props, total_mem)": H.DeviceProps.total_mem.offset}
+    src = "#include <stddef.h>\n#include \"kfunca_hip.h\"\n" + "".join(f'_Static_assert({e} == {v}, "{e} != {v}");\n' for e, v in want.items())
+    res = subprocess.run(["gcc", "-x", "c", "-fsyntax-only", f"-I{ROOT / 'include'}", "-"], input=src, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
 
 
 def test_no_gpu_calls_fail_loudly_not_silently():

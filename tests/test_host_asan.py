@@ -24,7 +24,9 @@ def test_host_geometry_and_promotion_under_asan_ubsan():
     import tempfile
 
     from kfunca_amd import _build
-    tmp = tempfile.mkdtemp(prefix="kf_asan_")
+    # beside the product's own libraries, not in $TMPDIR: a temporary directory may be mounted noexec, and then the instrumented _C cannot be loaded
+    _build.BUILD.mkdir(exist_ok=True)
+    tmp = tempfile.mkdtemp(prefix="kf_asan_", dir=_build.BUILD)
     try:
         _run_under_asan(_build.build_core_asan(tmp))  # a shadow package `kfunca_amd` with the instrumented _C
     finally:
@@ -38,6 +40,8 @@ def _run_under_asan(shadow):
                PYTHONPATH=f"{shadow}{os.pathsep}{ROOT}")
     code = (f"import sys, kfunca_amd, pytest; assert kfunca_amd.__file__.startswith(r'{shadow}'), kfunca_amd.__file__; "
             f"sys.exit(pytest.main(['-q', '-x', '-p', 'no:cacheprovider', r'{ROOT / 'tests' / 'test_host_geometry.py'}']))")
-    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(shadow), timeout=900)
+    # the child sees the same site-packages as this process (-s when user site-packages are ignored here)
+    res = subprocess.run([sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c", code], capture_output=True, text=True, env=env,
+                         cwd=str(shadow), timeout=900)
     assert res.returncode == 0, (res.stdout[-3000:], res.stderr[-3000:])
     assert "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]

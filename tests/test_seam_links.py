@@ -1,10 +1,11 @@
 """CPU: the drop-in boundary proved by the LINKER.
 
-oracle/build_ref_host.py compiles the reference's own host half - src/core/*.cpp, unmodified, where it lies under /root/reference -
+oracle/build_ref_host.py (run by build()) compiles the reference's own host half - src/core/*.cpp, unmodified, where it lies -
 together with docs/seam.cpp (this repository's definitions of src/device/include/*.h over include/kfunca_hip.h) and links the result
 against kfunca_amd/libkfunca_hip.so with -Wl,--no-undefined: every symbol the reference's host core expects from its device library
 must be resolved by the C ABI, or the link fails. On top of that object src/register.cpp (the reference's pybind11 module) is linked
-into oracle/_ref/kfunca*.so, which tests/test_gpu_reference_host.py then drives on the GPU. Skipped where the reference is not mounted."""
+into oracle/_ref/kfunca*.so, which tests/test_gpu_reference_host.py then drives on the GPU. These tests read what build() left in
+oracle/_ref/ and nothing outside the repository; skipped where build() had no reference tree to build it from."""
 import re
 import shutil
 import subprocess
@@ -14,17 +15,17 @@ from pathlib import Path
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
-REF = Path("/root/reference/src")
+REFDIR = ROOT / "oracle" / "_ref"
 
-pytestmark = [pytest.mark.skipif(not (REF / "core" / "tensor.cpp").exists(), reason="reference tree not mounted"),
-              pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")]
+pytestmark = pytest.mark.skipif(shutil.which("nm") is None, reason="no binutils")
 
 
 @pytest.fixture(scope="module")
 def built():
-    sys.path.insert(0, str(ROOT))
-    from oracle import build_ref_host
-    return build_ref_host.build(with_module=True)
+    mods = sorted(REFDIR.glob("kfunca*.so"))
+    if not mods:
+        pytest.skip("oracle/_ref/kfunca*.so not built (build() builds it where the reference tree is readable)")
+    return mods[0]
 
 
 def test_reference_core_plus_seam_links_with_no_undefined_symbols(built):

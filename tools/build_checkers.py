@@ -9,6 +9,7 @@
 `__graft_entry__.build()` calls build_all() after the product build (building a checker is not using it). Rebuild decisions are made on
 content signatures (kfunca_amd/_build.py: _fresh / _mark), not on mtimes.
 """
+import os
 import sys
 from pathlib import Path
 
@@ -33,7 +34,7 @@ def build_oracle(force: bool = False) -> Path:
 def build_ref_host() -> bool:
     """True when oracle/_ref was (re)built; False without the reference mount. A failure is reported, not raised: the tests that need the
     module (tests/test_seam_links.py, tests/test_gpu_reference_host.py) say so themselves."""
-    if not Path("/root/reference/src/core/tensor.cpp").exists():
+    if not os.path.exists("/root/reference/src/core/tensor.cpp"):  # (False, not PermissionError, where the tree exists but this user may not read it)
         return False
     try:
         from oracle import build_ref_host as R
