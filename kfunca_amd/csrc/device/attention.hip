@@ -56,7 +56,7 @@ struct AttnArgs {
     float scale_log2e; // scale * log2(e), formed on the host (attn_fwd_w4_kernel hands it to its instruction stream as a scalar)
     int xcd_map; // 1: nbh % 8 == 0, heads are pinned to XCDs (a_block_map)
     float defer; // forward: adopt a new running maximum only beyond this many exponent units (kDeferMax; -inf: always)
-    unsigned nvwg;   // the generated kernels: virtual workgroups (= gridDim.x unless KF_ATTN_GRID_WGS asks for fewer real ones: grid-stride loop)
+    unsigned nvwg;   // the generated kernels: virtual workgroups (the host launches gridDim.x = nvwg; the kernels walk them in a grid-stride loop)
     int persist;     // k > 0: a workgroup handles k pairs {block x, its causal mirror}: equal work per workgroup (k = 1 is used)
     int persist_rev; // the short block of a pair first
     // global layouts of the 16-bit matrix-core path: byte strides of batch, head and row (the last dim is contiguous). Contiguous
@@ -631,8 +631,8 @@ __global__ __launch_bounds__(256) void attn_fwd_w4_kernel(const AttnArgs a) {
     const unsigned kvn = (unsigned)((a.Skv - 1) * a.lk.sr + dbytes);
     const float c = a.scale_log2e, defer = a.defer; // (kernel arguments are scalar registers; a float product formed here would be a vector one)
     const int qsr = (int)a.lq.sr, kvsr = (int)a.lk.sr, osr = (int)a.lo.sr;
-    // (a.nvwg virtual workgroups over gridDim.x real ones: KF_ATTN_GRID_WGS, an experiment - default one each. A stride of a multiple of 8 keeps
-    //  a virtual workgroup on the XCD its id maps to.)
+    // (a.nvwg virtual workgroups over gridDim.x real ones; the host launches one real workgroup each, so the loop runs once. A stride of a
+    //  multiple of 8 would keep a virtual workgroup on the XCD its id maps to.)
 #pragma nounroll
     for (unsigned vwg = blockIdx.x; vwg < a.nvwg; vwg += gridDim.x) {
     int xb0;
@@ -2627,24 +2627,22 @@ static int attn_fwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Sk
         a.persist = (nxb3 % 2 == 0 && nxb3 >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0;
         dim3 grid3((unsigned)((a.persist ? nxb3 / (2 * a.persist) : nxb3) * B * H));
         a.nvwg = grid3.x;
-        dim3 grid3w = grid3; // the generated kernels' real grid: all virtual workgroups, or KF_ATTN_GRID_WGS of them looping (a multiple of 8)
-        if (const long gw = knob_int(KNOB_ATTN_GRID_WGS, 0); gw >= 8 && (unsigned)gw < grid3.x) grid3w.x = (unsigned)(gw / 8 * 8);
         KF_PROF(D == 64 ? "attn_fwd_mfma_d64" : "attn_fwd_mfma", st);
         // round 4: the one-wave-per-SIMD stream (attn_fwd_w4_kernel) wherever its shape conditions hold; KF_ATTN_FWD_V3 keeps the 8-wave kernel (A/B)
         if (fwd_w4) {
 #define KF_FWD4(BF_, SQ_)                                                                                   \
     {                                                                                                       \
         if ((rc = set_lds(attn_fwd_w4_kernel<BF_, SQ_>, KF_FWD_W4_LDS_BYTES)) != KF_OK) return rc;           \
-        attn_fwd_w4_kernel<BF_, SQ_><<<grid3w, 256, KF_FWD_W4_LDS_BYTES, st>>>(a);                           \
+        attn_fwd_w4_kernel<BF_, SQ_><<<grid3, 256, KF_FWD_W4_LDS_BYTES, st>>>(a);                           \
     }
             const bool sq = D == AD && knob(KNOB_ATTN_SCALED_OPERANDS); // opt-in: c q rounded once per pass (faster; score error grows with the logits)
             if (D == 64) {
                 if (dtype == KF_BF16) {
                     if ((rc = set_lds(attn_fwd_w4_kernel<true, false, true>, KF_FWD_W4_LDS_BYTES)) != KF_OK) return rc;
-                    attn_fwd_w4_kernel<true, false, true><<<grid3w, 256, KF_FWD_W4_LDS_BYTES, st>>>(a);
+                    attn_fwd_w4_kernel<true, false, true><<<grid3, 256, KF_FWD_W4_LDS_BYTES, st>>>(a);
                 } else {
                     if ((rc = set_lds(attn_fwd_w4_kernel<false, false, true>, KF_FWD_W4_LDS_BYTES)) != KF_OK) return rc;
-                    attn_fwd_w4_kernel<false, false, true><<<grid3w, 256, KF_FWD_W4_LDS_BYTES, st>>>(a);
+                    attn_fwd_w4_kernel<false, false, true><<<grid3, 256, KF_FWD_W4_LDS_BYTES, st>>>(a);
                 }
             } else if (dtype == KF_BF16) { if (sq) KF_FWD4(true, true) else KF_FWD4(true, false) }
             else { if (sq) KF_FWD4(false, true) else KF_FWD4(false, false) }
@@ -2665,7 +2663,7 @@ static int attn_fwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Sk
     }
     // (from here on: kernels of contiguous [B, H, S, D] tensors only)
     KF_REQUIRE(!lays, KF_ERR_UNSUPPORTED, "kf_attn_fwd_strided: this shape / stride combination has no matrix-core kernel (ragged lengths want K and V with one row stride)");
-    if (dtype == KF_F32 && (D == 64 || D == 128) && Sq % 32 == 0 && Skv % 32 == 0 && !knob(KNOB_ATTN_F32_GENERIC)) {
+    if (dtype == KF_F32 && (D == 64 || D == 128) && Sq % 32 == 0 && Skv % 32 == 0) {
         // the reference's own fast path (f32, head size 64 or 128): exact-f32 MFMA
         const size_t ldsx = std::max((size_t)2 * XK * (D + 4), (size_t)4 * 32 * (D + 4)) * sizeof(float);
         const int64_t nxx = (Sq + XQ - 1) / XQ;
@@ -2857,7 +2855,6 @@ static int attn_bwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Sk
                     a.persist = (nkb5 % 2 == 0 && nkb5 >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0;
                     dim3 gk5((unsigned)((a.persist ? nkb5 / 2 : nkb5) * a.nbh));
                     a.nvwg = gk5.x;
-                    if (const long gw = knob_int(KNOB_ATTN_GRID_WGS, 0); gw >= 8 && (unsigned)gw < gk5.x) gk5.x = (unsigned)(gw / 8 * 8);
 #define KF_DKV5(BF_, DS_, SQ_)                                                                                    \
     {                                                                                                             \
         if ((rc = set_lds(attn_bwd_dkv_w4_kernel<BF_, DS_, SQ_>, KF_DKV_W4_LDS_BYTES)) != KF_OK) return rc;        \
@@ -2904,7 +2901,7 @@ static int attn_bwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Sk
     // (from here on: kernels of contiguous [B, H, S, D] tensors only)
     KF_REQUIRE(!lays, KF_ERR_UNSUPPORTED, "kf_attn_bwd_strided: this shape / stride / workspace combination has no matrix-core kernel (ragged lengths want room for dS)");
     const unsigned gd = (unsigned)((nrows + 3) / 4);
-    if (dtype == KF_F32 && (D == 64 || D == 128) && Sq % 32 == 0 && Skv % 32 == 0 && !knob(KNOB_ATTN_F32_GENERIC)) {
+    if (dtype == KF_F32 && (D == 64 || D == 128) && Sq % 32 == 0 && Skv % 32 == 0) {
         // exact-f32 MFMA backward (the f32 forward's counterpart; the reference has no backward)
         {
             KF_PROF("attn_bwd_delta", st);

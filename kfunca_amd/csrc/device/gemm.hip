@@ -4,8 +4,8 @@
 // (src/device/launcher_cuda.h:537-614). Hand-written for CDNA4:
 //   f32      v_mfma_f32_32x32x2_f32 (exact f32 fma chain), 128x128x16 block tile (64x64x16 for small grids), LDS tiles
 //            kept k-major so every fragment read is a conflict-free ds_read_b32.
-//   bf16/f16 large grids: 256x256x64 block tile, v_mfma_f32_16x16x32, LDS-DMA staging - an 8-wave form (two waves per SIMD
-//            half a phase apart) and a 4-wave form (one wave per SIMD, 256 in-place AGPR accumulators);
+//   bf16/f16 large grids: 256x256x64 block tile, v_mfma_f32_16x16x32, LDS-DMA staging, 4 waves (one wave per SIMD,
+//            256 in-place AGPR accumulators);
 //            smaller grids: 128x128x64 block tile, v_mfma_f32_32x32x16, double-buffered LDS, one barrier per K tile.
 //   Every kernel consumes all four op(A) / op(B) layouts in place: an operand whose contraction dim is the strided one is
 //   staged as it lies in memory and read with ds_read_b64_tr_b16 - no re-layout pass, no workspace.
@@ -722,18 +722,18 @@ __global__ __launch_bounds__(256) void gemm_splitk_fold_kernel(const GemmArgs g)
 }
 
 // ------------------------------------------------------------------------------------------
-// bf16 / f16, large shapes: 256 x 256 x 64 block tile, 8 waves (2 x 4, 128 x 64 per wave), MFMA 16x16x32,
-// two waves per SIMD running HALF A PHASE APART: while one group of four waves is in a matrix segment
-// (16 MFMAs) the other is in its load segment (fragment ds_reads + one half-tile of LDS-DMA), swapping at
-// every raw s_barrier. A K tile is cut into four half-tiles of 128 rows x 64 k, chosen so that each is read
-// in exactly ONE phase by every wave:
-//     HA0 = rows {wr*128 + 0..63}   (A0 fragments, phase 0)      HB0 = cols {wc*64 + 0..31}  (B0, phase 0)
-//     HA1 = rows {wr*128 + 64..127} (A1 fragments, phase 1)      HB1 = cols {wc*64 + 32..63} (B1, phase 2)
-// Quadrant order (A0,B0) (A1,B0) (A1,B1) (A0,B1): all four fragment sets stay in registers, so a half-tile's
-// LDS region is free one phase after its single read and is re-staged 5-6 phases before its next read:
-//     phase 0: stage HA1(T+1)   phase 1: HB1(T+1)   phase 2: HA0(T+2)   phase 3: HB0(T+2)
-// Every wave issues 2 DMA operations per phase, so ONE counted wait per phase, s_waitcnt vmcnt(8) (the four
-// youngest half-tiles stay in flight), retires exactly what the next phase reads; the barrier publishes it.
+// bf16 / f16, large shapes: 256 x 256 x 64 block tile, FOUR waves (2 x 2, 128 x 128 of C per wave), ONE wave per SIMD
+// with the whole register file: 256 accumulator registers (AGPRs) + two sets of fragments (2 x 64 VGPRs), MFMA 16x16x32.
+// There is ONE barrier per K tile and nothing depends on a partner wave: the fragments of the next k-step are read under
+// the 64 MFMAs of the current one. (Until round 3 an 8-wave form, 128 x 64 of C per wave and two waves per SIMD, ran the
+// large grids. This one reads each LDS byte for twice the MFMA work, 128 KiB of LDS traffic per K tile against 192, with
+// one barrier per K tile against eight, and was ahead of it at every size measured, same process, interleaved:
+// 4096 x 12288 x 4096 NN 1258 vs 1120 TFLOP/s, TN 1234 vs 1091; 4096 x 4096 x 16384 TN 1315 vs 1130; 8192^3 NN 1396 vs 1264,
+// NT 1454 vs 1390; 5120^3 TN 1058 vs 934.)
+//     S0: 64 MFMAs of (tile t, k-step 0) | under them: read fragments (t, k-step 1)
+//     P : s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier   - tile t + 1 has landed for everyone, tile t's buffer is free
+//     S1: 64 MFMAs of (t, k-step 1)      | under them: 16 DMA operations of tile t + 2, read fragments (t + 1, k-step 0)
+// Half-tiles: HA0 / HA1 = rows 0..127 / 128..255 of the A tile, HB0 / HB1 likewise for B; wave (wr, wc) reads HA[wr], HB[wc].
 // LDS: 2 K tiles x 4 half-tiles x (16 KiB + 256 B) = 130 KiB.
 // Operand layouts (TRA / TRB): a K-contiguous operand (A [M,K], B stored [N,K]) is staged as a [128 rows][128 B]
 // image and its 16 x 32 fragments are one ds_read_b128 each. An operand whose contraction dim is the STRIDED one
@@ -743,305 +743,6 @@ __global__ __launch_bounds__(256) void gemm_splitk_fold_kernel(const GemmArgs g)
 // chunk index by (k & 3) << 2 applied on the DMA source, plus 32 B of padding after every PAIR of 4-row groups
 // (a DMA instruction's 1 KiB lands contiguously, so padding can only sit between instructions); the k-step and
 // the lo / hi row quad of a fragment are then immediates (8192 + 128, 1024) off one per-tile address.
-// ------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-constexpr int G_BM = 256, G_BN = 256, G_BK = 64, G_NT = 512;
-constexpr int G_HALF = 128 * G_BK * 2 + 256; // 16 KiB + the transposed image's padding (32 B x 7, rounded up)
-constexpr int G_TILE = 4 * G_HALF;          // HA0 | HB0 | HA1 | HB1
-constexpr int G_LDS = 2 * G_TILE;           // 130 KiB
-
-
-// one 16 (m or n) x 32 (k) fragment out of a [k][256 B] image: rows 8*(lane>>4) + {0..3} and + {4..7} of the k-step
-template <bool BF, int OFF>
-__device__ __forceinline__ typename HFrag<BF>::type g_tr_frag(unsigned addr) {
-    g_s16x4 lo, hi;
-    asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%c3\n\tds_read_b64_tr_b16 %1, %2 offset:%c4"
-                 : "=&v"(lo), "=&v"(hi)
-                 : "v"(addr), "n"(OFF), "n"(OFF + 1024)
-                 : "memory");
-    g_s16x8 r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return __builtin_bit_cast(typename HFrag<BF>::type, r);
-}
-
-template <bool BF>
-__device__ __forceinline__ f32x4 g_mfma16(typename HFrag<BF>::type a, typename HFrag<BF>::type b, f32x4 c) {
-    if constexpr (BF)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-template <bool BF, bool TRA, bool TRB>
-__global__ __launch_bounds__(G_NT, 2) void gemm_h256_kernel(const GemmArgs g) {
-    using frag_t = typename HFrag<BF>::type;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wr = __builtin_amdgcn_readfirstlane(wid) >> 2, wc = __builtin_amdgcn_readfirstlane(wid) & 3;
-    const uint32_t tiles_n = (uint32_t)(g.N / G_BN);
-    uint32_t tm, tn;
-    grouped_tile(xcd_remap(blockIdx.x, gridDim.x), (uint32_t)(g.M / G_BM), tiles_n, (uint32_t)g.group_m, tm, tn);
-    const int64_t m0 = (int64_t)tm * G_BM, n0 = (int64_t)tn * G_BN;
-    const int nt = (int)(g.K / G_BK);
-
-    // ---- LDS-DMA source pointers. K-contiguous operand: wave w moves rows (2w + i) * 8 .. + 7 (i = 0, 1) of every
-    // half-tile. Transposed-read operand: wave w moves k rows (2w + i) * 4 .. + 3, 256 B (128 rows / columns) each.
-    const char *srcA[2][2], *srcB[2][2]; // [half 0/1][i]
-    int ldsoffA[2], ldsoffB[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int hr = (wid * 2 + i) * 8 + (lane >> 3), pos = lane & 7;
-        const int chunk = pos ^ ((hr >> 1) & 7);
-        const int kr = (wid * 2 + i) * 4 + (lane >> 4);                // transposed image: k row of this lane
-        const int j0 = ((lane & 15) ^ ((kr & 3) << 2)) * 8;            // ... and the first of its 8 rows / columns
-        if constexpr (TRA) {
-            ldsoffA[i] = (wid * 2 + i) * 1024 + 32 * wid;
-            srcA[0][i] = (const char *)g.A + ((int64_t)kr * g.lda + m0 + j0) * 2; // HA0 = rows 0..127: whole 256-B lines per k
-            srcA[1][i] = srcA[0][i] + 128 * 2;
-        } else {
-            ldsoffA[i] = (wid * 2 + i) * 8 * 128;
-            const int64_t arow = m0 + (hr >> 6) * 128 + (hr & 63);
-            srcA[0][i] = (const char *)g.A + arow * g.lda * 2 + chunk * 16;
-            srcA[1][i] = srcA[0][i] + 64 * g.lda * 2;
-        }
-        if constexpr (TRB) {
-            ldsoffB[i] = (wid * 2 + i) * 1024 + 32 * wid;
-            srcB[0][i] = (const char *)g.B + ((int64_t)kr * g.ldb + n0 + j0) * 2; // HB0 = columns 0..127
-            srcB[1][i] = srcB[0][i] + 128 * 2;
-        } else {
-            ldsoffB[i] = (wid * 2 + i) * 8 * 128;
-            const int64_t brow = n0 + (hr >> 5) * 64 + (hr & 31);
-            srcB[0][i] = (const char *)g.B + brow * g.ldb * 2 + chunk * 16;
-            srcB[1][i] = srcB[0][i] + 32 * g.ldb * 2;
-        }
-    }
-    const int64_t kstepA = TRA ? (int64_t)G_BK * g.lda * 2 : (int64_t)G_BK * 2;
-    const int64_t kstepB = TRB ? (int64_t)G_BK * g.ldb * 2 : (int64_t)G_BK * 2;
-    // which: 0 HA0, 1 HB0, 2 HA1, 3 HB1 (also the slot inside a tile buffer)
-    auto stage = [&](int which, int kt) {
-        const int64_t ktc = kt < nt ? kt : nt - 1; // past the end: re-fetch the last tile (never read)
-        char *dst = smem + (kt & 1) * G_TILE + which * G_HALF;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const char *src = (which & 1) ? srcB[which >> 1][i] + ktc * kstepB : srcA[which >> 1][i] + ktc * kstepA;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                             (__attribute__((address_space(3))) void *)(dst + ((which & 1) ? ldsoffB[i] : ldsoffA[i])), 16, 0, 0);
-        }
-    };
-
-    // ---- fragment read offsets: row r of a 16-row tile, k-chunk (ks*4 + lane>>4), XOR swizzle on (row>>1)&7
-    const int fr = lane & 15, fg = lane >> 4;
-    const int sw = (fr >> 1) & 7;
-    const int offk0 = fr * 128 + (((0 + fg) ^ sw) << 4), offk1 = fr * 128 + (((4 + fg) ^ sw) << 4);
-    const int abase = TRA ? 0 : wr * 64 * 128, bbase = TRB ? 0 : wc * 32 * 128; // this wave's rows inside HA* / HB*
-    // transposed image: per-lane address of tile 0's low row quad; tile t is this XOR (16-B chunk index ^ 2 t), see above
-    const int tq = fr >> 2;
-    const int lbT = fg * 2048 + tq * 256 + (((((fr & 3) >> 1)) ^ (tq << 2)) << 4) + 8 * (fr & 1);
-    const int pbT = 32 * fg;
-    const unsigned smem_u = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)smem;
-    const int ecA = wr * 128, ecB = wc * 64; // (first chunk of this wave's columns) << 4
-
-    f32x4 acc[4][8]; // [n-tile 0..3][m-tile 0..7]: D = B_frag x A_frag, i.e. C^T tiles (rows = n on registers)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
-    frag_t a0[4][2], a1[4][2], b0[2][2], b1[2][2];
-
-    // ---- prologue: the issues of "phases -6 .. -1"
-    stage(0, 0); stage(1, 0); stage(2, 0); stage(3, 0); stage(0, 1); stage(1, 1);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier(); // waves 4-7 run half a phase behind waves 0-3
-    asm volatile("" ::: "memory");
-
-#define G_SEG_END()                            \
-    asm volatile("" ::: "memory");             \
-    __builtin_amdgcn_sched_barrier(0);         \
-    __builtin_amdgcn_s_barrier();              \
-    __builtin_amdgcn_sched_barrier(0);         \
-    asm volatile("" ::: "memory");
-
-    // fragment loads of one half-tile, NTL tiles of 16 rows / columns. PART 0 runs in the load segment: both k-steps
-    // of a ds_read_b128 operand, k-step 0 of a transposed-read operand; PART 1 (transposed-read operands only) issues
-    // k-step 1; PART 2 both. The transposed A operand (16 + 16 read instructions per half-tile) is split: k-step 1 is
-    // issued at the top of the wave's own matrix segment, under the k-step-0 MFMAs, which keeps the load segment as
-    // short as the other group's matrix segment; the B operand (8 + 8) loads whole in the load segment.
-#define G_LOAD(FR, NTL, HB, TR, EC, PART)                                                             \
-    _Pragma("unroll") for (int t = 0; t < NTL; ++t) {                                                 \
-        if constexpr (TR) {                                                                           \
-            const unsigned x = (unsigned)((lbT ^ ((EC) + t * 32)) + pbT) + smem_u + (unsigned)((HB) - smem); \
-            if constexpr ((PART) == 0 || (PART) == 2) FR[t][0] = g_tr_frag<BF, 0>(x);                     \
-            if constexpr ((PART) == 1 || (PART) == 2) FR[t][1] = g_tr_frag<BF, 8192 + 128>(x);            \
-        } else if constexpr ((PART) == 0 || (PART) == 2) {                                                \
-            FR[t][0] = *(const frag_t *)((HB) + t * 2048 + offk0);                                    \
-            FR[t][1] = *(const frag_t *)((HB) + t * 2048 + offk1);                                    \
-        }                                                                                             \
-    }
-// the asm-issued transposed reads are invisible to the compiler's wait insertion: counted lgkmcnt waits by hand,
-// placed AFTER the barrier (the reads' latency overlaps the barrier wait, as the compiler arranges for ds_read_b128)
-#define G_LGKM(N)                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                   \
-    asm volatile("s_waitcnt lgkmcnt(%c0)" ::"n"(N) : "memory");          \
-    __builtin_amdgcn_sched_barrier(0);
-#define G_MFMA(KS, ACC, NOFF, MOFF, BF_, AF_)                                                           \
-    _Pragma("unroll") for (int n = 0; n < 2; ++n)                                                     \
-        _Pragma("unroll") for (int m = 0; m < 4; ++m)                                                 \
-            ACC[NOFF + n][MOFF + m] = g_mfma16<BF>(BF_[n][KS], AF_[m][KS], ACC[NOFF + n][MOFF + m]);
-    constexpr int NLA = 8; // k-step-1 read instructions of a transposed A half-tile (4 tiles x lo, hi)
-    constexpr bool SPLITB = TRA && TRB; // both operands transposed: B's k-step 1 moves into the matrix segment too
-
-    for (int kt = 0; kt < nt; ++kt) {
-        const char *buf = smem + (kt & 1) * G_TILE;
-        const char *ha0 = buf + abase, *hb0 = buf + G_HALF + bbase, *ha1 = buf + 2 * G_HALF + abase, *hb1 = buf + 3 * G_HALF + bbase;
-        // ---------------- phase 0: (A0, B0) ----------------
-        G_LOAD(b0, 2, hb0, TRB, ecB, (SPLITB ? 0 : 2))
-        G_LOAD(a0, 4, ha0, TRA, ecA, 0)
-        stage(2, kt + 1);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        G_SEG_END()
-        if constexpr (TRA) {
-            if constexpr (SPLITB) { G_LOAD(b0, 2, hb0, TRB, ecB, 1) }
-            G_LOAD(a0, 4, ha0, TRA, ecA, 1)
-            G_LGKM(NLA + (SPLITB ? 4 : 0))
-        } else if constexpr (TRB) {
-            G_LGKM(0)
-        }
-        __builtin_amdgcn_s_setprio(1);
-        G_MFMA(0, acc, 0, 0, b0, a0)
-        if constexpr (TRA) { G_LGKM(0) }
-        G_MFMA(1, acc, 0, 0, b0, a0)
-        __builtin_amdgcn_s_setprio(0);
-        G_SEG_END()
-        // ---------------- phase 1: (A1, B0) ----------------
-        G_LOAD(a1, 4, ha1, TRA, ecA, 0)
-        stage(3, kt + 1);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        G_SEG_END()
-        if constexpr (TRA) {
-            G_LOAD(a1, 4, ha1, TRA, ecA, 1)
-            G_LGKM(NLA)
-        }
-        __builtin_amdgcn_s_setprio(1);
-        G_MFMA(0, acc, 0, 4, b0, a1)
-        if constexpr (TRA) { G_LGKM(0) }
-        G_MFMA(1, acc, 0, 4, b0, a1)
-        __builtin_amdgcn_s_setprio(0);
-        G_SEG_END()
-        // ---------------- phase 2: (A1, B1) ----------------
-        G_LOAD(b1, 2, hb1, TRB, ecB, (SPLITB ? 0 : 2))
-        stage(0, kt + 2);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        G_SEG_END()
-        if constexpr (SPLITB) {
-            G_LOAD(b1, 2, hb1, TRB, ecB, 1)
-            G_LGKM(4)
-        } else if constexpr (TRB) {
-            G_LGKM(0)
-        }
-        __builtin_amdgcn_s_setprio(1);
-        G_MFMA(0, acc, 2, 4, b1, a1)
-        if constexpr (SPLITB) { G_LGKM(0) }
-        G_MFMA(1, acc, 2, 4, b1, a1)
-        __builtin_amdgcn_s_setprio(0);
-        G_SEG_END()
-        // ---------------- phase 3: (A0, B1): no fragment reads ----------------
-        stage(1, kt + 2);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        G_SEG_END()
-        __builtin_amdgcn_s_setprio(1);
-        G_MFMA(0, acc, 2, 0, b1, a0)
-        G_MFMA(1, acc, 2, 0, b1, a0)
-        __builtin_amdgcn_s_setprio(0);
-        G_SEG_END()
-    }
-#undef G_MFMA
-#undef G_SEG_END
-#undef G_LOAD
-#undef G_LGKM
-    if (wr == 0) __builtin_amdgcn_s_barrier(); // pairs with the extra barrier of waves 4-7
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-    // ---- epilogue. acc[n][m][e] = C[m0 + wr*128 + m*16 + (lane & 15)][n0 + wc*64 + n*16 + (lane >> 4)*4 + e]:
-    // four consecutive columns per lane. Column tiles n and n + 1 are neighbours, so one v_permlane16_swap per register
-    // pair (16-lane row 1 of tile n <-> row 0 of tile n + 1, row 3 <-> row 2) leaves every lane with EIGHT consecutive
-    // columns: one 16-byte store per lane, 64 contiguous bytes per C row per instruction instead of 32 (8-byte stores
-    // wrote 2.4x the algorithmic bytes beyond L2). A transposed-read operand splits its 256 rows / columns into halves
-    // 0..127 | 128..255 instead (whole 256-B lines per DMA row), so a wave's tiles are then
-    // {half*128 + wr*64 + ..} / {half*128 + wc*32 + ..}.
-    uint16_t *C = (uint16_t *)g.C;
-    const bool wide = g.ldc % 8 == 0 && (uintptr_t)g.C % 16 == 0;
-    auto colbase = [&](int n) { return TRB ? (n >> 1) * 128 + wc * 32 + (n & 1) * 16 : wc * 64 + n * 16; };
-#pragma unroll
-    for (int np = 0; np < 4; np += 2) {
-        float bias[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        if (g.epilogue == KF_EPI_BIAS_ROW) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const uint16_t bb = ((const uint16_t *)g.bias)[n0 + colbase(np + t) + fg * 4 + e];
-                    bias[t][e] = BF ? bf16_to_f32(bf16_t{bb}) : f16_to_f32(f16_t{bb});
-                }
-        }
-        // after the exchange: lane rows 0 / 2 hold columns 0..7 / 8..15 of tile np, rows 1 / 3 those of tile np + 1
-        const int64_t col = n0 + ((fg & 1) ? colbase(np + 1) : colbase(np)) + (fg >> 1) * 8;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int64_t row = m0 + (TRA ? (m >> 2) * 128 + wr * 64 + (m & 3) * 16 : wr * 128 + m * 16) + fr;
-            uint16_t *dst = C + row * g.ldc + col;
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float lo = g.alpha * acc[np][m][e] + bias[0][e], hi = g.alpha * acc[np + 1][m][e] + bias[1][e];
-                const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
-                v[e] = __uint_as_float(sw[0]);
-                v[4 + e] = __uint_as_float(sw[1]);
-            }
-            if (g.beta != 0.f) {
-                uint32_t ow[4];
-                if (wide) {
-                    const uint4 old = *(const uint4 *)dst;
-                    ow[0] = old.x, ow[1] = old.y, ow[2] = old.z, ow[3] = old.w;
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ow[e] = (uint32_t)dst[2 * e] | ((uint32_t)dst[2 * e + 1] << 16);
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const uint16_t o = (uint16_t)(ow[e >> 1] >> ((e & 1) * 16));
-                    v[e] += g.beta * (BF ? bf16_to_f32(bf16_t{o}) : f16_to_f32(f16_t{o}));
-                }
-            }
-            h_epi8<BF>(g, row, col, v);
-            uint32_t w[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                w[e] = g_pack2<BF>(v[2 * e], v[2 * e + 1]);
-            }
-            if (wide) {
-                *(uint4 *)dst = uint4{w[0], w[1], w[2], w[3]};
-            } else { // C rows not 16-byte aligned
-#pragma unroll
-                for (int e = 0; e < 8; ++e) dst[e] = (uint16_t)(w[e >> 1] >> ((e & 1) * 16));
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// bf16 / f16, large shapes, second form: the same 256 x 256 x 64 block tile and the same LDS images, but FOUR waves
-// (2 x 2, 128 x 128 of C per wave), ONE wave per SIMD with the whole register file: 256 accumulator registers (AGPRs)
-// + two sets of fragments (2 x 64 VGPRs). A wave reads each LDS byte for 128 rows / columns of MFMA work instead of 64
-// (LDS traffic per K tile 128 KiB instead of 192), there is ONE barrier per K tile instead of eight, and nothing
-// depends on a partner wave: the fragments of the next k-step are read under the 64 MFMAs of the current one.
-//     S0: 64 MFMAs of (tile t, k-step 0) | under them: read fragments (t, k-step 1)
-//     P : s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier   - tile t + 1 has landed for everyone, tile t's buffer is free
-//     S1: 64 MFMAs of (t, k-step 1)      | under them: 16 DMA operations of tile t + 2, read fragments (t + 1, k-step 0)
-// Half-tiles: HA0 / HA1 = rows 0..127 / 128..255 of the A tile, HB0 / HB1 likewise for B; wave (wr, wc) reads HA[wr], HB[wc].
 // Where a 4096^3 launch's 110 us go (round 3, random operands, back to back; each row = the kernel with parts compiled out): MFMAs alone
 // 71 us (2048 cycles per K tile at 2.2 GHz + 12 us of launch, prologue and epilogue), + the LDS-DMA stream 83, + the fragment reads 94,
 // everything 110; the data movement without the MFMAs 67. No single unit is the bound - every activity added lowers the clock the power
@@ -1051,6 +752,11 @@ __global__ __launch_bounds__(G_NT, 2) void gemm_h256_kernel(const GemmArgs g) {
 // the next tile's first MFMAs behind a counted wait. Bit-identical, and within +-3 % of one tile per workgroup on every shape measured in
 // one process (4096 x 12288 x 4096 ... 8192^3): the dispatcher already starts the next workgroup as fast as a tile loop does.)
 // ------------------------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+constexpr int G_BM = 256, G_BN = 256, G_BK = 64;
+constexpr int G_HALF = 128 * G_BK * 2 + 256; // 16 KiB + the transposed image's padding (32 B x 7, rounded up)
+constexpr int G_TILE = 4 * G_HALF;          // HA0 | HB0 | HA1 | HB1
+constexpr int G_LDS = 2 * G_TILE;           // 130 KiB
 constexpr int W4_NT = 256;
 #ifndef W4_DMA_GROUPS
 #define W4_DMA_GROUPS 16 // the 16 LDS-DMA operations of a K tile go behind the first W4_DMA_GROUPS x 4 MFMAs after the barrier (4, 8 or 16)
@@ -1111,7 +817,8 @@ __device__ __forceinline__ void gemm_w4_body(const GemmArgs &g, const uint32_t b
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
     };
 
-    // ---- fragment reads (same images and address forms as gemm_h256_kernel)
+    // ---- fragment reads. K-contiguous image: row r of a 16-row tile, k-chunk (ks*4 + lane>>4), XOR swizzle on (row>>1)&7.
+    // Transposed image: per-lane address of tile 0's low row quad; tile t is this XOR (16-B chunk index ^ 2 t), see above.
     const int fr = lane & 15, fg = lane >> 4;
     const int sw = (fr >> 1) & 7;
     const int offk[2] = {fr * 128 + (((0 + fg) ^ sw) << 4), fr * 128 + (((4 + fg) ^ sw) << 4)};
@@ -1263,7 +970,10 @@ __device__ __forceinline__ void gemm_w4_body(const GemmArgs &g, const uint32_t b
                  :
                  : "memory");
 
-    // ---- epilogue: as gemm_h256_kernel's (lane exchange between neighbouring column tiles, 16-byte stores)
+    // ---- epilogue. acc[n][m][e] = C[m0 + wr*128 + m*16 + (lane & 15)][n0 + wc*128 + n*16 + (lane >> 4)*4 + e]: four consecutive
+    // columns per lane. Column tiles n and n + 1 are neighbours, so one v_permlane16_swap per register pair (16-lane row 1 of tile n
+    // <-> row 0 of tile n + 1, row 3 <-> row 2) leaves every lane with EIGHT consecutive columns: one 16-byte store per lane, 64
+    // contiguous bytes per C row per instruction instead of 32 (8-byte stores wrote 2.4x the algorithmic bytes beyond L2).
     uint16_t *C = (uint16_t *)g.C;
     const bool wide = g.ldc % 8 == 0 && (uintptr_t)g.C % 16 == 0;
 #pragma unroll
@@ -1423,12 +1133,12 @@ using namespace kf;
 
 // the 256-tile kernel when its grid covers a good part of the chip (256 CUs, one block each); smaller problems get four
 // times as many 128-tile blocks instead (2048^3: 64 tiles of 256^2 would leave three quarters of the CUs idle).
-// Where the line is (round 5, random bf16 operands, back to back, KF_GEMM_H256_MIN): 64 tiles 394 vs 721 TFLOP/s for the 128-tile kernel,
+// Where the line is (round 5, random bf16 operands, back to back): 64 tiles 394 vs 721 TFLOP/s for the 128-tile kernel,
 // 81 tiles 573 vs 595, 100 tiles 592-610 vs 532-592, 121 tiles 720-752 vs 627-656, 128 tiles 816-850 vs 704-724, 144 tiles (3072^3) 886-923
 // vs 599 - the line had stood at 160 tiles.
+constexpr int64_t H256_MIN_TILES = 100;
 static bool h256_ok(int64_t M, int64_t N, int64_t K) {
-    return M % G_BM == 0 && N % G_BN == 0 && K % G_BK == 0 && M > 0 && N > 0 && K > 0 && (M / G_BM) * (N / G_BN) >= knob_int(KNOB_GEMM_H256_MIN, 100) &&
-           !knob(KNOB_GEMM_128);
+    return M % G_BM == 0 && N % G_BN == 0 && K % G_BK == 0 && M > 0 && N > 0 && K > 0 && (M / G_BM) * (N / G_BN) >= H256_MIN_TILES;
 }
 
 // Split-K plan: only where the 128-tile 16-bit kernel would leave most of the chip idle (at most 128 tiles = half a round of 256 CUs)
@@ -1491,24 +1201,10 @@ extern "C" int kf_gemm_workspace_bytes(int dtype, int trans_a, int trans_b, int6
     return KF_OK;
 }
 
-// Round 3: the 4-wave form on every grid. It used to win only up to two rounds of tiles; with its transposed reads spread over the MFMA
-// gaps and the shorter epilogue it is ahead of the 8-wave form everywhere measured (tools/scratch/w4_vs_w8.py, same process, interleaved):
-// 4096 x 12288 x 4096 NN 1258 vs 1120 TFLOP/s, TN 1234 vs 1091; 4096 x 4096 x 16384 TN 1315 vs 1130; 8192^3 NN 1396 vs 1264, NT 1454
-// vs 1390; 5120^3 TN 1058 vs 934. KF_GEMM_W8 still selects the 8-wave kernel (tests keep it covered).
-static bool h256_use_w4(int64_t M, int64_t N) {
-    (void)M; (void)N;
-    return !knob(KNOB_GEMM_W8);
-}
-
 template <bool BF>
-static int launch_h256(const GemmArgs &g, bool tra, bool trb, bool w4, hipStream_t st) {
+static int launch_h256(const GemmArgs &g, bool tra, bool trb, hipStream_t st) {
     const unsigned grid = (unsigned)((g.M / G_BM) * (g.N / G_BN));
     const bool tail = g.mul || g.add || g.aux;
-#define KF_H256(TA, TB)                                                                                                   \
-    {                                                                                                                     \
-        KF_ENSURE_LDS((gemm_h256_kernel<BF, TA, TB>), G_LDS); \
-        gemm_h256_kernel<BF, TA, TB><<<grid, G_NT, G_LDS, st>>>(g);                                                       \
-    }
 #define KF_W4(TA, TB)                                                                                                     \
     {                                                                                                                     \
         if (tail) {                                                                                                       \
@@ -1519,20 +1215,11 @@ static int launch_h256(const GemmArgs &g, bool tra, bool trb, bool w4, hipStream
             gemm_w4_kernel<BF, TA, TB><<<grid, W4_NT, G_LDS, st>>>(g);                                                    \
         }                                                                                                                 \
     }
-    if (w4) {
-        if (!tra && !trb) KF_W4(false, false)
-        else if (!tra && trb) KF_W4(false, true)
-        else if (tra && !trb) KF_W4(true, false)
-        else KF_W4(true, true)
-        KF_LAUNCH_CHECK();
-        return KF_OK;
-    }
+    if (!tra && !trb) KF_W4(false, false)
+    else if (!tra && trb) KF_W4(false, true)
+    else if (tra && !trb) KF_W4(true, false)
+    else KF_W4(true, true)
 #undef KF_W4
-    if (!tra && !trb) KF_H256(false, false)
-    else if (!tra && trb) KF_H256(false, true)
-    else if (tra && !trb) KF_H256(true, false)
-    else KF_H256(true, true)
-#undef KF_H256
     KF_LAUNCH_CHECK();
     return KF_OK;
 }
@@ -1565,7 +1252,7 @@ extern "C" int kf_gemm(int dtype, int trans_a, int trans_b, int64_t M, int64_t N
 static bool grouped_single_grid(int dtype, int count, const kf_gemm_problem *p) {
     const bool half = dtype == KF_BF16 || dtype == KF_F16;
     auto pair_ok = [&](const kf_gemm_problem &q) {
-        return q.A && q.B && q.C && h_fast_ok(q.M, q.N, q.K) && h256_ok(q.M, q.N, q.K) && h256_use_w4(q.M, q.N) && ((q.M / G_BM) * (q.N / G_BN)) % 8 == 0 &&
+        return q.A && q.B && q.C && h_fast_ok(q.M, q.N, q.K) && h256_ok(q.M, q.N, q.K) && ((q.M / G_BM) * (q.N / G_BN)) % 8 == 0 &&
                (uintptr_t)q.A % 16 == 0 && (uintptr_t)q.B % 16 == 0 && q.lda % 8 == 0 && q.ldb % 8 == 0 && q.ldc >= q.N &&
                q.lda >= (q.trans_a ? q.M : q.K) && q.ldb >= (q.trans_b ? q.K : q.N);
     };
@@ -1583,7 +1270,7 @@ extern "C" int kf_gemm_grouped(int dtype, int count, const kf_gemm_problem *p, v
         GemmArgs g1{p[1].A, p[1].B, p[1].C, nullptr, p[1].M, p[1].N, p[1].K, p[1].lda, p[1].ldb, p[1].ldc, p[1].alpha, p[1].beta, KF_EPI_NONE, 0};
         g0.c_f32 = p[0].c_f32 ? 1 : 0;
         g1.c_f32 = p[1].c_f32 ? 1 : 0;
-        g0.group_m = g1.group_m = (int)knob_int(KNOB_GEMM_GROUP_M, 4);
+        g0.group_m = g1.group_m = 4;
         const unsigned n0 = (unsigned)((p[0].M / G_BM) * (p[0].N / G_BN)), n1 = (unsigned)((p[1].M / G_BM) * (p[1].N / G_BN));
         KF_PROF(dtype == KF_BF16 ? "gemm_bf16_mfma_pair" : "gemm_f16_mfma_pair", st);
         if (dtype == KF_BF16) {
@@ -1635,8 +1322,8 @@ static int gemm_impl(int dtype, int trans_a, int trans_b, int64_t M, int64_t N, 
     if (ex) { g.mul = ex->mul; g.add = ex->add; g.aux = ex->aux; g.ldmul = ex->ldmul; g.ldadd = ex->ldadd; g.ldaux = ex->ldaux; g.c_f32 = ex->c_f32 ? 1 : 0; }
     KF_REQUIRE(!g.c_f32 || dtype == KF_BF16 || dtype == KF_F16, KF_ERR_INVALID, "kf_gemm_ex: c_f32 asks for a float output behind 16-bit operands (dtype %d)", dtype);
     // tile rows per group of the XCD-aware tile walk: 4, and 8 once the grid is >= 1024 tiles of 256^2 (8192^3 NN: 1187 -> 1234 TFLOP/s per
-    // launch, same box, tools/scratch/gemm_stride.py; 2..8 alike at 768 tiles, 1 and 16 behind everywhere)
-    g.group_m = (int)knob_int(KNOB_GEMM_GROUP_M, (M / 256) * (N / 256) >= 1024 ? 8 : 4);
+    // launch, same box; 2..8 alike at 768 tiles, 1 and 16 behind everywhere)
+    g.group_m = (M / 256) * (N / 256) >= 1024 ? 8 : 4;
 
     const bool al16 = ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0);
     if (dtype == KF_F32 && M % 64 == 0 && N % 64 == 0 && K % F_BK == 0 && K > 0 && al16 && lda % 4 == 0 && ldb % 4 == 0) {
@@ -1656,7 +1343,7 @@ static int gemm_impl(int dtype, int trans_a, int trans_b, int64_t M, int64_t N, 
         KF_LAUNCH_CHECK();
         return KF_OK;
     }
-    if (dtype == KF_F64 && M % D_T == 0 && N % D_T == 0 && K % D_BK == 0 && K > 0 && al16 && lda % 2 == 0 && ldb % 2 == 0 && !knob(KNOB_GEMM_F64_GENERIC)) {
+    if (dtype == KF_F64 && M % D_T == 0 && N % D_T == 0 && K % D_BK == 0 && K > 0 && al16 && lda % 2 == 0 && ldb % 2 == 0) {
         const unsigned grid = (unsigned)((M / D_T) * (N / D_T));
         KF_PROF("gemm_f64_mfma", st);
         if (!trans_a && !trans_b) gemm_f64_kernel<false, false><<<grid, 256, 0, st>>>(g);
@@ -1670,9 +1357,8 @@ static int gemm_impl(int dtype, int trans_a, int trans_b, int64_t M, int64_t N, 
         if (h256_ok(M, N, K)) { // every operand layout is consumed in place
             // products with mul / add / aux operands take the 4-wave kernel's tail instantiation (round 3; same loop, same accumulation
             // order, so aux is bit-identical to the plain product)
-            const bool w4 = h256_use_w4(M, N) || g.c_f32; // profile labels name the kernel that ran (tests assert them); the float output lives in the 4-wave kernel
-            KF_PROF(dtype == KF_BF16 ? (w4 ? "gemm_bf16_mfma" : "gemm_bf16_mfma_w8") : (w4 ? "gemm_f16_mfma" : "gemm_f16_mfma_w8"), st);
-            return dtype == KF_BF16 ? launch_h256<true>(g, trans_a != 0, !trans_b, w4, st) : launch_h256<false>(g, trans_a != 0, !trans_b, w4, st);
+            KF_PROF(dtype == KF_BF16 ? "gemm_bf16_mfma" : "gemm_f16_mfma", st);
+            return dtype == KF_BF16 ? launch_h256<true>(g, trans_a != 0, !trans_b, st) : launch_h256<false>(g, trans_a != 0, !trans_b, st);
         }
         unsigned grid = (unsigned)((M / H_BM) * (N / H_BN));
         const size_t lds = (size_t)H_STAGES * 2 * H_TILE_BYTES;

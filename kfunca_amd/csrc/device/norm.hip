@@ -482,14 +482,13 @@ static NormPlan norm_plan(int dtype, int64_t cols, int64_t ldx, const void *cons
     // rows of up to 32 packs (512 B): 8, 16 or 32 lanes per row, 32 / 16 / 8 rows per block - a whole wave on a 128-byte row left 56 of its 64 lanes idle
     // (round 5, bf16 [4 Mi, 64]: forward 0.9 TB/s, backward 0.9)
     for (int t = 8; t <= 32; t *= 2)
-        if (npk <= t && (!bwd || knob_int(KNOB_NORM_BWD_TPR, 0) == 0)) return {t, 1};
+        if (npk <= t) return {t, 1};
     if (bwd) {
-        const long forced = knob_int(KNOB_NORM_BWD_TPR, 0); // A/B switch: threads per row (64 | 256 | 512 | 1024)
-        for (int p = 1; p <= (forced == 64 ? 4 : 2); p *= 2) // short rows: one wave per row (no barrier), up to 2 packs per lane (4 packs without a row ahead:
-            if (npk <= 64 * p && (forced == 0 || forced == 64)) return {64, p}; // bf16 [131072, 2048] 4.2 - 4.4 TB/s against 5.05 with the row across one 256-thread block)
+        for (int p = 1; p <= 2; p *= 2) // short rows: one wave per row (no barrier), up to 2 packs per lane (4 packs without a row ahead:
+            if (npk <= 64 * p) return {64, p}; // bf16 [131072, 2048] 4.2 - 4.4 TB/s against 5.05 with the row across one 256-thread block)
         for (int p = 1; p <= 2; ++p) // longer ones: one pack per lane wherever 1024 threads reach (the fewest registers), two beyond
             for (int t = 256; t <= 1024; t *= 2)
-                if (npk <= (int64_t)t * p && (forced == 0 || forced == t || (p == 2 && t == 1024))) return {t, p};
+                if (npk <= (int64_t)t * p) return {t, p};
         return {0, 0};
     }
     if (npk <= 64 * 4) { // one wave per row, up to 4 packs per lane (4 KiB rows)

@@ -6,7 +6,7 @@ sampled output rows / sampled (batch, head) pairs with the CPU oracle — the or
 subset of attention, so the check costs seconds while the launch is the real one.
 
   C2  fp32 4096^3 fwd + bwd            -> gemm_f32_mfma (the 128-tile form of gemm_f32_kernel), bit-exact vs the fma chain
-  C4  bf16 8192 x 8192 x K + epilogue  -> gemm_bf16_mfma (the 4-wave 256-tile kernel: every grid since round 3) and, forced, gemm_bf16_mfma_w8; all four layouts, alpha / beta / bias
+  C4  bf16 8192 x 8192 x K + epilogue  -> gemm_bf16_mfma (the 4-wave 256-tile kernel); all four layouts, alpha / beta / bias
   C3  bf16 attention B8 H32 S4096 D128 -> forward and the backward kernels with the XCD block map on
 Reference bars: test/test_gemm.py:9-17, test/test_nn.py:11-33, test/common.py:6-11.
 """
@@ -69,17 +69,12 @@ def _bf16_rows_check(got, want64, mag, eps=2.0 ** -8, scale=1.0):
     assert (np.abs(got - want64) <= scale * eps * np.abs(want64) + scale * 1e-6 * mag + scale * eps * 1e-3).all()
 
 
-@pytest.mark.parametrize("K,w8", [(512, False), (8192, False), (512, True)])
-def test_c4_bf16_8192_epilogue_on_both_256_tile_kernels(K, w8):
-    """8192 x 8192 x K bf16 with alpha / beta and the fused bias row: 1024 tiles of 256^2 -> the 4-wave kernel (every grid since
-    round 3: it is ahead of the 8-wave form at every size measured), and the 8-wave kernel forced with KF_GEMM_W8. K = 512 sweeps
-    all four layouts; K = 8192 is config C4 itself (NN and NT). Sampled rows against the oracle (bf16 inputs, f32
+@pytest.mark.parametrize("K", [512, 8192])
+def test_c4_bf16_8192_epilogue_on_the_256_tile_kernel(K):
+    """8192 x 8192 x K bf16 with alpha / beta and the fused bias row: 1024 tiles of 256^2 -> the 4-wave 256-tile kernel. K = 512
+    sweeps all four layouts; K = 8192 is config C4 itself (NN and NT). Sampled rows against the oracle (bf16 inputs, f32
     accumulation, one rounding) and against f64 numpy with the bound of tests/test_gpu_gemm.py."""
-    with H.knobs(KF_GEMM_W8="1" if w8 else None, KF_GEMM_W4=None):
-        _c4_case(K, "gemm_bf16_mfma_w8" if w8 else "gemm_bf16_mfma")
-
-
-def _c4_case(K, label):
+    label = "gemm_bf16_mfma"
     M = N = 8192
     rng = np.random.default_rng(1004 + K)
     bits = lambda shape: O.f32_to_bf16(rng.uniform(-1, 1, shape).astype(np.float32))
@@ -116,12 +111,12 @@ def _c4_case(K, label):
 
 
 @pytest.mark.parametrize("code", [H.BF16, H.F16])
-def test_8_wave_kernel_forced_at_an_oracle_sized_shape(code):
-    """KF_GEMM_W8 forces the 8-wave kernel on a 160-tile grid (2560 x 4096, K = 192): the WHOLE output against the oracle for
+def test_256_tile_kernel_at_an_oracle_sized_shape(code):
+    """The 4-wave 256-tile kernel on a 160-tile grid (2560 x 4096, K = 192): the WHOLE output against the oracle for
     every layout, plus small-integer operands (exact in 16 bits and in the f32 accumulation: any fragment / lane /
     transposed-read mistake is a wrong integer)."""
     eps = 2.0 ** -8 if code == H.BF16 else 2.0 ** -11
-    label = "gemm_bf16_mfma_w8" if code == H.BF16 else "gemm_f16_mfma_w8"
+    label = "gemm_bf16_mfma" if code == H.BF16 else "gemm_f16_mfma"
     rng = np.random.default_rng(88 + code)
     M, N, K = 2560, 4096, 192
     a = O.from_float(rng.uniform(-1, 1, (M, K)).astype(np.float32), code)
@@ -131,22 +126,21 @@ def test_8_wave_kernel_forced_at_an_oracle_sized_shape(code):
     af, bf_ = O.to_float(a, code).astype(np.float64), O.to_float(b, code).astype(np.float64)
     want, mag, want_i = af @ bf_, np.abs(af) @ np.abs(bf_), ai.astype(np.float64) @ bi.astype(np.float64)
     dc = H.DevBuf(2 * M * N)
-    with H.knobs(KF_GEMM_W8="1", KF_GEMM_W4=None):
-        for ta in (0, 1):
-            for tb in (0, 1):
-                for x, y, ref, exact in ((a, b, want, False), (O.from_float(ai, code), O.from_float(bi, code), want_i, True)):
-                    sa, sb = (np.ascontiguousarray(x.T) if ta else x), (np.ascontiguousarray(y.T) if tb else y)
-                    da, db = H.DevBuf.from_numpy(sa), H.DevBuf.from_numpy(sb)
-                    ran = gemm_dev(code, da, db, dc, M, N, K, ta, tb, sa.shape[1], sb.shape[1])
-                    assert ran == {label}, (ta, tb, ran)
-                    got = O.to_float(dc.to_numpy((M, N), x.dtype), code).astype(np.float64)
-                    if exact:
-                        ok = np.abs(ref) <= (256 if code == H.BF16 else 2048)
-                        assert np.array_equal(got[ok], ref[ok]), (code, ta, tb)
-                    else:
-                        assert (np.abs(got - ref) <= eps * np.abs(ref) + 1e-6 * mag + 1e-30).all(), (code, ta, tb)
-                        orc = O.to_float(O.gemm(sa, sb, trans_a=bool(ta), trans_b=bool(tb), code=code), code).astype(np.float64)
-                        assert (np.abs(got - orc) <= 2 * eps * np.abs(ref) + 2e-6 * mag + 1e-30).all(), "vs oracle"
+    for ta in (0, 1):
+        for tb in (0, 1):
+            for x, y, ref, exact in ((a, b, want, False), (O.from_float(ai, code), O.from_float(bi, code), want_i, True)):
+                sa, sb = (np.ascontiguousarray(x.T) if ta else x), (np.ascontiguousarray(y.T) if tb else y)
+                da, db = H.DevBuf.from_numpy(sa), H.DevBuf.from_numpy(sb)
+                ran = gemm_dev(code, da, db, dc, M, N, K, ta, tb, sa.shape[1], sb.shape[1])
+                assert ran == {label}, (ta, tb, ran)
+                got = O.to_float(dc.to_numpy((M, N), x.dtype), code).astype(np.float64)
+                if exact:
+                    ok = np.abs(ref) <= (256 if code == H.BF16 else 2048)
+                    assert np.array_equal(got[ok], ref[ok]), (code, ta, tb)
+                else:
+                    assert (np.abs(got - ref) <= eps * np.abs(ref) + 1e-6 * mag + 1e-30).all(), (code, ta, tb)
+                    orc = O.to_float(O.gemm(sa, sb, trans_a=bool(ta), trans_b=bool(tb), code=code), code).astype(np.float64)
+                    assert (np.abs(got - orc) <= 2 * eps * np.abs(ref) + 2e-6 * mag + 1e-30).all(), "vs oracle"
 
 
 def _rand16(rng, shape, code):

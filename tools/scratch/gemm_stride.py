@@ -41,8 +41,3 @@ for (M, N, K) in ((8192, 8192, 8192), (4096, 12288, 4096), (4096, 4096, 4096)):
     Bt = H.DevBuf.from_numpy(bf16(rng, (N, K)))
     p, b = t(lambda: H.gemm(H.BF16, 0, 1, M, N, K, 1.0, A.ptr, K, Bt.ptr, K, 0.0, C.ptr, N, 0, None, None, 0))
     print(f"{M}x{N}x{K} NT               : per launch {p:.4f} ms {fl / p / 1e9:7.1f} TF/s | back to back {b:.4f} ms {fl / b / 1e9:7.1f} TF/s", flush=True)
-    for gm in (1, 2, 4, 8, 16):
-        B = H.DevBuf.from_numpy(bf16(rng, (K, N)))
-        with H.knobs(KF_GEMM_GROUP_M=str(gm)):
-            p, b = t(lambda: H.gemm(H.BF16, 0, 0, M, N, K, 1.0, A.ptr, K, B.ptr, N, 0.0, C.ptr, N, 0, None, None, 0))
-        print(f"{M}x{N}x{K} NN group_m {gm:2d}    : per launch {p:.4f} ms {fl / p / 1e9:7.1f} TF/s | back to back {b:.4f} ms {fl / b / 1e9:7.1f} TF/s", flush=True)
