@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define KF_ABI_VERSION 7 /* 7 (no signature changed): kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
+#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
 
 /* ---- status ------------------------------------------------------------------------------ */
 enum {
@@ -222,6 +222,40 @@ int kf_norm_bwd_workspace_bytes(int kind, int dtype, int64_t rows, int64_t cols,
 int kf_norm_bwd(int kind, int dtype, int64_t rows, int64_t cols, int64_t ld, const void *x, const void *weight, const float *mean,
                 const float *rstd, const void *dy, void *dx, void *dweight, void *dbias, void *workspace, size_t workspace_bytes,
                 void *stream);
+
+/* ---- softmax cross-entropy over the last dimension (no reference counterpart: the loss that ends a language model's chain) --- */
+enum {
+    KF_CE_NONE = 0, /* loss[r] per row                                   */
+    KF_CE_SUM = 1,  /* loss[0] = sum of the rows' losses                 */
+    KF_CE_MEAN = 2  /* loss[0] = that sum / the number of rows not ignored */
+};
+/*
+ * logits: [rows, V] with row stride `ld` elements (ld >= V), dtype in {KF_F32, KF_BF16, KF_F16}, aligned to its element size; target:
+ * int64 [rows] on the device. torch's F.cross_entropy, with the class axis LAST (torch takes dim 1 of an N-d input):
+ *     lse_r  = log(sum_v exp(x_rv))
+ *     loss_r = (1 - eps) (lse_r - x_r,t) + eps (lse_r - mean_v x_rv)             eps = label_smoothing in [0, 1], t = target[r]
+ *     dx_rv  = g_r (exp(x_rv - lse_r) - (1 - eps) [v == t] - eps / V)
+ * A row whose target is ignore_index has loss 0 and a zero gradient row and does not count toward the mean (every row ignored: the
+ * mean is NaN, as torch's). A target outside [0, V) that is not ignore_index gives that row a NaN loss and a NaN gradient row and
+ * disturbs no other row - unlike torch, which asserts on the device; nothing here reads out of bounds or synchronises to check.
+ * -inf logits (a masked vocabulary padding) are fine.
+ * Forward: loss is f32 [rows] for KF_CE_NONE, [1] otherwise; lse [rows] f32 (NULL: not kept; the backward needs it) is written for
+ * every row; count [1] f32 (NULL: not kept; the mean's backward needs it) receives the number of rows not ignored. The sums run in a
+ * fixed order through caller scratch of kf_cross_entropy_workspace_bytes() bytes (no initialisation, no atomics: bitwise
+ * reproducible). How a row is cut depends on (rows, V) only: V <= 4096 one wave per row; else rows >= 1024 one block per row; else
+ * each row splits into chunks whose partial (max, sum of exponentials, sum x) go to the scratch and are merged in chunk order.
+ * Backward: dlogits [rows, V] in the logits' dtype with row stride ldd; grad is f32 [rows] for KF_CE_NONE, a device scalar [1]
+ * otherwise; the mean's divisor is read from count on the device. Neither entry synchronises or allocates: both can be captured
+ * with kf_graph_*. Every argument is checked before any device call: KF_ERR_INVALID (null pointers, V < 1, ld < V, dtype, reduction,
+ * label_smoothing, a workspace that is too small).
+ */
+int kf_cross_entropy_workspace_bytes(int dtype, int64_t rows, int64_t V, int reduction, size_t *bytes);
+int kf_cross_entropy_fwd(int dtype, int64_t rows, int64_t V, int64_t ld, const void *logits, const int64_t *target, int64_t ignore_index,
+                         float label_smoothing, int reduction, float *loss, float *lse, float *count, void *workspace,
+                         size_t workspace_bytes, void *stream);
+int kf_cross_entropy_bwd(int dtype, int64_t rows, int64_t V, int64_t ld, const void *logits, const int64_t *target, int64_t ignore_index,
+                         float label_smoothing, int reduction, const float *lse, const float *count, const float *grad, void *dlogits,
+                         int64_t ldd, void *stream);
 
 /* ---- index_put_: replaces index_ops_kernel.h:5 --------------------------------------------- */
 /*

@@ -313,6 +313,15 @@ PYBIND11_MODULE(_C, m) {
         return gpu::layer_norm(x, w.is_none() ? Tensor() : w.cast<Tensor>(), b.is_none() ? Tensor() : b.cast<Tensor>(), eps);
     }, py::arg("x"), py::arg("weight") = py::none(), py::arg("bias") = py::none(), py::arg("eps") = 1e-5);
     m.def("embedding", &gpu::embedding, py::arg("table"), py::arg("indices"));
+    // torch's F.cross_entropy argument names; the class axis is the LAST dim of logits
+    m.def("cross_entropy", [](const Tensor &logits, const Tensor &target, int64_t ignore_index, const std::string &reduction, double label_smoothing) {
+        int r = -1;
+        if (reduction == "none") r = KF_CE_NONE;
+        else if (reduction == "sum") r = KF_CE_SUM;
+        else if (reduction == "mean") r = KF_CE_MEAN;
+        CHECK_FAIL(r >= 0, reduction, " is not a valid value for reduction");
+        return gpu::cross_entropy(logits, target, ignore_index, r, label_smoothing);
+    }, py::arg("logits"), py::arg("target"), py::arg("ignore_index") = -100, py::arg("reduction") = "mean", py::arg("label_smoothing") = 0.0);
     m.def("gemm_fused", [](const Tensor &a, const Tensor &b, float alpha, py::object bias, py::object mul, py::object add) {
         auto opt = [](py::object o) { return o.is_none() ? Tensor() : o.cast<Tensor>(); };
         return gpu::gemm_fused(a, b, alpha, opt(bias), opt(mul), opt(add));

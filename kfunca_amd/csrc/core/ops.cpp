@@ -972,6 +972,74 @@ Tensor norm_impl(int kind, const Tensor &x, const Tensor &w, const Tensor &b, do
 Tensor rms_norm(const Tensor &x, const Tensor &weight, double eps) { return norm_impl(KF_NORM_RMS, x, weight, Tensor(), eps); }
 Tensor layer_norm(const Tensor &x, const Tensor &weight, const Tensor &bias, double eps) { return norm_impl(KF_NORM_LAYER, x, weight, bias, eps); }
 
+// ---- cross_entropy: the loss at the end of a language model (kf_cross_entropy_*) --------------------------------------------------
+namespace {
+// saved for the backward: logits, target and the forward's f32 lse per row and count of rows not ignored
+class CrossEntropyGradFunction : public GradFunction {
+public:
+    CrossEntropyGradFunction(const Tensor &logits, const Tensor &target, const Tensor &lse, const Tensor &count, int64_t ignore_index,
+                             int reduction, float label_smoothing)
+        : target_(target), lse_(lse), count_(count), ignore_index_(ignore_index), reduction_(reduction), label_smoothing_(label_smoothing) {
+        inputs = {logits};
+    }
+    std::vector<Tensor> backward(Tensor g) override {
+        const Tensor &x = inputs[0];
+        const int64_t V = x.shape(-1), rows = x.numel() / V;
+        Tensor gc = g.dense();
+        CHECK_FAIL(gc.dtype() == ScalarType::Float && gc.numel() == (reduction_ == KF_CE_NONE ? rows : 1), "cross_entropy backward: unexpected gradient");
+        Tensor dx = empty(x.sizes(), x.dtype(), x.device());
+        DEV_CALL(kf_cross_entropy_bwd(code(x.dtype()), rows, V, V, x.data_ptr(), static_cast<const int64_t *>(target_.data_ptr()), ignore_index_,
+                                      label_smoothing_, reduction_, static_cast<const float *>(lse_.data_ptr()),
+                                      count_.defined() ? static_cast<const float *>(count_.data_ptr()) : nullptr,
+                                      static_cast<const float *>(gc.data_ptr()), dx.data_ptr(), V, dev::stream(x.device())));
+        return {dx};
+    }
+
+private:
+    Tensor target_, lse_, count_;
+    int64_t ignore_index_;
+    int reduction_;
+    float label_smoothing_;
+};
+} // namespace
+
+Tensor cross_entropy(const Tensor &logits, const Tensor &target, int64_t ignore_index, int reduction, double label_smoothing) {
+    CHECK_FAIL(logits.defined() && logits.dim() >= 1 && logits.is_dense(), "cross_entropy expects contiguous logits [..., V]");
+    CHECK_FAIL(norm_dtype_ok(logits.dtype()), "cross_entropy supports float, half and bfloat16 logits");
+    CHECK_FAIL(target.defined() && target.dtype() == ScalarType::Long, "cross_entropy: target must be of type Long");
+    CHECK_FAIL(target.device() == logits.device());
+    CHECK_FAIL(reduction == KF_CE_NONE || reduction == KF_CE_SUM || reduction == KF_CE_MEAN, "cross_entropy: unknown reduction ", reduction);
+    CHECK_FAIL(label_smoothing >= 0.0 && label_smoothing <= 1.0, "cross_entropy: label_smoothing must lie in [0, 1], got ", label_smoothing);
+    auto lead = logits.sizes();
+    lead.pop_back();
+    CHECK_FAIL(target.sizes() == lead, "cross_entropy: target must have the shape of logits without its last (class) dim");
+    const int64_t V = logits.shape(-1);
+    CHECK_FAIL(V > 0, "cross_entropy: no classes");
+    const int64_t rows = logits.numel() / V;
+    Tensor t = target.dense();
+    const int device = logits.device();
+    Tensor loss = empty(reduction == KF_CE_NONE ? lead : std::vector<int64_t>{1}, ScalarType::Float, device);
+    const bool grad = logits.requires_grad();
+    Tensor lse, count;
+    if (grad) {
+        lse = empty({rows}, ScalarType::Float, device);
+        if (reduction == KF_CE_MEAN) count = empty({1}, ScalarType::Float, device);
+    }
+    size_t need = 0;
+    DEV_CALL(kf_cross_entropy_workspace_bytes(code(logits.dtype()), rows, V, reduction, &need));
+    DataPtr scratch;
+    if (need) scratch = DeviceAllocator::GetInstance()->allocate(need, device);
+    DEV_CALL(kf_cross_entropy_fwd(code(logits.dtype()), rows, V, V, logits.data_ptr(), static_cast<const int64_t *>(t.data_ptr()), ignore_index,
+                                  (float)label_smoothing, reduction, static_cast<float *>(loss.data_ptr()),
+                                  lse.defined() ? static_cast<float *>(lse.data_ptr()) : nullptr,
+                                  count.defined() ? static_cast<float *>(count.data_ptr()) : nullptr, scratch.get(), need, dev::stream(device)));
+    if (grad) {
+        loss.set_requires_grad(true);
+        loss.set_grad_fn(new CrossEntropyGradFunction(logits, t, lse, count, ignore_index, reduction, (float)label_smoothing));
+    }
+    return loss;
+}
+
 // ---- embedding (README.md:30; index arithmetic of tensor_index.h:56-104) -------------------------------------------------------
 namespace {
 class EmbeddingGradFunction : public GradFunction { // dTable[r] = sum of the gradient rows gathered from r, in input order

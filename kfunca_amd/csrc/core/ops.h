@@ -69,6 +69,10 @@ Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H);
 //   reference API spells gemm + add + mul + add over three extra passes of the output. bias [N]; mul, add shaped like the output;
 //   any of the three may be undefined. Residual connection: add = the stream; gated MLP: mul = the other projection.
 Tensor gemm_fused(const Tensor &a, const Tensor &b, float alpha, const Tensor &bias, const Tensor &mul, const Tensor &add);
+//   cross_entropy: torch's F.cross_entropy over the LAST dim of logits [..., V] (f32 / f16 / bf16) with Long targets of shape
+//   logits.shape[:-1]; reduction KF_CE_NONE (loss shaped like target), KF_CE_SUM or KF_CE_MEAN ([1]); the loss is f32. A target
+//   outside [0, V) that is not ignore_index gives that row NaN (torch asserts instead).
+Tensor cross_entropy(const Tensor &logits, const Tensor &target, int64_t ignore_index, int reduction, double label_smoothing);
 
 // extensions used by the backward passes (no reference counterpart)
 Tensor gemm_ex(const Tensor &a, bool trans_a, const Tensor &b, bool trans_b, float alpha);

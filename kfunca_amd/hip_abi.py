@@ -26,6 +26,7 @@ RED_SUM, RED_MEAN = range(2)
 MOM_VAR, MOM_STD, MOM_INVSTD = range(3)
 EPI_NONE, EPI_BIAS_ROW = range(2)
 NORM_RMS, NORM_LAYER = range(2)
+CE_NONE, CE_SUM, CE_MEAN = range(3)
 MAX_DIMS, MAX_TENSORS = 12, 8
 KF_OK, KF_ERR_HIP, KF_ERR_INVALID, KF_ERR_UNSUPPORTED, KF_ERR_INDEX_RANGE, KF_ERR_WORKSPACE, KF_ERR_COMM, KF_ERR_OOM = range(8)
 COMM_ID_BYTES = 128
@@ -44,6 +45,7 @@ EXPORTS = [
     "kf_device_props_get", "kf_elementwise", "kf_reduce_workspace_bytes", "kf_reduce",
     "kf_reduce_moments_workspace_bytes", "kf_reduce_moments",
     "kf_norm_fwd", "kf_norm_bwd_workspace_bytes", "kf_norm_bwd",
+    "kf_cross_entropy_workspace_bytes", "kf_cross_entropy_fwd", "kf_cross_entropy_bwd",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
 ]
@@ -144,6 +146,9 @@ def lib():
         _lib.kf_norm_fwd.argtypes = [C.c_int, C.c_int, i64, i64, i64, vp, vp, vp, C.c_double, vp, vp, vp, vp]
         _lib.kf_norm_bwd_workspace_bytes.argtypes = [C.c_int, C.c_int, i64, i64, i64, C.POINTER(sz)]
         _lib.kf_norm_bwd.argtypes = [C.c_int, C.c_int, i64, i64, i64] + [vp] * 9 + [sz, vp]
+        _lib.kf_cross_entropy_workspace_bytes.argtypes = [C.c_int, i64, i64, C.c_int, C.POINTER(sz)]
+        _lib.kf_cross_entropy_fwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_int, vp, vp, vp, vp, sz, vp]
+        _lib.kf_cross_entropy_bwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_int, vp, vp, vp, vp, i64, vp]
         _lib.kf_index_put.argtypes = [C.POINTER(IterDesc), C.c_int, C.POINTER(i64), C.POINTER(i64), vp]
         _lib.kf_index_get.argtypes = [vp, i64, i64, vp, i64, vp, vp]
         _lib.kf_index_add_workspace_bytes.argtypes = [i64]
@@ -438,6 +443,29 @@ def norm_bwd(kind, dtype, rows, cols, x, weight, mean, rstd, dy, dx, dweight, db
     ws = DevBuf(need.value) if need.value else None
     check(lib().kf_norm_bwd(kind, dtype, rows, cols, ld, x, weight, mean, rstd, dy, dx, dweight, dbias, ws.ptr if ws else None, need.value, stream))
     return ws  # keep alive until the stream is synchronised
+
+
+def ce_workspace_bytes(dtype, rows, V, reduction):
+    need = C.c_size_t(0)
+    check(lib().kf_cross_entropy_workspace_bytes(dtype, rows, V, reduction, C.byref(need)))
+    return need.value
+
+
+def ce_fwd(dtype, rows, V, logits, target, loss, lse=None, count=None, ignore_index=-100, label_smoothing=0.0, reduction=CE_MEAN, ld=None,
+           stream=None):
+    """Softmax cross-entropy forward (kf_cross_entropy_fwd) with scratch of its own; returns the scratch (keep it until the stream is synchronised)."""
+    need = ce_workspace_bytes(dtype, rows, V, reduction)
+    ws = DevBuf(need) if need else None
+    check(lib().kf_cross_entropy_fwd(dtype, rows, V, V if ld is None else ld, logits, target, ignore_index, float(label_smoothing), reduction, loss,
+                                     lse, count, ws.ptr if ws else None, need, stream))
+    return ws
+
+
+def ce_bwd(dtype, rows, V, logits, target, lse, count, grad, dlogits, ignore_index=-100, label_smoothing=0.0, reduction=CE_MEAN, ld=None,
+           ldd=None, stream=None):
+    ld = V if ld is None else ld
+    check(lib().kf_cross_entropy_bwd(dtype, rows, V, ld, logits, target, ignore_index, float(label_smoothing), reduction, lse, count, grad,
+                                     dlogits, ld if ldd is None else ldd, stream))
 
 
 def index_put(desc: IterDesc, sizes, strides_bytes, stream=None):
