@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
+#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
 
 /* ---- status ------------------------------------------------------------------------------ */
 enum {
@@ -256,6 +256,40 @@ int kf_cross_entropy_fwd(int dtype, int64_t rows, int64_t V, int64_t ld, const v
 int kf_cross_entropy_bwd(int dtype, int64_t rows, int64_t V, int64_t ld, const void *logits, const int64_t *target, int64_t ignore_index,
                          float label_smoothing, int reduction, const float *lse, const float *count, const float *grad, void *dlogits,
                          int64_t ldd, void *stream);
+
+/* ---- fused AdamW step over a list of tensors (no reference counterpart: the optimizer that applies a gradient to a weight) --- */
+typedef struct kf_adamw_tensor {
+    int64_t numel;         /* elements of param, grad, master, exp_avg and exp_avg_sq (all contiguous, any size, 0 included) */
+    int param_dtype;       /* KF_F32, KF_BF16 or KF_F16 */
+    int grad_dtype;        /* KF_F32 or param_dtype */
+    void *param;
+    const void *grad;
+    float *master;         /* NULL, or the f32 copy of a 16-bit param: the update runs on it and param is rewritten from it (RNE) */
+    float *exp_avg;        /* f32 state */
+    float *exp_avg_sq;     /* f32 state */
+    float *step;           /* f32 [1] on the device: this tensor's step count, advanced by one per call on the device */
+    float weight_decay;    /* >= 0, decoupled (AdamW) */
+} kf_adamw_tensor;
+/*
+ * torch.optim.AdamW (no amsgrad, no maximize) over n tensors in one call, with torch.nn.utils.clip_grad_norm_ when max_grad_norm > 0.
+ * Per element, in f32, with g = grad * grad_scale * clip_coef and s = the tensor's step count after it advances:
+ *     p = p (1 - lr wd);  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p = p - (lr / (1 - b1^s)) m / (sqrt(v) / sqrt(1 - b2^s) + eps)
+ * lr is a device f32 [1] (a schedule may rewrite it between graph replays). Every step count advances by exactly one, on the device.
+ * Clipping: norm = sqrt(sum of (grad * grad_scale)^2 over every tensor), clip_coef = min(1, max_grad_norm / (norm + 1e-6)); per-block
+ * partial sums go to the caller's workspace and are folded in a fixed order (no atomics), so the call is bitwise reproducible.
+ * The grads are NOT rewritten (torch's clip_grad_norm_ scales them in place). A NaN norm makes every param NaN and an infinite one
+ * makes clip_coef 0, as torch with error_if_nonfinite=False. grad_norm (f32 [1], optional, clipping only) receives the norm before
+ * clipping; max_grad_norm = INFINITY computes it without clipping.
+ * Launches: 2 ceil(n / 48) without clipping, 2 ceil(n / 48) + 1 with (48 tensors' pointers travel in each launch's arguments).
+ * Pointers need only be aligned to their element size. The workspace (clipping only) is
+ *     kf_adamw_workspace_bytes = max_grad_norm > 0 ? 256 + 8192 ceil(n / 48) : 0 bytes.
+ * Neither entry synchronises or allocates: the step can be captured with kf_graph_*. Every argument is checked before any device
+ * call: KF_ERR_INVALID (null pointers, dtypes, negative numel, beta outside [0, 1), eps or weight_decay < 0, a master for an f32
+ * param, a workspace that is too small).
+ */
+int kf_adamw_workspace_bytes(int64_t n, float max_grad_norm, size_t *bytes);
+int kf_adamw_step(const kf_adamw_tensor *tensors, int64_t n, double beta1, double beta2, double eps, const float *lr, float grad_scale,
+                  float max_grad_norm, float *grad_norm, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- index_put_: replaces index_ops_kernel.h:5 --------------------------------------------- */
 /*

@@ -13,6 +13,7 @@
 #include "comm.h"
 #include "device_api.h"
 #include "ops.h"
+#include "optim.h"
 #include "tensor.h"
 #include "tensor_iterator.h"
 
@@ -280,6 +281,55 @@ PYBIND11_MODULE(_C, m) {
         }
         return x;
     });
+    // torch.optim.AdamW's constructor: params is a list of tensors or of groups {"params": [...], "weight_decay": wd}
+    py::class_<gpu::AdamW, std::shared_ptr<gpu::AdamW>>(m, "AdamW", py::module_local())
+        .def(py::init([](py::iterable params, double lr, std::pair<double, double> betas, double eps, double weight_decay, py::object max_grad_norm,
+                         double grad_scale, bool master_weights) {
+                 std::vector<gpu::AdamW::Group> groups;
+                 gpu::AdamW::Group plain{{}, weight_decay};
+                 for (py::handle h : params) {
+                     if (py::isinstance<py::dict>(h)) {
+                         py::dict d = py::reinterpret_borrow<py::dict>(h);
+                         gpu::AdamW::Group g{{}, weight_decay};
+                         for (auto kv : d) {
+                             const std::string key = py::str(kv.first);
+                             if (key == "params") {
+                                 if (py::isinstance<Tensor>(kv.second)) g.params.push_back(kv.second.cast<Tensor>());
+                                 else for (py::handle t : py::reinterpret_borrow<py::iterable>(kv.second)) g.params.push_back(t.cast<Tensor>());
+                             } else if (key == "weight_decay") {
+                                 g.weight_decay = kv.second.cast<double>();
+                             } else {
+                                 throw py::value_error("AdamW: parameter group key '" + key + "' is not supported (only 'params' and 'weight_decay')");
+                             }
+                         }
+                         if (!d.contains("params")) throw py::value_error("AdamW: a parameter group needs 'params'");
+                         groups.push_back(std::move(g));
+                     } else {
+                         plain.params.push_back(h.cast<Tensor>());
+                     }
+                 }
+                 if (!plain.params.empty()) {
+                     if (!groups.empty()) throw py::value_error("AdamW: params mixes tensors and parameter groups");
+                     groups.push_back(std::move(plain));
+                 }
+                 return std::make_shared<gpu::AdamW>(groups, lr, betas.first, betas.second, eps, max_grad_norm.is_none() ? 0.0 : max_grad_norm.cast<double>(),
+                                                     grad_scale, master_weights);
+             }),
+             py::arg("params"), py::arg("lr") = 1e-3, py::arg("betas") = std::make_pair(0.9, 0.999), py::arg("eps") = 1e-8, py::arg("weight_decay") = 1e-2,
+             py::arg("max_grad_norm") = py::none(), py::arg("grad_scale") = 1.0, py::arg("master_weights") = true)
+        .def("step", [](gpu::AdamW &o) -> py::object {
+            Tensor n = o.step();
+            if (!n.defined()) return py::none();
+            return py::cast(n);
+        })
+        .def("zero_grad", &gpu::AdamW::zero_grad)
+        .def("set_lr", &gpu::AdamW::set_lr, py::arg("lr"))
+        .def_property_readonly("lr", &gpu::AdamW::lr)
+        .def("state", [](const gpu::AdamW &o, const Tensor &p) -> py::tuple {
+            auto [m, v, s, ms] = o.state(p);
+            return py::make_tuple(m, v, s, ms.defined() ? py::cast(ms) : py::none());
+        }, py::arg("param"))
+        .def("__len__", &gpu::AdamW::size);
     py::class_<gpu::GradBucket, std::shared_ptr<gpu::GradBucket>>(m, "GradBucket", py::module_local())
         .def(py::init([](const std::vector<Tensor> &params, double cap_mb, bool accum_f32) {
                  return gpu::GradBucket::create(params, (int64_t)(cap_mb * 1048576.0), accum_f32);

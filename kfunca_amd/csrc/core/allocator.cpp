@@ -75,6 +75,11 @@ DataPtr DeviceAllocator::allocate(size_t size, int device) {
     return DataPtr(b->ptr, b->size, device);
 }
 
+bool DeviceAllocator::capture_open(int device) {
+    std::lock_guard<std::mutex> lk(mu_);
+    return capturing_ != 0 && capture_device_ == device;
+}
+
 void DeviceAllocator::free(void *ptr) {
     std::lock_guard<std::mutex> lk(mu_);
     auto it = by_ptr_.find(ptr);

@@ -64,6 +64,7 @@ public:
     uint64_t begin_capture(int device);
     void end_capture(uint64_t graph_id);
     void release_graph(uint64_t graph_id);
+    bool capture_open(int device);        // a capture is open on `device` (graph_begin without graph_end yet)
 
     // Hands every idle cached block of `device` (owned by no live graph) back to the driver; returns the bytes released. allocate()
     // does this by itself, once, when the driver reports out-of-memory (KF_ERR_OOM), before it gives up with utils::OutOfMemory.

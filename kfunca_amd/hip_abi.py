@@ -46,6 +46,7 @@ EXPORTS = [
     "kf_reduce_moments_workspace_bytes", "kf_reduce_moments",
     "kf_norm_fwd", "kf_norm_bwd_workspace_bytes", "kf_norm_bwd",
     "kf_cross_entropy_workspace_bytes", "kf_cross_entropy_fwd", "kf_cross_entropy_bwd",
+    "kf_adamw_workspace_bytes", "kf_adamw_step",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
 ]
@@ -62,6 +63,12 @@ class IterDesc(C.Structure):
     _fields_ = [("ndim", C.c_int32), ("ntensors", C.c_int32), ("noutputs", C.c_int32), ("reserved", C.c_int32),
                 ("dtype", C.c_int32 * MAX_TENSORS), ("shape", C.c_int64 * MAX_DIMS),
                 ("stride_bytes", (C.c_int64 * MAX_DIMS) * MAX_TENSORS), ("data", C.c_void_p * MAX_TENSORS)]
+
+
+class AdamwTensor(C.Structure):
+    """kf_adamw_tensor: one tensor of a fused AdamW step (param, grad, optional f32 master, f32 exp_avg / exp_avg_sq, f32 step on the device)."""
+    _fields_ = [("numel", C.c_int64), ("param_dtype", C.c_int), ("grad_dtype", C.c_int), ("param", C.c_void_p), ("grad", C.c_void_p),
+                ("master", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p), ("weight_decay", C.c_float)]
 
 
 class GemmEpilogue(C.Structure):
@@ -149,6 +156,8 @@ def lib():
         _lib.kf_cross_entropy_workspace_bytes.argtypes = [C.c_int, i64, i64, C.c_int, C.POINTER(sz)]
         _lib.kf_cross_entropy_fwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_int, vp, vp, vp, vp, sz, vp]
         _lib.kf_cross_entropy_bwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_int, vp, vp, vp, vp, i64, vp]
+        _lib.kf_adamw_workspace_bytes.argtypes = [i64, C.c_float, C.POINTER(sz)]
+        _lib.kf_adamw_step.argtypes = [C.POINTER(AdamwTensor), i64, C.c_double, C.c_double, C.c_double, vp, C.c_float, C.c_float, vp, vp, sz, vp]
         _lib.kf_index_put.argtypes = [C.POINTER(IterDesc), C.c_int, C.POINTER(i64), C.POINTER(i64), vp]
         _lib.kf_index_get.argtypes = [vp, i64, i64, vp, i64, vp, vp]
         _lib.kf_index_add_workspace_bytes.argtypes = [i64]
@@ -466,6 +475,35 @@ def ce_bwd(dtype, rows, V, logits, target, lse, count, grad, dlogits, ignore_ind
     ld = V if ld is None else ld
     check(lib().kf_cross_entropy_bwd(dtype, rows, V, ld, logits, target, ignore_index, float(label_smoothing), reduction, lse, count, grad,
                                      dlogits, ld if ldd is None else ldd, stream))
+
+
+def adamw_workspace_bytes(n, max_grad_norm=0.0):
+    need = C.c_size_t(0)
+    check(lib().kf_adamw_workspace_bytes(n, float(max_grad_norm), C.byref(need)))
+    return need.value
+
+
+def adamw_tensors(tensors):
+    """A kf_adamw_tensor array from AdamwTensor structs or dicts of its fields."""
+    arr = (AdamwTensor * max(len(tensors), 1))()
+    for i, t in enumerate(tensors):
+        arr[i] = t if isinstance(t, AdamwTensor) else AdamwTensor(**t)
+    return arr
+
+
+def adamw_step(tensors, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, max_grad_norm=0.0, grad_norm=None, workspace=None,
+               workspace_bytes=None, stream=None):
+    """One fused AdamW step (kf_adamw_step) over `tensors` (AdamwTensor structs or dicts); lr: a device f32 [1]. Without a workspace, one of
+    the queried size is made here and returned (keep it until the stream is synchronised)."""
+    arr = adamw_tensors(tensors)
+    ws = None
+    if workspace is None:
+        need = adamw_workspace_bytes(len(tensors), max_grad_norm)
+        ws = DevBuf(need) if need else None
+        workspace, workspace_bytes = (ws.ptr if ws else None), need
+    check(lib().kf_adamw_step(arr, len(tensors), beta1, beta2, eps, lr, grad_scale, max_grad_norm, grad_norm, workspace,
+                              workspace_bytes or 0, stream))
+    return ws
 
 
 def index_put(desc: IterDesc, sizes, strides_bytes, stream=None):
