@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
+#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
 
 /* ---- status ------------------------------------------------------------------------------ */
 enum {
@@ -482,6 +482,31 @@ int kf_attn_bwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv
                         const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
                         const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- rotary position embeddings (no reference counterpart: the position signal between the QKV projection and attention) ---- */
+/*
+ * x, y: [B, H, S, D] addressed by kf_attn_layout element strides of B, H, S; D is contiguous; dtype in {KF_F32, KF_BF16, KF_F16};
+ * any element-aligned base and strides (16-byte aligned heads, tables and R/2 a multiple of 16 / sizeof(T) take the packed path).
+ * rotary_dim R: even, 2 <= R <= D. cos, sin: f32 [table_rows, R/2], contiguous. The position of token (b, s) is p = positions[b*S + s]
+ * (int64 on the device, B*S of them) or p = s when positions is NULL. With c = cos[p, i], s = sin[p, i], i < R/2, each pair (a, b)
+ *     interleaved = 0 (rotate-half: Llama, NeoX, HF rotate_half)   (a, b) = (i, i + R/2)
+ *     interleaved = 1 (GPT-J)                                      (a, b) = (2i, 2i + 1)
+ * becomes y_a = x_a c - x_b s, y_b = x_b c + x_a s, in f32 on the stored values with one rounding per output element. inverse = 1
+ * uses -s: the exact transpose, i.e. the backward. Dims d >= R and heads h >= h_rot are copied, so ONE call over the packed QKV
+ * projection [B*S, W], W = (Hq + 2 Hkv) D, with layout {S*W, D, W}, H = Hq + 2 Hkv and h_rot = Hq + Hkv rotates q and k and passes v
+ * through. In place (y == x, same layout) the copied parts are not written; y must not otherwise overlap x. A position outside
+ * [0, table_rows) makes that token's rotated elements NaN (no device assert, no read outside the table). One launch, no atomics,
+ * no allocation, no synchronisation: calls can be captured with kf_graph_*. Every argument is checked before any device call:
+ * KF_ERR_INVALID (dtype, R odd / < 2 / > D, h_rot outside [0, H], null pointers, table_rows < 1, no positions with S > table_rows,
+ * y == x with another layout).
+ * kf_rope_table writes cos[p, i] = cos(p base^(-2i/R)) and sin likewise for p < rows: the angle and both functions in f64, rounded
+ * once to f32 (torch's f32 angle is off by about p 2^-24 rad at large p). A caller who wants torch's exact table or a scaled variant
+ * (linear, NTK, Llama-3 frequency scaling) builds its own [rows, R/2] tables and passes them to kf_rope.
+ */
+int kf_rope(int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t h_rot, int64_t rotary_dim, int interleaved, int inverse,
+            const float *cos, const float *sin, int64_t table_rows, const int64_t *positions, const void *x, const kf_attn_layout *lx,
+            void *y, const kf_attn_layout *ly, void *stream);
+int kf_rope_table(double base, int64_t rotary_dim, int64_t rows, float *cos, float *sin, void *stream);
 
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128

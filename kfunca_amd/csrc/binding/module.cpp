@@ -14,6 +14,7 @@
 #include "device_api.h"
 #include "ops.h"
 #include "optim.h"
+#include "rope.h"
 #include "tensor.h"
 #include "tensor_iterator.h"
 
@@ -382,6 +383,20 @@ PYBIND11_MODULE(_C, m) {
         return gpu::gemm_fused(x, w_qkv, 1.0f, bias.is_none() ? Tensor() : bias.cast<Tensor>(), Tensor(), Tensor());
     }, py::arg("x"), py::arg("w_qkv"), py::arg("bias") = py::none());
     m.def("causal_attention_qkv", &gpu::causal_attention_qkv, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"));
+    // rotary position embeddings: f64-accurate tables, and the rotation of q and k in place in the packed projection (one launch each way)
+    m.def("rope_table", [](int64_t max_positions, int64_t rotary_dim, double base, int device) {
+        auto [c, sn] = gpu::rope_table(max_positions, rotary_dim, base, device);
+        return py::make_tuple(c, sn);
+    }, py::arg("max_positions"), py::arg("rotary_dim"), py::arg("base") = 10000.0, py::arg("device") = 0);
+    m.def("rope_qkv", [](const Tensor &qkv, const Tensor &cos, const Tensor &sin, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object positions,
+                         bool interleaved) {
+        return gpu::rope_qkv(qkv, cos, sin, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>(),
+                             positions.is_none() ? Tensor() : positions.cast<Tensor>(), interleaved);
+    }, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none(),
+          py::arg("positions") = py::none(), py::arg("interleaved") = false);
+    m.def("rope", [](const Tensor &x, const Tensor &cos, const Tensor &sin, py::object positions, bool interleaved) {
+        return gpu::rope(x, cos, sin, positions.is_none() ? Tensor() : positions.cast<Tensor>(), interleaved);
+    }, py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("positions") = py::none(), py::arg("interleaved") = false);
     // from_numpy for bfloat16: uint16 bit patterns in, a BFloat16 tensor out (the inverse of to_numpy's uint16 view)
     m.def("from_numpy_bf16", [](py::array array, int device) {
         CHECK_FAIL(array.dtype().kind() == 'u' && array.dtype().itemsize() == 2, "from_numpy_bf16 expects uint16 bit patterns");

@@ -47,6 +47,7 @@ EXPORTS = [
     "kf_norm_fwd", "kf_norm_bwd_workspace_bytes", "kf_norm_bwd",
     "kf_cross_entropy_workspace_bytes", "kf_cross_entropy_fwd", "kf_cross_entropy_bwd",
     "kf_adamw_workspace_bytes", "kf_adamw_step",
+    "kf_rope", "kf_rope_table",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
 ]
@@ -181,6 +182,8 @@ def lib():
         _lib.kf_attn_fwd_strided.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
         _lib.kf_attn_bwd_strided.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp, vp, lp, vp, lp,
                                              vp, lp, vp, sz, vp]
+        _lib.kf_rope.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, vp, vp, lp, vp, lp, vp]
+        _lib.kf_rope_table.argtypes = [C.c_double, i64, i64, vp, vp, vp]
         _lib.kf_comm_unique_id.argtypes = [C.c_char_p]
         _lib.kf_comm_init.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int, C.c_int]
         _lib.kf_comm_destroy.argtypes = [vp]
@@ -591,6 +594,23 @@ def attn_bwd_strided(dtype, B, H, Sq, Skv, D, scale, q, lq, k, lk, v, lv, o, lo,
     L = [AttnLayout(*t) for t in (lq, lk, lv, lo, ldo, ldq, ldk, ldv)]
     check(lib().kf_attn_bwd_strided(dtype, B, H, Sq, Skv, D, scale, q, C.byref(L[0]), k, C.byref(L[1]), v, C.byref(L[2]), o, C.byref(L[3]), lse,
                                     d_o, C.byref(L[4]), dq, C.byref(L[5]), dk, C.byref(L[6]), dv, C.byref(L[7]), workspace, workspace_bytes, stream))
+
+
+def rope(dtype, B, H, S, D, x, lx, y=None, ly=None, cos=None, sin=None, table_rows=None, rotary_dim=None, h_rot=None, positions=None,
+         interleaved=False, inverse=False, stream=None):
+    """Rotary position embeddings (kf_rope). lx / ly are (batch, head, row) element-stride triples; y = None: in place (y = x, ly = lx).
+    rotary_dim defaults to D, h_rot to H; cos / sin are f32 [table_rows, rotary_dim / 2] device tables."""
+    R = D if rotary_dim is None else rotary_dim
+    if y is None:
+        y, ly = x, lx
+    Lx, Ly = AttnLayout(*lx), AttnLayout(*(lx if ly is None else ly))
+    check(lib().kf_rope(dtype, B, H, S, D, H if h_rot is None else h_rot, R, int(interleaved), int(inverse), cos, sin, table_rows, positions, x,
+                        C.byref(Lx), y, C.byref(Ly), stream))
+
+
+def rope_table(base, rotary_dim, rows, cos, sin, stream=None):
+    """kf_rope_table: cos / sin = f32 [rows, rotary_dim / 2] device buffers, cos(p base^(-2i/R)) from f64."""
+    check(lib().kf_rope_table(float(base), rotary_dim, rows, cos, sin, stream))
 
 
 def device_sync():
