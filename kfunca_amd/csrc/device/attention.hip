@@ -2508,6 +2508,11 @@ static bool mfma_ok(int dtype, int64_t Sq, int64_t Skv, int64_t D) {
 static bool w4_any_ok(int dtype, int64_t Sq, int64_t Skv, int64_t D) {
     return (dtype == KF_BF16 || dtype == KF_F16) && (D == AD || D == 64) && Sq > 0 && Skv >= Sq;
 }
+// the 16-bit matrix-core kernels serve this shape (whole 128-row tiles, or the generated streams' ragged lengths)
+static bool mfma16_ok(int dtype, int64_t Sq, int64_t Skv, int64_t D) { return mfma_ok(dtype, Sq, Skv, D) || w4_any_ok(dtype, Sq, Skv, D); }
+
+// AttnArgs::persist over n blocks: a workgroup takes the pair {block, its causal mirror} when n is even and at least 4
+static int pair_flag(int64_t n) { return (n % 2 == 0 && n >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0; }
 
 static inline size_t a_align(size_t v) { return (v + 255) / 256 * 256; }
 
@@ -2538,9 +2543,12 @@ static size_t ds_cap() { // KF_ATTN_DS_CAP_MB, clamped to [0, 4 Ti MB): a negati
     const long long mb = knob_int(KNOB_ATTN_DS_CAP_MB, 16384);
     return (size_t)std::min<long long>(std::max<long long>(mb, 0), 4ll << 20) << 20;
 }
-
-template <typename K>
-static int set_lds(K kernel, size_t bytes) { return ensure_dynamic_lds((const void *)kernel, (int)bytes); }
+// May the backward keep dS in `budget` bytes: the layout, and the pairs per group (0: dS is not kept - too small a budget, or KF_ATTN_SPLIT_BWD)
+struct DsPlan { int tri; int64_t group; };
+static DsPlan ds_plan(int64_t nbh, int64_t Sq, int64_t Skv, size_t budget) {
+    const int tri = ds_tri_mode(nbh, Sq, Skv, budget);
+    return {tri, knob(KNOB_ATTN_SPLIT_BWD) ? 0 : ds_group(nbh, Sq, Skv, budget, tri)};
+}
 
 } // namespace kf
 
@@ -2549,6 +2557,9 @@ using namespace kf;
 #ifdef KF_MUTANT
 static int g_mutant = 0; // see KF_MUT above
 extern "C" int kfmut_select(int which) { g_mutant = which; return KF_OK; }
+#endif
+#if defined(KF_FWD_W4_STAMPS) || defined(KF_DKV_W4_STAMPS)
+unsigned long long *kf_attn_tl_host_ptr();
 #endif
 
 static int check_common(const char *who, int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D) {
@@ -2559,11 +2570,6 @@ static int check_common(const char *who, int dtype, int64_t B, int64_t H, int64_
     return KF_OK;
 }
 
-extern "C" int kf_attn_fwd(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, const void *q,
-                           const void *k, const void *v, void *o, float *lse, void *stream) {
-    return kf_attn_fwd_scaled(dtype, B, H, Sq, Skv, D, D > 0 ? 1.0f / sqrtf((float)D) : 1.0f, q, k, v, o, lse, stream);
-}
-
 static AttnArgs::Lay lay_contig(int64_t H, int64_t S, int64_t D, int es) { return {H * S * D * es, S * D * es, D * es}; }
 static bool lay_from(const kf_attn_layout *l, int es, AttnArgs::Lay &out) {
     if (!l || l->batch < 0 || l->head < 0 || l->row < 0) return false;
@@ -2571,24 +2577,28 @@ static bool lay_from(const kf_attn_layout *l, int es, AttnArgs::Lay &out) {
     return out.sb % 16 == 0 && out.sh % 16 == 0 && out.sr % 16 == 0; // 16-byte row pieces
 }
 
-static int attn_fwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
-                         const void *v, void *o, float *lse, const AttnArgs::Lay *lays, void *stream);
-
-extern "C" int kf_attn_fwd_scaled(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
-                                  const void *k, const void *v, void *o, float *lse, void *stream) {
-    return attn_fwd_impl(dtype, B, H, Sq, Skv, D, scale, q, k, v, o, lse, nullptr, stream);
-}
-
-extern "C" int kf_attn_fwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
-                                   const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
-                                   void *o, const kf_attn_layout *lo, float *lse, void *stream) {
-    KF_REQUIRE(mfma_ok(dtype, Sq, Skv, D) || w4_any_ok(dtype, Sq, Skv, D), KF_ERR_UNSUPPORTED,
-               "kf_attn_fwd_strided: strided layouts are served by the 16-bit matrix-core kernels only (D = 64 or 128; Skv >= Sq, or Sq, Skv multiples of 128)");
-    AttnArgs::Lay lays[4];
-    KF_REQUIRE(lay_from(lq, 2, lays[0]) && lay_from(lk, 2, lays[1]) && lay_from(lv, 2, lays[2]) && lay_from(lo, 2, lays[3]), KF_ERR_INVALID,
-               "kf_attn_fwd_strided: strides must be non-negative multiples of 8 elements");
-    KF_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0, KF_ERR_INVALID, "kf_attn_fwd_strided: operands must be 16-byte aligned");
-    return attn_fwd_impl(dtype, B, H, Sq, Skv, D, scale, q, k, v, o, lse, lays, stream);
+// The AttnArgs fields the forward and the backward share. nlay layouts in the order q, k, v, o (forward: 4) and dO, dQ, dK, dV
+// (backward: 8): the caller's `lays`, or contiguous [B, H, S, D] tensors when it has none.
+static int attn_args(AttnArgs &a, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const AttnArgs::Lay *lays, int nlay) {
+    memset(&a, 0, sizeof(a));
+    KF_REQUIRE(scale > 0.f && scale < INFINITY, KF_ERR_INVALID, "attention: the softmax scale must be positive and finite");
+    a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.D = D;
+    a.nbh = (int)(B * H);
+    a.scale = scale;
+    a.scale_log2e = scale * kLog2e;
+    a.xcd_map = ((B * H) % 8 == 0) && !knob(KNOB_ATTN_NO_XCD);
+#if defined(KF_FWD_W4_STAMPS) || defined(KF_DKV_W4_STAMPS)
+    a.dbg = kf_attn_tl_host_ptr();
+#endif
+#ifdef KF_MUTANT
+    a.mutant = g_mutant;
+#endif
+    AttnArgs::Lay *const out[8] = {&a.lq, &a.lk, &a.lv, &a.lo, &a.ldo, &a.ldq, &a.ldk, &a.ldv};
+    for (int i = 0; i < nlay; ++i) {
+        const bool key_rows = i == 1 || i == 2 || i >= 6; // k, v, dK, dV: Skv rows
+        *out[i] = lays ? lays[i] : lay_contig(H, key_rows ? Skv : Sq, D, 2);
+    }
+    return KF_OK;
 }
 
 static int attn_fwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
@@ -2598,111 +2608,65 @@ static int attn_fwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Sk
     if (B * H == 0 || Sq == 0) return KF_OK;
     KF_REQUIRE(Skv > 0, KF_ERR_INVALID, "kf_attn_fwd: Skv must be positive");
     KF_REQUIRE(q && k && v && o, KF_ERR_INVALID, "kf_attn_fwd: null operand");
-    hipStream_t st = as_stream(stream);
     AttnArgs a;
-    memset(&a, 0, sizeof(a));
+    if ((rc = attn_args(a, B, H, Sq, Skv, D, scale, lays, 4)) != KF_OK) return rc;
     a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.out = (char *)o; a.lse = lse;
-    a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.D = D;
-    a.nbh = (int)(B * H);
-    KF_REQUIRE(scale > 0.f && scale < INFINITY, KF_ERR_INVALID, "attention: the softmax scale must be positive and finite");
-    a.scale = scale;
-    a.scale_log2e = scale * kLog2e;
-#ifdef KF_FWD_W4_STAMPS
-    extern unsigned long long *kf_attn_tl_host_ptr();
-    a.dbg = kf_attn_tl_host_ptr();
-#endif
-    a.xcd_map = ((B * H) % 8 == 0) && !knob(KNOB_ATTN_NO_XCD);
     a.defer = knob(KNOB_ATTN_NO_DEFER) ? -INFINITY : kDeferMax; // A/B switch: rescale O at every tile
-#ifdef KF_MUTANT
-    a.mutant = g_mutant;
-#endif
-    if (lays) { a.lq = lays[0]; a.lk = lays[1]; a.lv = lays[2]; a.lo = lays[3]; }
-    else { a.lq = a.lo = lay_contig(H, Sq, D, 2); a.lk = a.lv = lay_contig(H, Skv, D, 2); }
-    // the generated stream's shape conditions (KF_ATTN_FWD_V3 keeps the 8-wave kernel where that one can run: A/B)
+    hipStream_t st = as_stream(stream);
+    const bool bf = dtype == KF_BF16, d64 = D == 64;
+    // round 4: the one-wave-per-SIMD generated stream (attn_fwd_w4_kernel) wherever its shape conditions hold; KF_ATTN_FWD_V3 keeps the
+    // 8-wave kernel where that one can run (A/B)
     const bool fwd_w4 = w4_any_ok(dtype, Sq, Skv, D) && a.lk.sr == a.lv.sr && (uint64_t)(Skv + FQ) * (uint64_t)a.lk.sr < (1ull << 32) &&
                         (uint64_t)FQ * (uint64_t)std::max(a.lq.sr, a.lo.sr) < (1ull << 31) && !knob(KNOB_ATTN_FWD_V3);
-    if (mfma_ok(dtype, Sq, Skv, D) || fwd_w4) {
-        const size_t lds3 = SRING * FBUF;
-        const int64_t nxb3 = (Sq + FQ - 1) / FQ;
-        a.persist = (nxb3 % 2 == 0 && nxb3 >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0;
-        dim3 grid3((unsigned)((a.persist ? nxb3 / (2 * a.persist) : nxb3) * B * H));
-        a.nvwg = grid3.x;
-        KF_PROF(D == 64 ? "attn_fwd_mfma_d64" : "attn_fwd_mfma", st);
-        // round 4: the one-wave-per-SIMD stream (attn_fwd_w4_kernel) wherever its shape conditions hold; KF_ATTN_FWD_V3 keeps the 8-wave kernel (A/B)
-        if (fwd_w4) {
-#define KF_FWD4(BF_, SQ_)                                                                                   \
-    {                                                                                                       \
-        if ((rc = set_lds(attn_fwd_w4_kernel<BF_, SQ_>, KF_FWD_W4_LDS_BYTES)) != KF_OK) return rc;           \
-        attn_fwd_w4_kernel<BF_, SQ_><<<grid3, 256, KF_FWD_W4_LDS_BYTES, st>>>(a);                           \
-    }
-            const bool sq = D == AD && knob(KNOB_ATTN_SCALED_OPERANDS); // opt-in: c q rounded once per pass (faster; score error grows with the logits)
-            if (D == 64) {
-                if (dtype == KF_BF16) {
-                    if ((rc = set_lds(attn_fwd_w4_kernel<true, false, true>, KF_FWD_W4_LDS_BYTES)) != KF_OK) return rc;
-                    attn_fwd_w4_kernel<true, false, true><<<grid3, 256, KF_FWD_W4_LDS_BYTES, st>>>(a);
-                } else {
-                    if ((rc = set_lds(attn_fwd_w4_kernel<false, false, true>, KF_FWD_W4_LDS_BYTES)) != KF_OK) return rc;
-                    attn_fwd_w4_kernel<false, false, true><<<grid3, 256, KF_FWD_W4_LDS_BYTES, st>>>(a);
-                }
-            } else if (dtype == KF_BF16) { if (sq) KF_FWD4(true, true) else KF_FWD4(true, false) }
-            else { if (sq) KF_FWD4(false, true) else KF_FWD4(false, false) }
-#undef KF_FWD4
-            KF_LAUNCH_CHECK();
-            return KF_OK;
-        }
-#define KF_FWD(BF_, D_)                                                                  \
-    {                                                                                    \
-        if ((rc = set_lds(attn_fwd_v3_kernel<BF_, D_>, lds3)) != KF_OK) return rc;       \
-        attn_fwd_v3_kernel<BF_, D_><<<grid3, FNT, lds3, st>>>(a);                         \
-    }
-        if (dtype == KF_BF16) { if (D == 64) KF_FWD(true, 64) else KF_FWD(true, 128) }
-        else { if (D == 64) KF_FWD(false, 64) else KF_FWD(false, 128) }
-#undef KF_FWD
-        KF_LAUNCH_CHECK();
-        return KF_OK;
+    const bool v3 = !fwd_w4 && mfma_ok(dtype, Sq, Skv, D);
+    const bool f32_mfma = dtype == KF_F32 && (D == 64 || D == 128) && Sq % 32 == 0 && Skv % 32 == 0; // the reference's own fast path: exact-f32 MFMA
+    if (fwd_w4 || v3) {
+        const int64_t nxb = (Sq + FQ - 1) / FQ;
+        a.persist = pair_flag(nxb);
+        const dim3 grid((unsigned)((a.persist ? nxb / 2 : nxb) * B * H));
+        a.nvwg = grid.x;
+        KF_PROF(d64 ? "attn_fwd_mfma_d64" : "attn_fwd_mfma", st);
+        if (v3) return with_flags([&](auto BF, auto D64) { return launch(attn_fwd_v3_kernel<BF, D64 ? 64 : 128>, grid, FNT, SRING * FBUF, st, a); }, bf, d64);
+        if (d64) return with_flags([&](auto BF) { return launch(attn_fwd_w4_kernel<BF, false, true>, grid, 256, KF_FWD_W4_LDS_BYTES, st, a); }, bf);
+        const bool sq = knob(KNOB_ATTN_SCALED_OPERANDS); // opt-in: c q rounded once per pass (faster; score error grows with the logits)
+        return with_flags([&](auto BF, auto SQ) { return launch(attn_fwd_w4_kernel<BF, SQ>, grid, 256, KF_FWD_W4_LDS_BYTES, st, a); }, bf, sq);
     }
     // (from here on: kernels of contiguous [B, H, S, D] tensors only)
     KF_REQUIRE(!lays, KF_ERR_UNSUPPORTED, "kf_attn_fwd_strided: this shape / stride combination has no matrix-core kernel (ragged lengths want K and V with one row stride)");
-    if (dtype == KF_F32 && (D == 64 || D == 128) && Sq % 32 == 0 && Skv % 32 == 0) {
-        // the reference's own fast path (f32, head size 64 or 128): exact-f32 MFMA
+    if (f32_mfma) {
         const size_t ldsx = std::max((size_t)2 * XK * (D + 4), (size_t)4 * 32 * (D + 4)) * sizeof(float);
         const int64_t nxx = (Sq + XQ - 1) / XQ;
-        a.persist = (nxx % 2 == 0 && nxx >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0;
-        dim3 gridx((unsigned)((a.persist ? nxx / 2 : nxx) * B * H));
+        a.persist = pair_flag(nxx);
         KF_PROF("attn_fwd_f32_mfma", st);
-        if (D == 128) {
-            if ((rc = set_lds(attn_fwd_f32_mfma_kernel<128>, ldsx)) != KF_OK) return rc;
-            attn_fwd_f32_mfma_kernel<128><<<gridx, 256, ldsx, st>>>(a);
-        } else {
-            if ((rc = set_lds(attn_fwd_f32_mfma_kernel<64>, ldsx)) != KF_OK) return rc;
-            attn_fwd_f32_mfma_kernel<64><<<gridx, 256, ldsx, st>>>(a);
-        }
-        KF_LAUNCH_CHECK();
-        return KF_OK;
+        return launch(D == 128 ? attn_fwd_f32_mfma_kernel<128> : attn_fwd_f32_mfma_kernel<64>, (unsigned)((a.persist ? nxx / 2 : nxx) * B * H), 256, ldsx, st, a);
     }
     const int DP = (int)D + 1;
     const size_t lds = sizeof(float) * ((size_t)GQ * DP + (size_t)GK * DP + (size_t)GK * D + (size_t)GQ * (GK + 1) + GQ);
-    dim3 grid((unsigned)((Sq + GQ - 1) / GQ), (unsigned)(B * H));
     KF_PROF("attn_fwd_generic", st);
-    switch (dtype) {
-    case KF_F32:
-        rc = set_lds(attn_fwd_generic_kernel<float>, lds);
-        if (rc != KF_OK) return rc;
-        attn_fwd_generic_kernel<float><<<grid, 256, lds, st>>>(a);
-        break;
-    case KF_BF16:
-        rc = set_lds(attn_fwd_generic_kernel<bf16_t>, lds);
-        if (rc != KF_OK) return rc;
-        attn_fwd_generic_kernel<bf16_t><<<grid, 256, lds, st>>>(a);
-        break;
-    default:
-        rc = set_lds(attn_fwd_generic_kernel<f16_t>, lds);
-        if (rc != KF_OK) return rc;
-        attn_fwd_generic_kernel<f16_t><<<grid, 256, lds, st>>>(a);
-        break;
-    }
-    KF_LAUNCH_CHECK();
-    return KF_OK;
+    return launch(dtype == KF_F32 ? attn_fwd_generic_kernel<float> : bf ? attn_fwd_generic_kernel<bf16_t> : attn_fwd_generic_kernel<f16_t>,
+                  dim3((unsigned)((Sq + GQ - 1) / GQ), (unsigned)(B * H)), 256, lds, st, a);
+}
+
+extern "C" int kf_attn_fwd(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, const void *q,
+                           const void *k, const void *v, void *o, float *lse, void *stream) {
+    return kf_attn_fwd_scaled(dtype, B, H, Sq, Skv, D, D > 0 ? 1.0f / sqrtf((float)D) : 1.0f, q, k, v, o, lse, stream);
+}
+
+extern "C" int kf_attn_fwd_scaled(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
+                                  const void *k, const void *v, void *o, float *lse, void *stream) {
+    return attn_fwd_impl(dtype, B, H, Sq, Skv, D, scale, q, k, v, o, lse, nullptr, stream);
+}
+
+extern "C" int kf_attn_fwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
+                                   const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
+                                   void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+    KF_REQUIRE(mfma16_ok(dtype, Sq, Skv, D), KF_ERR_UNSUPPORTED,
+               "kf_attn_fwd_strided: strided layouts are served by the 16-bit matrix-core kernels only (D = 64 or 128; Skv >= Sq, or Sq, Skv multiples of 128)");
+    AttnArgs::Lay lays[4];
+    KF_REQUIRE(lay_from(lq, 2, lays[0]) && lay_from(lk, 2, lays[1]) && lay_from(lv, 2, lays[2]) && lay_from(lo, 2, lays[3]), KF_ERR_INVALID,
+               "kf_attn_fwd_strided: strides must be non-negative multiples of 8 elements");
+    KF_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0, KF_ERR_INVALID, "kf_attn_fwd_strided: operands must be 16-byte aligned");
+    return attn_fwd_impl(dtype, B, H, Sq, Skv, D, scale, q, k, v, o, lse, lays, stream);
 }
 
 extern "C" int kf_attn_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D,
@@ -2711,12 +2675,142 @@ extern "C" int kf_attn_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int6
     int rc = check_common("kf_attn_bwd_workspace_bytes", dtype, B, H, Sq, Skv, D);
     if (rc != KF_OK) return rc;
     *bytes = bwd_stats_bytes(B * H, Sq); // delta | -lse log2(e) | -delta
-    if ((mfma_ok(dtype, Sq, Skv, D) || w4_any_ok(dtype, Sq, Skv, D)) && !knob(KNOB_ATTN_SPLIT_BWD) && B * H > 0)
-    { // + dS in 16 bits (DS_TILE): full rows for every pair when the cap allows (the faster dQ stream), else the causal half of as many pairs as the cap holds
-        const int tri = ds_tri_mode(B * H, Sq, Skv, ds_cap());
-        *bytes += ds_bytes(ds_group(B * H, Sq, Skv, ds_cap(), tri), Sq, Skv, tri);
+    if (mfma16_ok(dtype, Sq, Skv, D) && B * H > 0) {
+        // + dS in 16 bits (DS_TILE): full rows for every pair when the cap allows (the faster dQ stream), else the causal half of as many pairs as the cap holds
+        const DsPlan ds = ds_plan(B * H, Sq, Skv, ds_cap());
+        *bytes += ds_bytes(ds.group, Sq, Skv, ds.tri);
     }
     return KF_OK;
+}
+
+static int attn_bwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
+                         const void *v, const void *o, const float *lse, const void *d_o, void *dq, void *dk, void *dv, const AttnArgs::Lay *lays,
+                         void *workspace, size_t workspace_bytes, void *stream) {
+    int rc = check_common("kf_attn_bwd", dtype, B, H, Sq, Skv, D);
+    if (rc != KF_OK) return rc;
+    if (B * H == 0 || Sq == 0 || Skv == 0) return KF_OK;
+    KF_REQUIRE(q && k && v && o && lse && d_o && dq && dk && dv, KF_ERR_INVALID, "kf_attn_bwd: null operand");
+    const size_t need = bwd_stats_bytes(B * H, Sq); // the minimum; what lies beyond it holds dS (see ds_group)
+    KF_REQUIRE(workspace && workspace_bytes >= need, KF_ERR_WORKSPACE, "kf_attn_bwd: workspace of at least %zu bytes required, got %zu", need, workspace_bytes);
+    AttnArgs a;
+    if ((rc = attn_args(a, B, H, Sq, Skv, D, scale, lays, 8)) != KF_OK) return rc;
+    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.o = (const char *)o; a.d_o = (const char *)d_o;
+    a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv;
+    a.lse_r = lse; a.delta = (float *)workspace;
+    a.Sqc = stat_rows(Sq);
+    a.nlse = (float *)((char *)workspace + a_align((size_t)B * H * Sq * sizeof(float)));
+    a.ndelta = (float *)((char *)a.nlse + a_align((size_t)B * H * a.Sqc * sizeof(float)));
+    hipStream_t st = as_stream(stream);
+    const int64_t nbh = B * H, nrows = nbh * Sq;
+    const bool bf = dtype == KF_BF16, d64 = D == 64;
+    const bool tiled = mfma_ok(dtype, Sq, Skv, D); // whole 128-row tiles: every 16-bit matrix-core kernel can run
+    // round 4: 64 keys per wave (attn_bwd_dkv_w4_kernel) wherever its shape conditions hold; KF_ATTN_DKV_V4 keeps the 32-key kernel (A/B).
+    // round 6: any Sq, Skv with Skv >= Sq (w4_any_ok: rows beyond a tensor's end are zero-filled / dropped by the descriptors)
+    const bool dkv_w4 = ((tiled && Skv % K5B == 0) || w4_any_ok(dtype, Sq, Skv, D)) && a.lk.sr == a.lv.sr && a.ldk.sr == a.ldv.sr &&
+                        (uint64_t)(Sq + 32) * (uint64_t)std::max(a.lq.sr, a.ldo.sr) < (1ull << 32) && (uint64_t)K5B * (uint64_t)std::max(a.lk.sr, a.ldk.sr) < (1ull << 31) &&
+                        (uint64_t)((const char *)a.ndelta - (const char *)a.nlse) < (1ull << 31) && !knob(KNOB_ATTN_DKV_V4);
+    const DsPlan ds = ds_plan(nbh, Sq, Skv, workspace_bytes - need);
+    const bool keep_ds = ds.group > 0;
+    // a ragged shape has no other matrix-core kernels: it needs the generated dK/dV stream AND room for dS (the recomputing dQ kernel wants whole tiles)
+    const bool mfma16 = tiled || (dkv_w4 && keep_ds);
+    const bool f32_mfma = dtype == KF_F32 && (D == 64 || D == 128) && Sq % 32 == 0 && Skv % 32 == 0; // the f32 forward's counterpart (the reference has no backward)
+    if (mfma16) {
+        // exact f32 scores everywhere by default (exponent = (s - lse / scale) * scale log2 e: the row constant is -lse / scale); only the opt-in
+        // scaled-K form of the generated stream scales K by scale log2 e once per block and wants -lse log2 e
+        const bool dkv_sq = dkv_w4 && D == AD && knob(KNOB_ATTN_SCALED_OPERANDS);
+        const float rscale = dkv_sq ? kLog2e : 1.0f / scale;
+        {
+            KF_PROF("attn_bwd_delta", st);
+            // two rows per 16-lane group (four 16-byte loads in flight per lane): 0.110 -> 0.101 ms at C3; four rows: 0.100
+            const int64_t nrows_c = nbh * a.Sqc; // (rows of the padded row-constant arrays: the pad rows are written as zeros)
+            rc = launch(bf ? attn_delta_kernel<true, 2> : attn_delta_kernel<false, 2>, (unsigned)((nrows_c + 31) / 32), 256, 0, st, a.o, a.d_o, a.delta,
+                        nrows_c, a.lse_r, a.nlse, a.ndelta, rscale, a.lo, a.ldo, Sq, H, (int)(D / 8), a.Sqc);
+            if (rc != KF_OK) return rc;
+        }
+        a.ds = keep_ds ? (char *)workspace + need : nullptr;
+        a.ds_tri = ds.tri;
+        a.ds_pair = ds_pair_tiles(Sq, Skv, ds.tri);
+        a.ds_nkb = (Skv + 255) / 256;
+        const int64_t nkb4 = Skv / K4B, nkb5 = (Skv + K5B - 1) / K5B, nxq = (Sq + FQ - 1) / FQ;
+        // (Tried in round 3 and removed: the dS workspace as two half-group slots with group g's dQ - HBM-bound, it streams dS - on a second
+        // stream beside group g + 1's matrix-bound dK/dV. At C3 the backward took 3.39-3.78 ms against 3.32-3.36 in sequence
+        // (profiles/r03_attn_bwd_overlap_experiment.txt): both kernels fill every CU, so the dispatcher interleaves them instead of
+        // running them side by side, and each group boundary adds a tail.)
+        const int64_t grp = keep_ds ? ds.group : nbh;
+        // one group of (batch, head) pairs at a time: dK/dV (stores the group's dS), then dQ from it. Without dS: one group, all pairs.
+        for (int64_t bh0 = 0; bh0 < nbh; bh0 += grp) {
+            a.bh0 = bh0;
+            a.nbh = (int)std::min<int64_t>(grp, nbh - bh0);
+            a.xcd_map = (a.nbh % 8 == 0) && !knob(KNOB_ATTN_NO_XCD);
+            { // dK / dV: one wave per SIMD, pinned MFMA / VALU interleave
+                a.persist_rev = 1; // the short block of the pair first: 2.17 ms against 2.32 the other way round (2.22 unpaired)
+                KF_PROF(d64 ? "attn_bwd_dkv_mfma_d64" : "attn_bwd_dkv_mfma", st);
+                if (dkv_w4) {
+                    a.persist = pair_flag(nkb5);
+                    const dim3 grid((unsigned)((a.persist ? nkb5 / 2 : nkb5) * a.nbh));
+                    a.nvwg = grid.x;
+                    if (d64)
+                        rc = with_flags([&](auto BF, auto DS) { return launch(attn_bwd_dkv_w4_kernel<BF, DS, false, true>, grid, 256, KF_DKV_W4_LDS_BYTES, st, a); },
+                                        bf, keep_ds);
+                    else
+                        rc = with_flags([&](auto BF, auto DS, auto SQ) { return launch(attn_bwd_dkv_w4_kernel<BF, DS, SQ>, grid, 256, KF_DKV_W4_LDS_BYTES, st, a); },
+                                        bf, keep_ds, dkv_sq);
+                } else {
+                    a.persist = pair_flag(nkb4);
+                    const dim3 grid((unsigned)((a.persist ? nkb4 / 2 : nkb4) * a.nbh));
+                    rc = with_flags([&](auto BF, auto DS, auto D64) { return launch(attn_bwd_dkv_v4_kernel<BF, DS, D64 ? 64 : 128>, grid, 256, K4LDS, st, a); },
+                                    bf, keep_ds, d64);
+                }
+                if (rc != KF_OK) return rc;
+            }
+            a.persist = pair_flag(nxq);
+            a.persist_rev = 0;
+            const dim3 grid((unsigned)((a.persist ? nxq / 2 : nxq) * a.nbh));
+            if (keep_ds) { // dQ = scale dS K from the stored dS
+                KF_PROF(d64 ? "attn_bwd_dq_mfma_d64" : "attn_bwd_dq_mfma", st);
+                rc = with_flags([&](auto BF, auto D64) { return launch(attn_bwd_dq_ds_kernel<BF, D64 ? 64 : 128>, grid, FNT, DQ_LDS, st, a); }, bf, d64);
+            } else { // the recomputing dQ kernel (S and dP again)
+                KF_PROF(d64 ? "attn_bwd_dq_mfma_split_d64" : "attn_bwd_dq_mfma_split", st);
+                rc = with_flags([&](auto BF, auto D64) { return launch(attn_bwd_dq_v2_kernel<BF, D64 ? 64 : 128>, grid, FNT, QLDS, st, a); }, bf, d64);
+            }
+            if (rc != KF_OK) return rc;
+        }
+        return KF_OK;
+    }
+    // (from here on: kernels of contiguous [B, H, S, D] tensors only)
+    KF_REQUIRE(!lays, KF_ERR_UNSUPPORTED, "kf_attn_bwd_strided: this shape / stride / workspace combination has no matrix-core kernel (ragged lengths want room for dS)");
+    const unsigned gd = (unsigned)((nrows + 3) / 4);
+    if (f32_mfma) {
+        {
+            KF_PROF("attn_bwd_delta", st);
+            rc = launch(attn_delta_generic_kernel<float>, gd, 256, 0, st, (const float *)o, (const float *)d_o, a.delta, nrows, (int)D);
+            if (rc != KF_OK) return rc;
+        }
+        const size_t tiles = (size_t)2 * XK * (D + 4) * sizeof(float) + 256, slabs = (size_t)4 * 32 * (D + 4) * sizeof(float);
+        const size_t ldsx = std::max(tiles, slabs);
+        const int64_t nxq = (Sq + XQ - 1) / XQ, nkb = (Skv + XQ - 1) / XQ;
+        {
+            a.persist = pair_flag(nkb);
+            KF_PROF("attn_bwd_dkv_f32_mfma", st);
+            rc = launch(D == 128 ? attn_bwd_dkv_f32_mfma_kernel<128> : attn_bwd_dkv_f32_mfma_kernel<64>, (unsigned)((a.persist ? nkb / 2 : nkb) * B * H), 256, ldsx, st, a);
+            if (rc != KF_OK) return rc;
+        }
+        a.persist = pair_flag(nxq);
+        KF_PROF("attn_bwd_dq_f32_mfma", st);
+        return launch(D == 128 ? attn_bwd_dq_f32_mfma_kernel<128> : attn_bwd_dq_f32_mfma_kernel<64>, (unsigned)((a.persist ? nxq / 2 : nxq) * B * H), 256, ldsx, st, a);
+    }
+    const int DP = (int)D + 1;
+    const size_t lds = sizeof(float) * ((size_t)2 * GQ * DP + (size_t)2 * GK * DP + (size_t)2 * GQ * (GK + 1) + 2 * GK);
+    const dim3 gq((unsigned)((Sq + GQ - 1) / GQ), (unsigned)(B * H)), gk((unsigned)((Skv + GQ - 1) / GQ), (unsigned)(B * H));
+    KF_PROF("attn_bwd_generic", st);
+    auto generic = [&](auto t) {
+        using T = decltype(t);
+        int r = launch(attn_delta_generic_kernel<T>, gd, 256, 0, st, (const T *)o, (const T *)d_o, a.delta, nrows, (int)D);
+        if (r == KF_OK) r = launch(attn_bwd_generic_kernel<T, 0>, gq, 256, lds, st, a);
+        if (r == KF_OK) r = launch(attn_bwd_generic_kernel<T, 1>, gk, 256, lds, st, a);
+        return r;
+    };
+    return dtype == KF_F32 ? generic(float{}) : bf ? generic(bf16_t{}) : generic(f16_t{});
 }
 
 extern "C" int kf_attn_bwd(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, const void *q,
@@ -2725,10 +2819,6 @@ extern "C" int kf_attn_bwd(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t 
     return kf_attn_bwd_scaled(dtype, B, H, Sq, Skv, D, D > 0 ? 1.0f / sqrtf((float)D) : 1.0f, q, k, v, o, lse, d_o, dq, dk, dv, workspace,
                               workspace_bytes, stream);
 }
-
-static int attn_bwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
-                         const void *v, const void *o, const float *lse, const void *d_o, void *dq, void *dk, void *dv, const AttnArgs::Lay *lays,
-                         void *workspace, size_t workspace_bytes, void *stream);
 
 extern "C" int kf_attn_bwd_scaled(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
                                   const void *k, const void *v, const void *o, const float *lse, const void *d_o, void *dq,
@@ -2741,7 +2831,7 @@ extern "C" int kf_attn_bwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, 
                                    const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
                                    const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
                                    void *workspace, size_t workspace_bytes, void *stream) {
-    KF_REQUIRE(mfma_ok(dtype, Sq, Skv, D) || w4_any_ok(dtype, Sq, Skv, D), KF_ERR_UNSUPPORTED,
+    KF_REQUIRE(mfma16_ok(dtype, Sq, Skv, D), KF_ERR_UNSUPPORTED,
                "kf_attn_bwd_strided: strided layouts are served by the 16-bit matrix-core kernels only (D = 64 or 128; Skv >= Sq, or Sq, Skv multiples of 128)");
     AttnArgs::Lay lays[8];
     const kf_attn_layout *in[8] = {lq, lk, lv, lo, ldo, ldq, ldk, ldv};
@@ -2750,215 +2840,6 @@ extern "C" int kf_attn_bwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, 
     KF_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16 == 0,
                KF_ERR_INVALID, "kf_attn_bwd_strided: operands must be 16-byte aligned");
     return attn_bwd_impl(dtype, B, H, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, lays, workspace, workspace_bytes, stream);
-}
-
-static int attn_bwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
-                         const void *v, const void *o, const float *lse, const void *d_o, void *dq, void *dk, void *dv, const AttnArgs::Lay *lays,
-                         void *workspace, size_t workspace_bytes, void *stream) {
-    int rc = check_common("kf_attn_bwd", dtype, B, H, Sq, Skv, D);
-    if (rc != KF_OK) return rc;
-    if (B * H == 0 || Sq == 0 || Skv == 0) return KF_OK;
-    KF_REQUIRE(q && k && v && o && lse && d_o && dq && dk && dv, KF_ERR_INVALID, "kf_attn_bwd: null operand");
-    const size_t need = bwd_stats_bytes(B * H, Sq); // the minimum; what lies beyond it holds dS (see ds_group)
-    KF_REQUIRE(workspace && workspace_bytes >= need, KF_ERR_WORKSPACE, "kf_attn_bwd: workspace of at least %zu bytes required, got %zu", need, workspace_bytes);
-    hipStream_t st = as_stream(stream);
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.o = (const char *)o; a.d_o = (const char *)d_o;
-    a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv;
-    a.lse_r = lse; a.delta = (float *)workspace;
-    a.Sqc = stat_rows(Sq);
-    a.nlse = (float *)((char *)workspace + a_align((size_t)B * H * Sq * sizeof(float)));
-    a.ndelta = (float *)((char *)a.nlse + a_align((size_t)B * H * a.Sqc * sizeof(float)));
-    a.xcd_map = ((B * H) % 8 == 0) && !knob(KNOB_ATTN_NO_XCD);
-    a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.D = D;
-    a.nbh = (int)(B * H);
-    KF_REQUIRE(scale > 0.f && scale < INFINITY, KF_ERR_INVALID, "attention: the softmax scale must be positive and finite");
-    a.scale = scale;
-    a.scale_log2e = scale * kLog2e;
-#ifdef KF_DKV_W4_STAMPS
-    extern unsigned long long *kf_attn_tl_host_ptr();
-    a.dbg = kf_attn_tl_host_ptr();
-#endif
-#ifdef KF_MUTANT
-    a.mutant = g_mutant;
-#endif
-    if (lays) { a.lq = lays[0]; a.lk = lays[1]; a.lv = lays[2]; a.lo = lays[3]; a.ldo = lays[4]; a.ldq = lays[5]; a.ldk = lays[6]; a.ldv = lays[7]; }
-    else { a.lq = a.lo = a.ldo = a.ldq = lay_contig(H, Sq, D, 2); a.lk = a.lv = a.ldk = a.ldv = lay_contig(H, Skv, D, 2); }
-    const int64_t nrows = B * H * Sq;
-    const bool tiled = mfma_ok(dtype, Sq, Skv, D); // whole 128-row tiles: every 16-bit matrix-core kernel can run
-    // round 4: 64 keys per wave (attn_bwd_dkv_w4_kernel) wherever its shape conditions hold; KF_ATTN_DKV_V4 keeps the 32-key kernel (A/B).
-    // round 6: any Sq, Skv with Skv >= Sq (w4_any_ok: rows beyond a tensor's end are zero-filled / dropped by the descriptors)
-    const bool dkv_w4 = ((tiled && Skv % K5B == 0) || w4_any_ok(dtype, Sq, Skv, D)) && a.lk.sr == a.lv.sr && a.ldk.sr == a.ldv.sr &&
-                        (uint64_t)(Sq + 32) * (uint64_t)std::max(a.lq.sr, a.ldo.sr) < (1ull << 32) && (uint64_t)K5B * (uint64_t)std::max(a.lk.sr, a.ldk.sr) < (1ull << 31) &&
-                        (uint64_t)((const char *)a.ndelta - (const char *)a.nlse) < (1ull << 31) && !knob(KNOB_ATTN_DKV_V4);
-    // a ragged shape has no other matrix-core kernels: it needs the generated dK/dV stream AND room for dS (the recomputing dQ kernel wants whole tiles)
-    const int ds_tri = ds_tri_mode(B * H, Sq, Skv, workspace_bytes - need);
-    const bool ragged_ok = !tiled && dkv_w4 && !knob(KNOB_ATTN_SPLIT_BWD) && ds_group(B * H, Sq, Skv, workspace_bytes - need, ds_tri) > 0;
-    if (tiled || ragged_ok) {
-        const bool bf = dtype == KF_BF16;
-        // exact f32 scores everywhere by default (exponent = (s - lse / scale) * scale log2 e: the row constant is -lse / scale); only the opt-in
-        // scaled-K form of the generated stream scales K by scale log2 e once per block and wants -lse log2 e
-        const bool dkv_sq = dkv_w4 && D == AD && knob(KNOB_ATTN_SCALED_OPERANDS);
-        const float rscale = dkv_sq ? kLog2e : 1.0f / scale;
-        {
-            KF_PROF("attn_bwd_delta", st);
-            // two rows per 16-lane group (four 16-byte loads in flight per lane): 0.110 -> 0.101 ms at C3; four rows: 0.100
-            const int64_t nrows_c = B * H * a.Sqc;   // (rows of the padded row-constant arrays: the pad rows are written as zeros)
-            const unsigned gd2 = (unsigned)((nrows_c + 31) / 32);
-            if (bf) attn_delta_kernel<true, 2><<<gd2, 256, 0, st>>>(a.o, a.d_o, a.delta, nrows_c, a.lse_r, a.nlse, a.ndelta, rscale, a.lo, a.ldo, Sq, H, (int)(D / 8), a.Sqc);
-            else attn_delta_kernel<false, 2><<<gd2, 256, 0, st>>>(a.o, a.d_o, a.delta, nrows_c, a.lse_r, a.nlse, a.ndelta, rscale, a.lo, a.ldo, Sq, H, (int)(D / 8), a.Sqc);
-            KF_LAUNCH_CHECK();
-        }
-        const int64_t nbh = B * H;
-        const int64_t group = knob(KNOB_ATTN_SPLIT_BWD) ? 0 : ds_group(nbh, Sq, Skv, workspace_bytes - need, ds_tri);
-        const bool keep_ds = group > 0;
-        a.ds = keep_ds ? (char *)workspace + need : nullptr;
-        a.ds_tri = ds_tri;
-        a.ds_pair = ds_pair_tiles(Sq, Skv, ds_tri);
-        a.ds_nkb = (Skv + 255) / 256;
-        const int64_t nkb4 = Skv / K4B, nxq = (Sq + FQ - 1) / FQ;
-        const int pair_kv = (nkb4 % 2 == 0 && nkb4 >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0;
-        const int pair_q = (nxq % 2 == 0 && nxq >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0;
-#define KF_DKV(BF_, DS_, D_)                                                                  \
-    {                                                                                         \
-        if ((rc = set_lds(attn_bwd_dkv_v4_kernel<BF_, DS_, D_>, K4LDS)) != KF_OK) return rc;  \
-        attn_bwd_dkv_v4_kernel<BF_, DS_, D_><<<gk4, 256, K4LDS, st>>>(a);                     \
-    }
-#define KF_DQ(BF_, D_)                                                                      \
-    {                                                                                       \
-        if ((rc = set_lds(attn_bwd_dq_ds_kernel<BF_, D_>, DQ_LDS)) != KF_OK) return rc;     \
-        attn_bwd_dq_ds_kernel<BF_, D_><<<gq2, FNT, DQ_LDS, st>>>(a);                         \
-    }
-#define KF_DQ2(BF_, D_)                                                                     \
-    {                                                                                       \
-        if ((rc = set_lds(attn_bwd_dq_v2_kernel<BF_, D_>, QLDS)) != KF_OK) return rc;       \
-        attn_bwd_dq_v2_kernel<BF_, D_><<<gq2, FNT, QLDS, st>>>(a);                           \
-    }
-        // (Tried in round 3 and removed: the dS workspace as two half-group slots with group g's dQ - HBM-bound, it streams dS - on a second
-        // stream beside group g + 1's matrix-bound dK/dV. At C3 the backward took 3.39-3.78 ms against 3.32-3.36 in sequence
-        // (profiles/r03_attn_bwd_overlap_experiment.txt): both kernels fill every CU, so the dispatcher interleaves them instead of
-        // running them side by side, and each group boundary adds a tail.)
-        const int64_t grp = keep_ds ? group : nbh;
-        // one group of (batch, head) pairs at a time: dK/dV (stores the group's dS), then dQ from it. Without dS: one group, all pairs.
-        for (int64_t bh0 = 0; bh0 < nbh; bh0 += grp) {
-            a.bh0 = bh0;
-            a.nbh = (int)std::min<int64_t>(grp, nbh - bh0);
-            a.xcd_map = (a.nbh % 8 == 0) && !knob(KNOB_ATTN_NO_XCD);
-            { // dK / dV: one wave per SIMD, pinned MFMA / VALU interleave
-                a.persist = pair_kv;
-                a.persist_rev = 1; // the short block of the pair first: 2.17 ms against 2.32 the other way round (2.22 unpaired)
-                dim3 gk4((unsigned)((a.persist ? nkb4 / 2 : nkb4) * a.nbh));
-                KF_PROF(D == 64 ? "attn_bwd_dkv_mfma_d64" : "attn_bwd_dkv_mfma", st);
-                const int64_t nkb5 = (Skv + K5B - 1) / K5B;
-                if (dkv_w4) {
-                    a.persist = (nkb5 % 2 == 0 && nkb5 >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0;
-                    dim3 gk5((unsigned)((a.persist ? nkb5 / 2 : nkb5) * a.nbh));
-                    a.nvwg = gk5.x;
-#define KF_DKV5(BF_, DS_, SQ_)                                                                                    \
-    {                                                                                                             \
-        if ((rc = set_lds(attn_bwd_dkv_w4_kernel<BF_, DS_, SQ_>, KF_DKV_W4_LDS_BYTES)) != KF_OK) return rc;        \
-        attn_bwd_dkv_w4_kernel<BF_, DS_, SQ_><<<gk5, 256, KF_DKV_W4_LDS_BYTES, st>>>(a);                          \
-    }
-#define KF_DKV5D(BF_, DS_)                                                                                              \
-    {                                                                                                                   \
-        if ((rc = set_lds(attn_bwd_dkv_w4_kernel<BF_, DS_, false, true>, KF_DKV_W4_LDS_BYTES)) != KF_OK) return rc;     \
-        attn_bwd_dkv_w4_kernel<BF_, DS_, false, true><<<gk5, 256, KF_DKV_W4_LDS_BYTES, st>>>(a);                        \
-    }
-#define KF_DKV5S(BF_, DS_) { if (D == 64) KF_DKV5D(BF_, DS_) else if (dkv_sq) KF_DKV5(BF_, DS_, true) else KF_DKV5(BF_, DS_, false) }
-                    if (bf) { if (keep_ds) KF_DKV5S(true, true) else KF_DKV5S(true, false) }
-                    else { if (keep_ds) KF_DKV5S(false, true) else KF_DKV5S(false, false) }
-#undef KF_DKV5S
-#undef KF_DKV5D
-#undef KF_DKV5
-                } else if (D == 64) {
-                    if (bf) { if (keep_ds) KF_DKV(true, true, 64) else KF_DKV(true, false, 64) }
-                    else { if (keep_ds) KF_DKV(false, true, 64) else KF_DKV(false, false, 64) }
-                } else if (bf) { if (keep_ds) KF_DKV(true, true, 128) else KF_DKV(true, false, 128) }
-                else { if (keep_ds) KF_DKV(false, true, 128) else KF_DKV(false, false, 128) }
-                KF_LAUNCH_CHECK();
-            }
-            a.persist = pair_q;
-            a.persist_rev = 0;
-            dim3 gq2((unsigned)((a.persist ? nxq / 2 : nxq) * a.nbh));
-            if (keep_ds) { // dQ = scale dS K from the stored dS
-                KF_PROF(D == 64 ? "attn_bwd_dq_mfma_d64" : "attn_bwd_dq_mfma", st);
-                if (bf) { if (D == 64) KF_DQ(true, 64) else KF_DQ(true, 128) }
-                else { if (D == 64) KF_DQ(false, 64) else KF_DQ(false, 128) }
-                KF_LAUNCH_CHECK();
-            } else { // the recomputing dQ kernel (S and dP again)
-                KF_PROF(D == 64 ? "attn_bwd_dq_mfma_split_d64" : "attn_bwd_dq_mfma_split", st);
-                if (bf) { if (D == 64) KF_DQ2(true, 64) else KF_DQ2(true, 128) }
-                else { if (D == 64) KF_DQ2(false, 64) else KF_DQ2(false, 128) }
-                KF_LAUNCH_CHECK();
-            }
-        }
-#undef KF_DKV
-#undef KF_DQ
-#undef KF_DQ2
-        return KF_OK;
-    }
-    // (from here on: kernels of contiguous [B, H, S, D] tensors only)
-    KF_REQUIRE(!lays, KF_ERR_UNSUPPORTED, "kf_attn_bwd_strided: this shape / stride / workspace combination has no matrix-core kernel (ragged lengths want room for dS)");
-    const unsigned gd = (unsigned)((nrows + 3) / 4);
-    if (dtype == KF_F32 && (D == 64 || D == 128) && Sq % 32 == 0 && Skv % 32 == 0) {
-        // exact-f32 MFMA backward (the f32 forward's counterpart; the reference has no backward)
-        {
-            KF_PROF("attn_bwd_delta", st);
-            attn_delta_generic_kernel<float><<<gd, 256, 0, st>>>((const float *)o, (const float *)d_o, a.delta, nrows, (int)D);
-            KF_LAUNCH_CHECK();
-        }
-        const size_t tiles = (size_t)2 * XK * (D + 4) * sizeof(float) + 256, slabs = (size_t)4 * 32 * (D + 4) * sizeof(float);
-        const size_t ldsx = std::max(tiles, slabs);
-        const int64_t nxq = (Sq + XQ - 1) / XQ, nkb = (Skv + XQ - 1) / XQ;
-        {
-            a.persist = (nkb % 2 == 0 && nkb >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0;
-            dim3 g((unsigned)((a.persist ? nkb / 2 : nkb) * B * H));
-            KF_PROF("attn_bwd_dkv_f32_mfma", st);
-            if (D == 128) {
-                if ((rc = set_lds(attn_bwd_dkv_f32_mfma_kernel<128>, ldsx)) != KF_OK) return rc;
-                attn_bwd_dkv_f32_mfma_kernel<128><<<g, 256, ldsx, st>>>(a);
-            } else {
-                if ((rc = set_lds(attn_bwd_dkv_f32_mfma_kernel<64>, ldsx)) != KF_OK) return rc;
-                attn_bwd_dkv_f32_mfma_kernel<64><<<g, 256, ldsx, st>>>(a);
-            }
-            KF_LAUNCH_CHECK();
-        }
-        {
-            a.persist = (nxq % 2 == 0 && nxq >= 4 && !knob(KNOB_ATTN_NO_PAIR)) ? 1 : 0;
-            dim3 g((unsigned)((a.persist ? nxq / 2 : nxq) * B * H));
-            KF_PROF("attn_bwd_dq_f32_mfma", st);
-            if (D == 128) {
-                if ((rc = set_lds(attn_bwd_dq_f32_mfma_kernel<128>, ldsx)) != KF_OK) return rc;
-                attn_bwd_dq_f32_mfma_kernel<128><<<g, 256, ldsx, st>>>(a);
-            } else {
-                if ((rc = set_lds(attn_bwd_dq_f32_mfma_kernel<64>, ldsx)) != KF_OK) return rc;
-                attn_bwd_dq_f32_mfma_kernel<64><<<g, 256, ldsx, st>>>(a);
-            }
-            KF_LAUNCH_CHECK();
-        }
-        return KF_OK;
-    }
-    const int DP = (int)D + 1;
-    const size_t lds = sizeof(float) * ((size_t)2 * GQ * DP + (size_t)2 * GK * DP + (size_t)2 * GQ * (GK + 1) + 2 * GK);
-    dim3 gq((unsigned)((Sq + GQ - 1) / GQ), (unsigned)(B * H)), gk((unsigned)((Skv + GQ - 1) / GQ), (unsigned)(B * H));
-    KF_PROF("attn_bwd_generic", st);
-#define KF_GENERIC_BWD(T)                                                                                   \
-    attn_delta_generic_kernel<T><<<gd, 256, 0, st>>>((const T *)o, (const T *)d_o, a.delta, nrows, (int)D);  \
-    KF_LAUNCH_CHECK();                                                                                      \
-    if ((rc = set_lds(attn_bwd_generic_kernel<T, 0>, lds)) != KF_OK) return rc;                             \
-    if ((rc = set_lds(attn_bwd_generic_kernel<T, 1>, lds)) != KF_OK) return rc;                             \
-    attn_bwd_generic_kernel<T, 0><<<gq, 256, lds, st>>>(a);                                                 \
-    KF_LAUNCH_CHECK();                                                                                      \
-    attn_bwd_generic_kernel<T, 1><<<gk, 256, lds, st>>>(a);                                                 \
-    KF_LAUNCH_CHECK();
-    switch (dtype) {
-    case KF_F32: { KF_GENERIC_BWD(float) } break;
-    case KF_BF16: { KF_GENERIC_BWD(bf16_t) } break;
-    default: { KF_GENERIC_BWD(f16_t) } break;
-    }
-#undef KF_GENERIC_BWD
-    return KF_OK;
 }
 
 #ifdef KF_ATTN_TIMELINE

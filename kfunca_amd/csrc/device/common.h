@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "kfunca_hip.h"
 
 namespace kf {
@@ -108,11 +110,26 @@ long knob_int(Knob k, long dflt); // its integer value, dflt when unset
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), not once per launch
 int ensure_dynamic_lds(const void *kernel, int bytes);
-#define KF_ENSURE_LDS(kernel, bytes)                                                      \
-    do {                                                                                  \
-        int rc_ = ::kf::ensure_dynamic_lds((const void *)(kernel), (int)(bytes));         \
-        if (rc_ != KF_OK) return rc_;                                                     \
-    } while (0)
+
+// One kernel launch: raise the kernel's dynamic-LDS limit when it takes any, launch, check (KF_LAUNCH_CHECK).
+template <typename... P, typename... A>
+static inline int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A &&...args) {
+    if (lds > 0) {
+        const int rc = ensure_dynamic_lds((const void *)kernel, (int)lds);
+        if (rc != KF_OK) return rc;
+    }
+    kernel<<<grid, block, lds, st>>>(static_cast<A &&>(args)...);
+    KF_LAUNCH_CHECK();
+    return KF_OK;
+}
+
+// Run-time flags as template arguments: with_flags(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...),
+// so f can name kernel<B0, B1> for every combination of the flags it is given.
+template <typename F> static inline int with_flags(F &&f) { return f(); }
+template <typename F, typename... B> static inline int with_flags(F &&f, bool b, B... rest) {
+    return b ? with_flags([&](auto... x) { return f(std::true_type{}, x...); }, rest...)
+             : with_flags([&](auto... x) { return f(std::false_type{}, x...); }, rest...);
+}
 
 // kf_sort with a promise about the keys (sort.hip)
 int sort_with_key_bits(int dtype, const void *keys_in, void *keys_out, int64_t *pos_out, int64_t nseg, int64_t n, int descending, void *workspace,

@@ -1201,29 +1201,6 @@ extern "C" int kf_gemm_workspace_bytes(int dtype, int trans_a, int trans_b, int6
     return KF_OK;
 }
 
-template <bool BF>
-static int launch_h256(const GemmArgs &g, bool tra, bool trb, hipStream_t st) {
-    const unsigned grid = (unsigned)((g.M / G_BM) * (g.N / G_BN));
-    const bool tail = g.mul || g.add || g.aux;
-#define KF_W4(TA, TB)                                                                                                     \
-    {                                                                                                                     \
-        if (tail) {                                                                                                       \
-            KF_ENSURE_LDS((gemm_w4_tail_kernel<BF, TA, TB>), G_LDS);                                                      \
-            gemm_w4_tail_kernel<BF, TA, TB><<<grid, W4_NT, G_LDS, st>>>(g);                                               \
-        } else {                                                                                                          \
-            KF_ENSURE_LDS((gemm_w4_kernel<BF, TA, TB>), G_LDS);                                                           \
-            gemm_w4_kernel<BF, TA, TB><<<grid, W4_NT, G_LDS, st>>>(g);                                                    \
-        }                                                                                                                 \
-    }
-    if (!tra && !trb) KF_W4(false, false)
-    else if (!tra && trb) KF_W4(false, true)
-    else if (tra && !trb) KF_W4(true, false)
-    else KF_W4(true, true)
-#undef KF_W4
-    KF_LAUNCH_CHECK();
-    return KF_OK;
-}
-
 // diagnostic entry, compiled only into the separate diagnostic library (-DKF_DIAG_BUILD, kfunca_amd/_build.py build_diag;
 // tools/gemm_clock.py) - never into libkfunca_hip.so: bf16 A [M,K] x B stored [N,K] through the 4-wave kernel with clock
 // stamps; diag receives {core-clock cycles, 100 MHz ticks} of the main loop per workgroup
@@ -1231,10 +1208,7 @@ static int launch_h256(const GemmArgs &g, bool tra, bool trb, hipStream_t st) {
 extern "C" int kfdbg_gemm_clock(int64_t M, int64_t N, int64_t K, const void *A, const void *B, void *C, void *diag, void *stream) {
     KF_REQUIRE(h256_ok(M, N, K) && A && B && C && diag, KF_ERR_INVALID, "kfdbg_gemm_clock: 256-tile shapes only");
     GemmArgs g{A, B, C, diag, M, N, K, K, K, N, 1.f, 0.f, KF_EPI_NONE, 4};
-    KF_ENSURE_LDS((gemm_w4_kernel<true, false, false, true>), G_LDS);
-    gemm_w4_kernel<true, false, false, true><<<(unsigned)((M / G_BM) * (N / G_BN)), W4_NT, G_LDS, as_stream(stream)>>>(g);
-    KF_LAUNCH_CHECK();
-    return KF_OK;
+    return launch(gemm_w4_kernel<true, false, false, true>, (unsigned)((M / G_BM) * (N / G_BN)), W4_NT, G_LDS, as_stream(stream), g);
 }
 #endif
 
@@ -1273,15 +1247,7 @@ extern "C" int kf_gemm_grouped(int dtype, int count, const kf_gemm_problem *p, v
         g0.group_m = g1.group_m = 4;
         const unsigned n0 = (unsigned)((p[0].M / G_BM) * (p[0].N / G_BN)), n1 = (unsigned)((p[1].M / G_BM) * (p[1].N / G_BN));
         KF_PROF(dtype == KF_BF16 ? "gemm_bf16_mfma_pair" : "gemm_f16_mfma_pair", st);
-        if (dtype == KF_BF16) {
-            KF_ENSURE_LDS((gemm_w4_pair_kernel<true>), G_LDS);
-            gemm_w4_pair_kernel<true><<<n0 + n1, W4_NT, G_LDS, st>>>(g0, g1, n0, n1);
-        } else {
-            KF_ENSURE_LDS((gemm_w4_pair_kernel<false>), G_LDS);
-            gemm_w4_pair_kernel<false><<<n0 + n1, W4_NT, G_LDS, st>>>(g0, g1, n0, n1);
-        }
-        KF_LAUNCH_CHECK();
-        return KF_OK;
+        return launch(dtype == KF_BF16 ? gemm_w4_pair_kernel<true> : gemm_w4_pair_kernel<false>, n0 + n1, W4_NT, G_LDS, st, g0, g1, n0, n1);
     }
     for (int i = 0; i < count; ++i) {
         kf_gemm_epilogue e{};
@@ -1326,69 +1292,42 @@ static int gemm_impl(int dtype, int trans_a, int trans_b, int64_t M, int64_t N, 
     g.group_m = (M / 256) * (N / 256) >= 1024 ? 8 : 4;
 
     const bool al16 = ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0);
+    const bool ta = trans_a != 0, tb = trans_b != 0, bf = dtype == KF_BF16;
     if (dtype == KF_F32 && M % 64 == 0 && N % 64 == 0 && K % F_BK == 0 && K > 0 && al16 && lda % 4 == 0 && ldb % 4 == 0) {
         // 128-tiles unless they would leave a quarter of the CUs idle and 64-tiles are possible... or are the only option
         const bool t128 = M % F_BM == 0 && N % F_BN == 0 && (M / F_BM) * (N / F_BN) >= 192;
+        const int64_t t = t128 ? 128 : 64;
         KF_PROF(t128 ? "gemm_f32_mfma" : "gemm_f32_mfma_t64", st);
-#define KF_F32G(T_)                                                                                          \
-    {                                                                                                        \
-        const unsigned grid = (unsigned)((M / T_) * (N / T_));                                               \
-        if (!trans_a && !trans_b) gemm_f32_kernel<false, false, T_><<<grid, 256, 0, st>>>(g);                \
-        else if (!trans_a && trans_b) gemm_f32_kernel<false, true, T_><<<grid, 256, 0, st>>>(g);             \
-        else if (trans_a && !trans_b) gemm_f32_kernel<true, false, T_><<<grid, 256, 0, st>>>(g);             \
-        else gemm_f32_kernel<true, true, T_><<<grid, 256, 0, st>>>(g);                                       \
-    }
-        if (t128) KF_F32G(128) else KF_F32G(64)
-#undef KF_F32G
-        KF_LAUNCH_CHECK();
-        return KF_OK;
+        return with_flags([&](auto TA, auto TB, auto T128) {
+            return launch(gemm_f32_kernel<TA, TB, T128 ? 128 : 64>, (unsigned)((M / t) * (N / t)), 256, 0, st, g);
+        }, ta, tb, t128);
     }
     if (dtype == KF_F64 && M % D_T == 0 && N % D_T == 0 && K % D_BK == 0 && K > 0 && al16 && lda % 2 == 0 && ldb % 2 == 0) {
-        const unsigned grid = (unsigned)((M / D_T) * (N / D_T));
         KF_PROF("gemm_f64_mfma", st);
-        if (!trans_a && !trans_b) gemm_f64_kernel<false, false><<<grid, 256, 0, st>>>(g);
-        else if (!trans_a && trans_b) gemm_f64_kernel<false, true><<<grid, 256, 0, st>>>(g);
-        else if (trans_a && !trans_b) gemm_f64_kernel<true, false><<<grid, 256, 0, st>>>(g);
-        else gemm_f64_kernel<true, true><<<grid, 256, 0, st>>>(g);
-        KF_LAUNCH_CHECK();
-        return KF_OK;
+        return with_flags([&](auto TA, auto TB) { return launch(gemm_f64_kernel<TA, TB>, (unsigned)((M / D_T) * (N / D_T)), 256, 0, st, g); }, ta, tb);
     }
     if ((dtype == KF_BF16 || dtype == KF_F16) && h_fast_ok(M, N, K) && al16 && lda % 8 == 0 && ldb % 8 == 0) {
+        const bool trb = !tb; // transposed-read operands: consumed as they lie in memory, no re-layout pass
         if (h256_ok(M, N, K)) { // every operand layout is consumed in place
             // products with mul / add / aux operands take the 4-wave kernel's tail instantiation (round 3; same loop, same accumulation
             // order, so aux is bit-identical to the plain product)
-            KF_PROF(dtype == KF_BF16 ? "gemm_bf16_mfma" : "gemm_f16_mfma", st);
-            return dtype == KF_BF16 ? launch_h256<true>(g, trans_a != 0, !trans_b, st) : launch_h256<false>(g, trans_a != 0, !trans_b, st);
+            const bool tail = g.mul || g.add || g.aux;
+            KF_PROF(bf ? "gemm_bf16_mfma" : "gemm_f16_mfma", st);
+            return with_flags([&](auto BF, auto TA, auto TB) {
+                return launch(tail ? gemm_w4_tail_kernel<BF, TA, TB> : gemm_w4_kernel<BF, TA, TB>, (unsigned)((M / G_BM) * (N / G_BN)), W4_NT, G_LDS, st, g);
+            }, bf, ta, trb);
         }
         unsigned grid = (unsigned)((M / H_BM) * (N / H_BN));
-        const size_t lds = (size_t)H_STAGES * 2 * H_TILE_BYTES;
         const int slices = splitk_slices(dtype, M, N, K);
         const bool split = slices > 1 && workspace && workspace_bytes >= (size_t)slices * M * N * sizeof(float) && (uintptr_t)workspace % 16 == 0 &&
                            N % 4 == 0;
         if (split) { g.split = slices; g.part = (float *)workspace; grid *= (unsigned)slices; }
-        KF_PROF(dtype == KF_BF16 ? (split ? "gemm_bf16_mfma_128_splitk" : "gemm_bf16_mfma_128") : (split ? "gemm_f16_mfma_128_splitk" : "gemm_f16_mfma_128"), st);
-        const bool tra = trans_a != 0, trb = !trans_b; // transposed-read operands: consumed as they lie in memory, no re-layout pass
-#define KF_H128(BF_, TA, TB)                                                                                                   \
-    {                                                                                                                          \
-        KF_ENSURE_LDS((gemm_h_kernel<BF_, TA, TB>), (int)lds); \
-        gemm_h_kernel<BF_, TA, TB><<<grid, 256, lds, st>>>(g);                                                                 \
-    }
-#define KF_H128_L(BF_)                                  \
-    if (!tra && !trb) KF_H128(BF_, false, false)         \
-    else if (!tra && trb) KF_H128(BF_, false, true)      \
-    else if (tra && !trb) KF_H128(BF_, true, false)      \
-    else KF_H128(BF_, true, true)
-        if (dtype == KF_BF16) { KF_H128_L(true) } else { KF_H128_L(false) }
-#undef KF_H128_L
-#undef KF_H128
-        KF_LAUNCH_CHECK();
-        if (split) {
-            const unsigned gf = (unsigned)((M * (N / 4) + 255) / 256);
-            if (dtype == KF_BF16) gemm_splitk_fold_kernel<true><<<gf, 256, 0, st>>>(g);
-            else gemm_splitk_fold_kernel<false><<<gf, 256, 0, st>>>(g);
-            KF_LAUNCH_CHECK();
-        }
-        return KF_OK;
+        KF_PROF(bf ? (split ? "gemm_bf16_mfma_128_splitk" : "gemm_bf16_mfma_128") : (split ? "gemm_f16_mfma_128_splitk" : "gemm_f16_mfma_128"), st);
+        const int rc = with_flags([&](auto BF, auto TA, auto TB) {
+            return launch(gemm_h_kernel<BF, TA, TB>, grid, 256, (size_t)H_STAGES * 2 * H_TILE_BYTES, st, g);
+        }, bf, ta, trb);
+        if (rc != KF_OK || !split) return rc;
+        return launch(bf ? gemm_splitk_fold_kernel<true> : gemm_splitk_fold_kernel<false>, (unsigned)((M * (N / 4) + 255) / 256), 256, 0, st, g);
     }
     if (const PadPlan pp = pad_plan(dtype, M, N, K); pp.use && workspace && workspace_bytes >= pp.total && (uintptr_t)workspace % 16 == 0 &&
                                                      !(g.mul || g.add || g.aux || g.c_f32) && K > 0) {
@@ -1402,13 +1341,13 @@ static int gemm_impl(int dtype, int trans_a, int trans_b, int64_t M, int64_t N, 
             const int64_t big = std::max(std::max(pp.Mp * pp.Kp, pp.Kp * pp.Np), pp.Mp * pp.Np) * es / 16;
             KF_REQUIRE((big + 255) / 256 <= 0x7fffffffLL, KF_ERR_INDEX_RANGE, "kf_gemm: a padded operand image of %lld pieces exceeds the grid limit", (long long)big);
         }
+        int rc = KF_OK;
         {
             KF_PROF("gemm_pad", st);
             auto pad = [&](const void *src, int64_t ld, int64_t rows, int64_t cols, char *dst, int64_t rows_p, int64_t cols_p) {
                 const int64_t total = rows_p * (cols_p * es / 16);
-                const unsigned gr = (unsigned)((total + 255) / 256);
-                if (es == 2) gemm_pad_copy_kernel<2><<<gr, 256, 0, st>>>((const char *)src, ld, rows, cols, dst, cols_p, total);
-                else gemm_pad_copy_kernel<4><<<gr, 256, 0, st>>>((const char *)src, ld, rows, cols, dst, cols_p, total);
+                return launch(es == 2 ? gemm_pad_copy_kernel<2> : gemm_pad_copy_kernel<4>, (unsigned)((total + 255) / 256), 256, 0, st, (const char *)src, ld,
+                              rows, cols, dst, cols_p, total);
             };
             // an operand that already is whole tiles on 16-byte rows is read where it lies (M = 16 rows against a tile-aligned 8192 x 8192 B:
             // copying B would cost twice the product)
@@ -1416,26 +1355,20 @@ static int gemm_impl(int dtype, int trans_a, int trans_b, int64_t M, int64_t N, 
             use_a = ar == arp && ac == acp && (uintptr_t)A % 16 == 0 && lda % ldq == 0;
             use_b = br == brp && bc == bcp && (uintptr_t)B % 16 == 0 && ldb % ldq == 0;
             use_c = M == pp.Mp && N == pp.Np;
-            if (!use_a) pad(A, lda, ar, ac, pa, arp, acp);
-            if (!use_b) pad(B, ldb, br, bc, pb, brp, bcp);
-            if (!use_c && beta != 0.f) pad(C, ldc, M, N, pc, pp.Mp, pp.Np);
-            if (!use_c && epilogue == KF_EPI_BIAS_ROW) pad(bias, N, 1, N, pbias, 1, pp.Np);
-            KF_LAUNCH_CHECK();
+            if (!use_a) rc = pad(A, lda, ar, ac, pa, arp, acp);
+            if (rc == KF_OK && !use_b) rc = pad(B, ldb, br, bc, pb, brp, bcp);
+            if (rc == KF_OK && !use_c && beta != 0.f) rc = pad(C, ldc, M, N, pc, pp.Mp, pp.Np);
+            if (rc == KF_OK && !use_c && epilogue == KF_EPI_BIAS_ROW) rc = pad(bias, N, 1, N, pbias, 1, pp.Np);
+            if (rc != KF_OK) return rc;
         }
-        const int rc = gemm_impl(dtype, trans_a, trans_b, pp.Mp, pp.Np, pp.Kp, alpha, use_a ? A : (const void *)pa, use_a ? lda : acp, use_b ? B : (const void *)pb,
+        rc = gemm_impl(dtype, trans_a, trans_b, pp.Mp, pp.Np, pp.Kp, alpha, use_a ? A : (const void *)pa, use_a ? lda : acp, use_b ? B : (const void *)pb,
                                  use_b ? ldb : bcp, beta, use_c ? C : (void *)pc, use_c ? ldc : pp.Np, epilogue,
                                  epilogue == KF_EPI_BIAS_ROW ? (use_c ? bias : (const void *)pbias) : nullptr, nullptr, stream, pp.inner_bytes ? inner : nullptr,
                                  pp.inner_bytes);
-        if (rc != KF_OK) return rc;
-        if (!use_c) {
-            KF_PROF("gemm_pad", st);
-            const int64_t total = M * ((N + 16 / es - 1) / (16 / es));
-            const unsigned gr = (unsigned)((total + 255) / 256);
-            if (es == 2) gemm_unpad_copy_kernel<2><<<gr, 256, 0, st>>>(pc, pp.Np, (char *)C, ldc, M, N);
-            else gemm_unpad_copy_kernel<4><<<gr, 256, 0, st>>>(pc, pp.Np, (char *)C, ldc, M, N);
-            KF_LAUNCH_CHECK();
-        }
-        return KF_OK;
+        if (rc != KF_OK || use_c) return rc;
+        KF_PROF("gemm_pad", st);
+        const int64_t total = M * ((N + 16 / es - 1) / (16 / es));
+        return launch(es == 2 ? gemm_unpad_copy_kernel<2> : gemm_unpad_copy_kernel<4>, (unsigned)((total + 255) / 256), 256, 0, st, pc, pp.Np, (char *)C, ldc, M, N);
     }
     if (const PadPlan pp = pad_plan(dtype, M, N, K); pp.use && workspace && !(g.mul || g.add || g.aux || g.c_f32)) {
         // a caller that DID bring scratch lands on the scalar kernel (20-40x slower): say why, once
@@ -1448,14 +1381,7 @@ static int gemm_impl(int dtype, int trans_a, int trans_b, int64_t M, int64_t N, 
     }
     const int64_t gtiles = ((N + 31) / 32) * ((M + 31) / 32);
     KF_REQUIRE(gtiles <= 0x7fffffffLL, KF_ERR_INDEX_RANGE, "kf_gemm: %lld output tiles exceed the grid limit", (long long)gtiles);
-    const unsigned grid = (unsigned)gtiles;
     KF_PROF("gemm_generic", st);
-    switch (dtype) {
-    case KF_F32: gemm_generic_kernel<float><<<grid, 256, 0, st>>>(g, trans_a, trans_b); break;
-    case KF_F64: gemm_generic_kernel<double><<<grid, 256, 0, st>>>(g, trans_a, trans_b); break;
-    case KF_BF16: gemm_generic_kernel<bf16_t><<<grid, 256, 0, st>>>(g, trans_a, trans_b); break;
-    default: gemm_generic_kernel<f16_t><<<grid, 256, 0, st>>>(g, trans_a, trans_b); break;
-    }
-    KF_LAUNCH_CHECK();
-    return KF_OK;
+    return launch(dtype == KF_F32 ? gemm_generic_kernel<float> : dtype == KF_F64 ? gemm_generic_kernel<double> : bf ? gemm_generic_kernel<bf16_t> : gemm_generic_kernel<f16_t>,
+                  (unsigned)gtiles, 256, 0, st, g, trans_a, trans_b);
 }

@@ -719,15 +719,12 @@ static int run_sort(const void *in, void *out, int64_t *pos, int64_t nseg, int64
 #define KF_BLOCK_RADIX(NW_, IT_)                                                                                                         \
     {                                                                                                                                    \
         const size_t lds = block_radix_lds<NW_, IT_>(sizeof(U));                                                                         \
-        KF_ENSURE_LDS((sort_block_radix_kernel<U, W, KIND, NW_, IT_>), lds);                                                                 \
-        sort_block_radix_kernel<U, W, KIND, NW_, IT_><<<(unsigned)nseg, NW_ * 64, lds, st>>>(a);                                          \
+        return launch(sort_block_radix_kernel<U, W, KIND, NW_, IT_>, (unsigned)nseg, NW_ * 64, lds, st, a);                                  \
     }
         if (n <= 1024) KF_BLOCK_RADIX(4, 4)
         else if (n <= 4096) KF_BLOCK_RADIX(4, 16)
         else KF_BLOCK_RADIX(8, 16)
 #undef KF_BLOCK_RADIX
-        KF_LAUNCH_CHECK();
-        return KF_OK;
     }
     if (p.small && n <= 64) { // rows of 64 slots in registers
         SmallArgs a{in, out, pos, nseg, (int)n, 0, npass, desc};
@@ -796,10 +793,8 @@ static int run_sort(const void *in, void *out, int64_t *pos, int64_t nseg, int64
             radix_scan_tiles_kernel<<<(unsigned)(nseg * p.nchunks), 256, 0, st>>>(counts, cbase, p.ntiles, p.nchunks);
             radix_scan_kernel<<<(unsigned)nseg, 1024, 0, st>>>(cbase, dbase, p.nchunks);
         }
-        const size_t lds = (size_t)R_TILE * (sizeof(U) + 4);
-        KF_ENSURE_LDS((radix_scatter_kernel<U, W, KIND>), lds);
-        radix_scatter_kernel<U, W, KIND><<<(unsigned)grid, R_NT, lds, st>>>(a);
-        KF_LAUNCH_CHECK();
+        const int rc = launch(radix_scatter_kernel<U, W, KIND>, (unsigned)grid, R_NT, (size_t)R_TILE * (sizeof(U) + 4), st, a);
+        if (rc != KF_OK) return rc;
     }
     return KF_OK;
 }
