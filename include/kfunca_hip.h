@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
+#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table, kf_attn_fwd_gqa, kf_attn_bwd_gqa_workspace_bytes, kf_attn_bwd_gqa):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
 
 /* ---- status ------------------------------------------------------------------------------ */
 enum {
@@ -469,7 +469,8 @@ int kf_attn_bwd_scaled(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv,
  * [B*S, 3*H*D] gradient. Contiguous [B,H,S,D] is {H*S*D, S*D, D}. lse stays [B,H,Sq] contiguous f32.
  * 16-bit matrix-core path only (dtype KF_BF16 / KF_F16, D = 64 or 128; Skv >= Sq with any lengths, or Sq and Skv multiples of 128;
  * KF_ERR_UNSUPPORTED otherwise: make contiguous copies and call the plain entries). Strides are multiples of 8 elements, operands 16-byte aligned.
- * Workspace as kf_attn_bwd_workspace_bytes().
+ * Workspace as kf_attn_bwd_workspace_bytes(). Grouped-query attention (fewer K/V heads than query heads, read in place from the packed
+ * [B*S, (Hq + 2 Hkv) D] projection that kf_rope rotates) is kf_attn_*_gqa below.
  */
 typedef struct kf_attn_layout {
     int64_t batch, head, row; /* element strides of dims B, H, S */
@@ -482,6 +483,34 @@ int kf_attn_bwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv
                         const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
                         const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
                         void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Grouped-query attention (GQA; Hkv = 1 is multi-query attention): query head h of batch b attends to K/V head h / G, G = Hq / Hkv.
+ * q, o, d_o, dq are [B, Hq, S, D]; k, v, dk, dv are [B, Hkv, Skv, D]; lse is [B, Hq, Sq] contiguous f32. Every other rule is that of the
+ * entries above: causal mask, scale, dtypes, D <= 256, any Sq / Skv, the four tiers. The layouts are ALL NULL - contiguous tensors, every
+ * tier - or ALL given - the _strided rules (16-bit matrix-core path only, else KF_ERR_UNSUPPORTED); a mix is KF_ERR_INVALID, and so are
+ * Hkv < 1, Hkv > Hq, Hq % Hkv != 0, null operands, bad strides and a workspace below the minimum, all before any device call.
+ * Hkv == Hq is exactly kf_attn_*_scaled (no layouts) / kf_attn_*_strided (layouts): the same launches, workspace and results.
+ * The forward and dQ read K/V head h / G where the multi-head kernels read head h: o, lse and dq equal the multi-head call on K and V
+ * repeated G times along the head dim, bit for bit. With G > 1 the dK/dV kernels run over the B Hq query heads into two partial arrays
+ * in the workspace, and one more kernel (profile label attn_bwd_dkv_group_sum) forms
+ *     dk[b, j] = dtype( ((f32 t_0 + t_1) + t_2) + ... + t_{G-1} ),   t_g = the dK of query head j G + g, rounded to the dtype
+ * - the multi-head call's per-head dK on repeated K/V, summed once over each group in ascending g - and dv likewise. No atomics:
+ * bitwise reproducible. Workspace (kf_attn_bwd_gqa_workspace_bytes): MINIMUM = the statistics of B Hq pairs (kf_attn_bwd's minimum) + two
+ * 256-aligned arrays of B Hq Skv D elements of the dtype (G > 1 only; 512 MiB at bf16 B 8, Hq 32, S 4096, D 128); RECOMMENDED = minimum +
+ * the dS part kf_attn_bwd_workspace_bytes gives for B Hq pairs. What lies beyond the minimum holds dS, as in kf_attn_bwd; any
+ * workspace_bytes >= the minimum is accepted. minimum may be NULL.
+ */
+int kf_attn_fwd_gqa(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                    const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
+                    const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream);
+int kf_attn_bwd_gqa_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D,
+                                    size_t *recommended, size_t *minimum);
+int kf_attn_bwd_gqa(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                    const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
+                    const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo,
+                    void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
+                    void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- rotary position embeddings (no reference counterpart: the position signal between the QKV projection and attention) ---- */
 /*

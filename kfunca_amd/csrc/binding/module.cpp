@@ -382,7 +382,11 @@ PYBIND11_MODULE(_C, m) {
     m.def("qkv_linear", [](const Tensor &x, const Tensor &w_qkv, py::object bias) {
         return gpu::gemm_fused(x, w_qkv, 1.0f, bias.is_none() ? Tensor() : bias.cast<Tensor>(), Tensor(), Tensor());
     }, py::arg("x"), py::arg("w_qkv"), py::arg("bias") = py::none());
-    m.def("causal_attention_qkv", &gpu::causal_attention_qkv, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"));
+    // kv_heads: grouped-query attention on the packed [B*S, (H + 2*kv_heads)*D] projection (rope_qkv's kv_heads layout)
+    m.def("causal_attention_qkv", [](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads) {
+        return gpu::causal_attention_qkv(qkv, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>());
+    }, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none());
+    m.def("causal_attention_gqa", &gpu::causal_attention_gqa, py::arg("q"), py::arg("k"), py::arg("v"));
     // rotary position embeddings: f64-accurate tables, and the rotation of q and k in place in the packed projection (one launch each way)
     m.def("rope_table", [](int64_t max_positions, int64_t rotary_dim, double base, int device) {
         auto [c, sn] = gpu::rope_table(max_positions, rotary_dim, base, device);

@@ -65,6 +65,12 @@ Tensor embedding(const Tensor &table, const Tensor &indices);
 //   QKV projection (columns q | k | v, each H heads of D); q, k, v are read IN PLACE, the result is [B*S, H*D] - the layout
 //   the output projection takes - and the backward writes one packed gradient: no split / permute / contiguous copies
 Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H);
+//   the same with kv_heads = Hkv K/V heads (grouped-query attention): qkv is [B*S, (H + 2*Hkv)*D], the layout rope_qkv(kv_heads = Hkv) rotates;
+//   kv_heads < 0 or == H is the call above
+Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads);
+//   causal_attention_gqa: grouped-query attention, q [B, Hq, Sq, D], k and v [B, Hkv, Skv, D] with Hkv dividing Hq; query head h attends
+//   to K/V head h / (Hq / Hkv). The gradients are shaped like their inputs; dk, dv are summed over each group (include/kfunca_hip.h: kf_attn_bwd_gqa)
+Tensor causal_attention_gqa(const Tensor &q, const Tensor &k, const Tensor &v);
 //   gemm_fused (fused projections, README.md:32): out = (alpha a b + bias) o mul + add in ONE kernel (kf_gemm_ex) - what the
 //   reference API spells gemm + add + mul + add over three extra passes of the output. bias [N]; mul, add shaped like the output;
 //   any of the three may be undefined. Residual connection: add = the stream; gated MLP: mul = the other projection.

@@ -51,6 +51,7 @@ struct AttnArgs {
     float *delta;
     float *nlse, *ndelta; // backward, dK/dV v4: -lse * sqrt(D) and -delta (initial accumulators of S and dP)
     int64_t B, H, Sq, Skv, D;
+    int G;             // grouped-query attention: query heads per K/V head (H / Hkv; 1: multi-head). K and V are read at head (bh % H) / G
     int64_t Sqc;       // backward, 16-bit matrix-core path: rows per head of the two row-constant arrays nlse / ndelta = Sq rounded up to 32 (a slice), pad rows zero
     float scale;
     float scale_log2e; // scale * log2(e), formed on the host (attn_fwd_w4_kernel hands it to its instruction stream as a scalar)
@@ -109,6 +110,13 @@ __host__ __device__ inline int64_t ds_tile_index(int64_t kwb, int64_t sl, int64_
 // fetching every head into every L2. Speed only: any placement is correct.
 // base of (batch, head) bh = b * H + h under a layout
 __device__ __forceinline__ int64_t a_head(const AttnArgs::Lay &l, int64_t bh, int64_t H) { return (bh / H) * l.sb + (bh % H) * l.sh; }
+// base of the K/V head that query pair bh reads: head (bh % H) / G of batch bh / H (G = 1: a_head). Every K or V read goes through this;
+// Q, O, dO, dQ, lse, delta, dS and the dK / dV the kernels write stay indexed by the query pair
+__device__ __forceinline__ int64_t a_head_kv(const AttnArgs::Lay &l, int64_t bh, int64_t H, int G) {
+    return (bh / H) * l.sb + (int64_t)((int)(bh % H) / G) * l.sh;
+}
+// the same for the kernels of contiguous tensors: the flat K/V head index (batch bh / H, head (bh % H) / G of H / G)
+__device__ __forceinline__ int64_t a_kv_index(int64_t bh, int64_t H, int G) { return (bh / H) * (H / G) + (int)(bh % H) / G; }
 
 __device__ __forceinline__ void a_block_map(int nx, int nbh, int xcd_map, int &x, int64_t &bh, unsigned id = blockIdx.x) {
     if (xcd_map) { // nbh % 8 == 0
@@ -485,8 +493,8 @@ __global__ __launch_bounds__(FNT, 2) void attn_fwd_v3_kernel(const AttnArgs a) {
     a_block_map(nwx, a.nbh, a.xcd_map, xb0, bh);
     const int rgrp = ((wid & 3) << 1) | (wid >> 2);
     const bool late = __builtin_amdgcn_readfirstlane(wid) >= 4;
-    const char *Kg = a.k + a_head(a.lk, bh, a.H);
-    const char *Vg = a.v + a_head(a.lv, bh, a.H);
+    const char *Kg = a.k + a_head_kv(a.lk, bh, a.H, a.G);
+    const char *Vg = a.v + a_head_kv(a.lv, bh, a.H, a.G);
     int ko[KS], vo[DB][2];
 #pragma unroll
     for (int kk = 0; kk < KS; ++kk) ko[kk] = a_off(xl, kk * 2 + hl);
@@ -638,7 +646,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w4_kernel(const AttnArgs a) {
     int xb0;
     int64_t bh;
     a_block_map(nwx, a.nbh, a.xcd_map, xb0, bh, vwg);
-    const char *kp = a.k + a_head(a.lk, bh, a.H), *vp = a.v + a_head(a.lv, bh, a.H);
+    const char *kp = a.k + a_head_kv(a.lk, bh, a.H, a.G), *vp = a.v + a_head_kv(a.lv, bh, a.H, a.G);
     const char *qh = a.q + a_head(a.lq, bh, a.H);
     char *oh = a.out + a_head(a.lo, bh, a.H);
 #pragma nounroll
@@ -802,8 +810,8 @@ __global__ __launch_bounds__(FNT, 2) void attn_bwd_dq_v2_kernel(const AttnArgs a
     // a.persist: a workgroup takes query block x and its causal mirror nxb - 1 - x (equal work per workgroup, as in the forward)
     const int nwx = a.persist ? nxb / (2 * a.persist) : nxb;
     a_block_map(nwx, a.nbh, a.xcd_map, xb0, bh);
-    const char *Kg = a.k + a_head(a.lk, bh, a.H);
-    const char *Vg = a.v + a_head(a.lv, bh, a.H);
+    const char *Kg = a.k + a_head_kv(a.lk, bh, a.H, a.G);
+    const char *Vg = a.v + a_head_kv(a.lv, bh, a.H, a.G);
     char *doslab = smem + FRING * FBUF + wid * QSLAB; // this wave's dO rows, same swizzled image as a K tile (B operand of dP^T)
     int ko[KS], vo[DB][2];
 #pragma unroll
@@ -925,7 +933,7 @@ __global__ __launch_bounds__(FNT, 2) void attn_bwd_dq_ds_kernel(const AttnArgs a
     const int nwx = a.persist ? nxb / (2 * a.persist) : nxb;
     a_block_map(nwx, a.nbh, a.xcd_map, xb0, bh);
     bh += a.bh0;
-    const char *Kg = a.k + a_head(a.lk, bh, a.H);
+    const char *Kg = a.k + a_head_kv(a.lk, bh, a.H, a.G);
     char *slab = smem + DQ_RING * FTILE + wid * DQ_RING * DQ_SLAB;
     int vo[DB][2];
 #pragma unroll
@@ -1258,6 +1266,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_v4_kernel(const AttnArgs a) 
     bh += a.bh0;
     const char *Qg = a.q + a_head(a.lq, bh, a.H);
     const char *dOg = a.d_o + a_head(a.ldo, bh, a.H);
+    const char *Kh = a.k + a_head_kv(a.lk, bh, a.H, a.G), *Vh = a.v + a_head_kv(a.lv, bh, a.H, a.G);
 #pragma nounroll
   for (int pass = 0; pass < (a.persist ? 2 * a.persist : 1); ++pass) {
     const int xp = xb0 + (pass >> 1) * nwx;
@@ -1270,8 +1279,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_v4_kernel(const AttnArgs a) 
     frag_t kf[8], vf[8]; // this wave's 32 keys: B operands of S = Q K^T and dP = dO V^T
     const float c = a.scale * kLog2e;
     {
-        const char *Kg = a.k + a_head(a.lk, bh, a.H) + n * a.lk.sr;
-        const char *Vg = a.v + a_head(a.lv, bh, a.H) + n * a.lv.sr;
+        const char *Kg = Kh + n * a.lk.sr;
+        const char *Vg = Vh + n * a.lv.sr;
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) {
             kf[kk] = *(const frag_t *)(Kg + (kk * 16 + 8 * hl) * 2);
@@ -1795,7 +1804,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_w4_kernel(const AttnArgs a) 
     a_block_map(nwx, a.nbh, a.xcd_map, xb0, bh, vwg);
     bh += a.bh0;
     const char *qp = a.q + a_head(a.lq, bh, a.H), *dop = a.d_o + a_head(a.ldo, bh, a.H);
-    const char *kh = a.k + a_head(a.lk, bh, a.H), *vh = a.v + a_head(a.lv, bh, a.H);
+    const char *kh = a.k + a_head_kv(a.lk, bh, a.H, a.G), *vh = a.v + a_head_kv(a.lv, bh, a.H, a.G);
     char *dkh = a.dk + a_head(a.ldk, bh, a.H), *dvh = a.dv + a_head(a.ldv, bh, a.H);
     const float *cp = a.nlse + bh * a.Sqc;
 #pragma nounroll
@@ -1879,8 +1888,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_mfma_kernel(const AttnArg
     const int nxb = (int)((a.Sq + XQ - 1) / XQ);
     const int nwx = a.persist ? nxb / (2 * a.persist) : nxb; // a.persist: a block and its causal mirror per workgroup (see attn_fwd_v3_kernel)
     a_block_map(nwx, a.nbh, a.xcd_map, xb0, bh);
-    const float *Kg = (const float *)a.k + bh * a.Skv * D;
-    const float *Vg = (const float *)a.v + bh * a.Skv * D;
+    const int64_t kvh = a_kv_index(bh, a.H, a.G);
+    const float *Kg = (const float *)a.k + kvh * a.Skv * D;
+    const float *Vg = (const float *)a.v + kvh * a.Skv * D;
   for (int pass = 0; pass < (a.persist ? 2 * a.persist : 1); ++pass) {
     const int xp = xb0 + (pass >> 1) * nwx;
     const int xb = (pass & 1) ? nxb - 1 - xp : xp;
@@ -2048,8 +2058,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_mfma_kernel(const AttnArg
     const int nxb = (int)((a.Sq + XQ - 1) / XQ);
     const int nwx = a.persist ? nxb / (2 * a.persist) : nxb;
     a_block_map(nwx, a.nbh, a.xcd_map, xb0, bh);
-    const float *Kg = (const float *)a.k + bh * a.Skv * D;
-    const float *Vg = (const float *)a.v + bh * a.Skv * D;
+    const int64_t kvh = a_kv_index(bh, a.H, a.G);
+    const float *Kg = (const float *)a.k + kvh * a.Skv * D;
+    const float *Vg = (const float *)a.v + kvh * a.Skv * D;
     const float c = a.scale * kLog2e;
 #pragma nounroll
   for (int pass = 0; pass < (a.persist ? 2 * a.persist : 1); ++pass) {
@@ -2162,6 +2173,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_mfma_kernel(const AttnAr
     a_block_map(nwx, a.nbh, a.xcd_map, xb0, bh);
     const float *Qg = (const float *)a.q + bh * a.Sq * D;
     const float *Og = (const float *)a.d_o + bh * a.Sq * D;
+    const int64_t kvh = a_kv_index(bh, a.H, a.G);
     const float c = a.scale * kLog2e;
 #pragma nounroll
   for (int pass = 0; pass < (a.persist ? 2 * a.persist : 1); ++pass) {
@@ -2171,8 +2183,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_mfma_kernel(const AttnAr
     const bool active = kw < a.Skv;
     float kreg[HD], vreg[HD];
     if (active) {
-        const float4 *Kp = (const float4 *)((const float *)a.k + (bh * a.Skv + n) * D + hl * HD);
-        const float4 *Vp = (const float4 *)((const float *)a.v + (bh * a.Skv + n) * D + hl * HD);
+        const float4 *Kp = (const float4 *)((const float *)a.k + (kvh * a.Skv + n) * D + hl * HD);
+        const float4 *Vp = (const float4 *)((const float *)a.v + (kvh * a.Skv + n) * D + hl * HD);
 #pragma unroll
         for (int j = 0; j < HD / 4; ++j) {
             const float4 v = Kp[j], w = Vp[j];
@@ -2291,8 +2303,9 @@ __global__ __launch_bounds__(256) void attn_fwd_generic_kernel(const AttnArgs a)
     float *al = Ps + GQ * (GK + 1);  // [GQ] rescale factor of the current tile
     const int64_t bh = blockIdx.y, q0 = (int64_t)blockIdx.x * GQ;
     const T *Qg = (const T *)a.q + bh * a.Sq * D;
-    const T *Kg = (const T *)a.k + bh * a.Skv * D;
-    const T *Vg = (const T *)a.v + bh * a.Skv * D;
+    const int64_t kvh = a_kv_index(bh, a.H, a.G);
+    const T *Kg = (const T *)a.k + kvh * a.Skv * D;
+    const T *Vg = (const T *)a.v + kvh * a.Skv * D;
     const int t = threadIdx.x;
 
     for (int i = t; i < GQ * D; i += 256) {
@@ -2403,7 +2416,8 @@ __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(const AttnArgs a)
     float *cd = cl + GK;              // per-col delta (MODE 1) [GK]
     const int64_t bh = blockIdx.y, r0 = (int64_t)blockIdx.x * GQ;
     const T *Qg = (const T *)a.q + bh * a.Sq * D, *dOg = (const T *)a.d_o + bh * a.Sq * D;
-    const T *Kg = (const T *)a.k + bh * a.Skv * D, *Vg = (const T *)a.v + bh * a.Skv * D;
+    const int64_t kvh = a_kv_index(bh, a.H, a.G);
+    const T *Kg = (const T *)a.k + kvh * a.Skv * D, *Vg = (const T *)a.v + kvh * a.Skv * D;
     const float *lse = a.lse_r + bh * a.Sq, *dlt = a.delta + bh * a.Sq;
     const int64_t nrow = MODE == 0 ? a.Sq : a.Skv, ncol = MODE == 0 ? a.Skv : a.Sq;
     const T *Rqg = MODE == 0 ? Qg : Kg, *Rdg = MODE == 0 ? dOg : Vg;
@@ -2499,6 +2513,99 @@ __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(const AttnArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// backward, grouped-query attention (G = H / Hkv > 1): the dK/dV kernels run unchanged over the B H query pairs and write per-query-head
+// partials into the workspace (contiguous [B H, Skv, D] of the dtype). dK of K/V head kv = b Hkv + j is the dtype rounding of the f32
+// sum, ascending g from the g = 0 term, of the partial rows of pairs kv G + g (= b H + j G + g); dV likewise; both in one launch.
+// Memory-bound: reads 2 B H Skv D, writes 2 B Hkv Skv D elements. A row's pieces (V elements: 16 bytes, or one element on the scalar path)
+// lie on 2^lg consecutive lanes (a row of more than 64 pieces walks them in steps of 64); R rows per lane, 2 R loads in flight per g.
+// Rows beyond Skv do not exist in the row numbering, so they are never touched.
+// ------------------------------------------------------------------------------------------
+template <typename T, int V>
+__device__ __forceinline__ void gs_unpack(const typename std::conditional<V == 1, T, uint4>::type &w, float *f) {
+    if constexpr (V == 1) {
+        f[0] = t_load<T>(&w);
+    } else {
+        const uint32_t u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (std::is_same<T, float>::value) {
+                f[e] = __uint_as_float(u[e]);
+            } else if constexpr (std::is_same<T, bf16_t>::value) {
+                f[2 * e] = __uint_as_float(u[e] << 16);
+                f[2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u);
+            } else {
+                f[2 * e] = f16_to_f32(f16_t{(uint16_t)(u[e] & 0xffff)});
+                f[2 * e + 1] = f16_to_f32(f16_t{(uint16_t)(u[e] >> 16)});
+            }
+        }
+    }
+}
+template <typename T, int V>
+__device__ __forceinline__ void gs_write(char *p, const float *f) {
+    if constexpr (V == 1) {
+        t_store<T>((T *)p, f[0]);
+    } else {
+        uint32_t u[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (std::is_same<T, float>::value) u[e] = __float_as_uint(f[e]);
+            else if constexpr (std::is_same<T, bf16_t>::value) u[e] = (uint32_t)f32_to_bf16(f[2 * e]).x | ((uint32_t)f32_to_bf16(f[2 * e + 1]).x << 16);
+            else u[e] = (uint32_t)f32_to_f16(f[2 * e]).x | ((uint32_t)f32_to_f16(f[2 * e + 1]).x << 16);
+        }
+        *(uint4 *)p = uint4{u[0], u[1], u[2], u[3]};
+    }
+}
+template <typename T, int V, int R>
+__global__ __launch_bounds__(256) void attn_dkv_group_sum_kernel(const char *pk, const char *pv, char *dk, char *dv, AttnArgs::Lay ldk, AttnArgs::Lay ldv,
+                                                                 int64_t nrows, int64_t Skv, int64_t Hkv, int G, int nparts, int lg) {
+    using W = typename std::conditional<V == 1, T, uint4>::type; // one piece as loaded
+    constexpr int PB = V * (int)sizeof(T);                       // bytes of a piece
+    const int64_t rpb = 256 >> lg;                               // rows per step i of a block
+    const int64_t row0 = (int64_t)blockIdx.x * rpb * R + (threadIdx.x >> lg);
+    const int64_t prow = (int64_t)nparts * PB, gstep = Skv * prow; // a partial row's bytes; from one query head's partial row to the next one's
+    const char *pkr[R], *pvr[R];
+    char *dkr[R], *dvr[R];
+    bool live[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const int64_t row = row0 + rpb * i;
+        live[i] = row < nrows;
+        const int64_t kv = live[i] ? row / Skv : 0, n = live[i] ? row - kv * Skv : 0, b = kv / Hkv, j = kv - b * Hkv;
+        pkr[i] = pk + (kv * G * Skv + n) * prow;
+        pvr[i] = pv + (kv * G * Skv + n) * prow;
+        dkr[i] = dk + b * ldk.sb + j * ldk.sh + n * ldk.sr;
+        dvr[i] = dv + b * ldv.sb + j * ldv.sh + n * ldv.sr;
+    }
+    for (int c = threadIdx.x & ((1 << lg) - 1); c < nparts; c += 1 << lg) {
+        const int64_t off = (int64_t)c * PB;
+        float sk[R][V], sv[R][V];
+        W wk[R] = {}, wv[R] = {};
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (live[i]) { wk[i] = *(const W *)(pkr[i] + off); wv[i] = *(const W *)(pvr[i] + off); }
+#pragma unroll
+        for (int i = 0; i < R; ++i) { gs_unpack<T, V>(wk[i], sk[i]); gs_unpack<T, V>(wv[i], sv[i]); }
+        for (int g = 1; g < G; ++g) {
+            const int64_t go = g * gstep + off;
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+                if (live[i]) { wk[i] = *(const W *)(pkr[i] + go); wv[i] = *(const W *)(pvr[i] + go); }
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                float fk[V], fv[V];
+                gs_unpack<T, V>(wk[i], fk);
+                gs_unpack<T, V>(wv[i], fv);
+#pragma unroll
+                for (int e = 0; e < V; ++e) { sk[i][e] += fk[e]; sv[i][e] += fv[e]; }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (live[i]) { gs_write<T, V>(dkr[i] + off, sk[i]); gs_write<T, V>(dvr[i] + off, sv[i]); }
+    }
+}
+
 static bool mfma_ok(int dtype, int64_t Sq, int64_t Skv, int64_t D) {
     return (dtype == KF_BF16 || dtype == KF_F16) && (D == AD || D == 64) && Sq % 128 == 0 && Skv % 128 == 0 && Sq > 0 && Skv > 0;
 }
@@ -2579,10 +2686,12 @@ static bool lay_from(const kf_attn_layout *l, int es, AttnArgs::Lay &out) {
 
 // The AttnArgs fields the forward and the backward share. nlay layouts in the order q, k, v, o (forward: 4) and dO, dQ, dK, dV
 // (backward: 8): the caller's `lays`, or contiguous [B, H, S, D] tensors when it has none.
-static int attn_args(AttnArgs &a, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const AttnArgs::Lay *lays, int nlay) {
+static int attn_args(AttnArgs &a, int64_t B, int64_t H, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const AttnArgs::Lay *lays,
+                     int nlay) {
     memset(&a, 0, sizeof(a));
     KF_REQUIRE(scale > 0.f && scale < INFINITY, KF_ERR_INVALID, "attention: the softmax scale must be positive and finite");
     a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.D = D;
+    a.G = (int)(H / Hkv);
     a.nbh = (int)(B * H);
     a.scale = scale;
     a.scale_log2e = scale * kLog2e;
@@ -2596,12 +2705,14 @@ static int attn_args(AttnArgs &a, int64_t B, int64_t H, int64_t Sq, int64_t Skv,
     AttnArgs::Lay *const out[8] = {&a.lq, &a.lk, &a.lv, &a.lo, &a.ldo, &a.ldq, &a.ldk, &a.ldv};
     for (int i = 0; i < nlay; ++i) {
         const bool key_rows = i == 1 || i == 2 || i >= 6; // k, v, dK, dV: Skv rows
-        *out[i] = lays ? lays[i] : lay_contig(H, key_rows ? Skv : Sq, D, 2);
+        const bool kv_heads = i == 1 || i == 2;          // k, v: Hkv heads (dK, dV of the kernels: one per query head, see attn_bwd_kernels)
+        *out[i] = lays ? lays[i] : lay_contig(kv_heads ? Hkv : H, key_rows ? Skv : Sq, D, 2);
     }
     return KF_OK;
 }
 
-static int attn_fwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
+// Hkv: K/V heads (grouped-query attention: query head h of a batch reads K/V head h / (H / Hkv); Hkv = H: multi-head attention)
+static int attn_fwd_impl(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
                          const void *v, void *o, float *lse, const AttnArgs::Lay *lays, void *stream) {
     int rc = check_common("kf_attn_fwd", dtype, B, H, Sq, Skv, D);
     if (rc != KF_OK) return rc;
@@ -2609,7 +2720,7 @@ static int attn_fwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Sk
     KF_REQUIRE(Skv > 0, KF_ERR_INVALID, "kf_attn_fwd: Skv must be positive");
     KF_REQUIRE(q && k && v && o, KF_ERR_INVALID, "kf_attn_fwd: null operand");
     AttnArgs a;
-    if ((rc = attn_args(a, B, H, Sq, Skv, D, scale, lays, 4)) != KF_OK) return rc;
+    if ((rc = attn_args(a, B, H, Hkv, Sq, Skv, D, scale, lays, 4)) != KF_OK) return rc;
     a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.out = (char *)o; a.lse = lse;
     a.defer = knob(KNOB_ATTN_NO_DEFER) ? -INFINITY : kDeferMax; // A/B switch: rescale O at every tile
     hipStream_t st = as_stream(stream);
@@ -2654,19 +2765,25 @@ extern "C" int kf_attn_fwd(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t 
 
 extern "C" int kf_attn_fwd_scaled(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
                                   const void *k, const void *v, void *o, float *lse, void *stream) {
-    return attn_fwd_impl(dtype, B, H, Sq, Skv, D, scale, q, k, v, o, lse, nullptr, stream);
+    return attn_fwd_impl(dtype, B, H, H, Sq, Skv, D, scale, q, k, v, o, lse, nullptr, stream);
 }
 
-extern "C" int kf_attn_fwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
-                                   const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
-                                   void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+static int attn_fwd_strided_impl(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
+                                 const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
+                                 void *o, const kf_attn_layout *lo, float *lse, void *stream) {
     KF_REQUIRE(mfma16_ok(dtype, Sq, Skv, D), KF_ERR_UNSUPPORTED,
                "kf_attn_fwd_strided: strided layouts are served by the 16-bit matrix-core kernels only (D = 64 or 128; Skv >= Sq, or Sq, Skv multiples of 128)");
     AttnArgs::Lay lays[4];
     KF_REQUIRE(lay_from(lq, 2, lays[0]) && lay_from(lk, 2, lays[1]) && lay_from(lv, 2, lays[2]) && lay_from(lo, 2, lays[3]), KF_ERR_INVALID,
                "kf_attn_fwd_strided: strides must be non-negative multiples of 8 elements");
     KF_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0, KF_ERR_INVALID, "kf_attn_fwd_strided: operands must be 16-byte aligned");
-    return attn_fwd_impl(dtype, B, H, Sq, Skv, D, scale, q, k, v, o, lse, lays, stream);
+    return attn_fwd_impl(dtype, B, H, Hkv, Sq, Skv, D, scale, q, k, v, o, lse, lays, stream);
+}
+
+extern "C" int kf_attn_fwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
+                                   const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
+                                   void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+    return attn_fwd_strided_impl(dtype, B, H, H, Sq, Skv, D, scale, q, lq, k, lk, v, lv, o, lo, lse, stream);
 }
 
 extern "C" int kf_attn_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D,
@@ -2683,19 +2800,53 @@ extern "C" int kf_attn_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int6
     return KF_OK;
 }
 
-static int attn_bwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
-                         const void *v, const void *o, const float *lse, const void *d_o, void *dq, void *dk, void *dv, const AttnArgs::Lay *lays,
-                         void *workspace, size_t workspace_bytes, void *stream) {
+// Grouped-query attention (Hkv < H): the dK/dV kernels write one partial dK and dV per QUERY head into the workspace, right behind the
+// statistics: two arrays of B H Skv D elements of the dtype, each rounded up to 256 bytes (attn_dkv_group_sum adds each group up)
+static size_t gqa_part_bytes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Skv, int64_t D) {
+    return H == Hkv ? 0 : a_align((size_t)B * H * Skv * D * (dtype == KF_F32 ? 4 : 2));
+}
+
+// dk, dv of K/V head j from the partials of query heads j G .. j G + G - 1 (ldk, ldv: the caller's byte layouts)
+static int attn_dkv_group_sum(int dtype, int64_t B, int64_t Hkv, int64_t Skv, int64_t D, int G, const char *pk, const char *pv, void *dk, void *dv,
+                              AttnArgs::Lay ldk, AttnArgs::Lay ldv, hipStream_t st) {
+    constexpr int R = 4; // rows per lane: 8 16-byte loads in flight per query head of the group
+    const int es = dtype == KF_F32 ? 4 : 2, vec = 16 / es;
+    const bool wide = D % vec == 0 && (((uintptr_t)dk | (uintptr_t)dv) % 16 == 0) &&
+                      ((ldk.sb | ldk.sh | ldk.sr | ldv.sb | ldv.sh | ldv.sr) % 16 == 0); // 16-byte pieces everywhere; else the scalar path
+    const int nparts = (int)(wide ? D / vec : D);
+    int lg = 0;
+    while ((1 << lg) < nparts && lg < 6) ++lg;
+    const int64_t nrows = B * Hkv * Skv, rows_per_block = (int64_t)(256 >> lg) * R;
+    const unsigned grid = (unsigned)((nrows + rows_per_block - 1) / rows_per_block);
+    KF_PROF("attn_bwd_dkv_group_sum", st);
+    auto go = [&](auto t) {
+        using T = decltype(t);
+        return wide ? launch(attn_dkv_group_sum_kernel<T, 16 / sizeof(T), R>, grid, 256, 0, st, pk, pv, (char *)dk, (char *)dv, ldk, ldv, nrows, Skv, Hkv, G,
+                             nparts, lg)
+                    : launch(attn_dkv_group_sum_kernel<T, 1, R>, grid, 256, 0, st, pk, pv, (char *)dk, (char *)dv, ldk, ldv, nrows, Skv, Hkv, G, nparts, lg);
+    };
+    return dtype == KF_F32 ? go(float{}) : dtype == KF_BF16 ? go(bf16_t{}) : go(f16_t{});
+}
+
+static int attn_bwd_kernels(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
+                            const void *v, const void *o, const float *lse, const void *d_o, void *dq, void *dk, void *dv, const AttnArgs::Lay *lays,
+                            void *workspace, size_t workspace_bytes, void *stream) {
     int rc = check_common("kf_attn_bwd", dtype, B, H, Sq, Skv, D);
     if (rc != KF_OK) return rc;
     if (B * H == 0 || Sq == 0 || Skv == 0) return KF_OK;
     KF_REQUIRE(q && k && v && o && lse && d_o && dq && dk && dv, KF_ERR_INVALID, "kf_attn_bwd: null operand");
-    const size_t need = bwd_stats_bytes(B * H, Sq); // the minimum; what lies beyond it holds dS (see ds_group)
+    const size_t stats = bwd_stats_bytes(B * H, Sq), part = gqa_part_bytes(dtype, B, H, Hkv, Skv, D);
+    const size_t need = stats + 2 * part; // the minimum; what lies beyond it holds dS (see ds_group)
     KF_REQUIRE(workspace && workspace_bytes >= need, KF_ERR_WORKSPACE, "kf_attn_bwd: workspace of at least %zu bytes required, got %zu", need, workspace_bytes);
     AttnArgs a;
-    if ((rc = attn_args(a, B, H, Sq, Skv, D, scale, lays, 8)) != KF_OK) return rc;
+    if ((rc = attn_args(a, B, H, Hkv, Sq, Skv, D, scale, lays, 8)) != KF_OK) return rc;
     a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.o = (const char *)o; a.d_o = (const char *)d_o;
     a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv;
+    if (part) { // grouped-query attention: the dK/dV kernels write the per-query-head partials (contiguous [B H, Skv, D]) instead of dk, dv
+        a.dk = (char *)workspace + stats;
+        a.dv = a.dk + part;
+        a.ldk = a.ldv = lay_contig(H, Skv, D, 2);
+    }
     a.lse_r = lse; a.delta = (float *)workspace;
     a.Sqc = stat_rows(Sq);
     a.nlse = (float *)((char *)workspace + a_align((size_t)B * H * Sq * sizeof(float)));
@@ -2813,6 +2964,19 @@ static int attn_bwd_impl(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Sk
     return dtype == KF_F32 ? generic(float{}) : bf ? generic(bf16_t{}) : generic(f16_t{});
 }
 
+// the kernels, then (Hkv < H) one group sum of the partials into the caller's dk, dv
+static int attn_bwd_impl(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q, const void *k,
+                         const void *v, const void *o, const float *lse, const void *d_o, void *dq, void *dk, void *dv, const AttnArgs::Lay *lays,
+                         void *workspace, size_t workspace_bytes, void *stream) {
+    const int rc = attn_bwd_kernels(dtype, B, H, Hkv, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, lays, workspace, workspace_bytes, stream);
+    if (rc != KF_OK || Hkv == H || B * H == 0 || Sq == 0 || Skv == 0) return rc;
+    const int es = dtype == KF_F32 ? 4 : 2;
+    const size_t part = gqa_part_bytes(dtype, B, H, Hkv, Skv, D);
+    const char *pk = (const char *)workspace + bwd_stats_bytes(B * H, Sq), *pv = pk + part;
+    return attn_dkv_group_sum(dtype, B, Hkv, Skv, D, (int)(H / Hkv), pk, pv, dk, dv, lays ? lays[6] : lay_contig(Hkv, Skv, D, es),
+                              lays ? lays[7] : lay_contig(Hkv, Skv, D, es), as_stream(stream));
+}
+
 extern "C" int kf_attn_bwd(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, const void *q,
                            const void *k, const void *v, const void *o, const float *lse, const void *d_o, void *dq,
                            void *dk, void *dv, void *workspace, size_t workspace_bytes, void *stream) {
@@ -2823,14 +2987,14 @@ extern "C" int kf_attn_bwd(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t 
 extern "C" int kf_attn_bwd_scaled(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
                                   const void *k, const void *v, const void *o, const float *lse, const void *d_o, void *dq,
                                   void *dk, void *dv, void *workspace, size_t workspace_bytes, void *stream) {
-    return attn_bwd_impl(dtype, B, H, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, nullptr, workspace, workspace_bytes, stream);
+    return attn_bwd_impl(dtype, B, H, H, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, nullptr, workspace, workspace_bytes, stream);
 }
 
-extern "C" int kf_attn_bwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
-                                   const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
-                                   const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
-                                   const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
-                                   void *workspace, size_t workspace_bytes, void *stream) {
+static int attn_bwd_strided_impl(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
+                                 const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
+                                 const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
+                                 const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
     KF_REQUIRE(mfma16_ok(dtype, Sq, Skv, D), KF_ERR_UNSUPPORTED,
                "kf_attn_bwd_strided: strided layouts are served by the 16-bit matrix-core kernels only (D = 64 or 128; Skv >= Sq, or Sq, Skv multiples of 128)");
     AttnArgs::Lay lays[8];
@@ -2839,7 +3003,77 @@ extern "C" int kf_attn_bwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, 
         KF_REQUIRE(lay_from(in[i], 2, lays[i]), KF_ERR_INVALID, "kf_attn_bwd_strided: strides must be non-negative multiples of 8 elements");
     KF_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16 == 0,
                KF_ERR_INVALID, "kf_attn_bwd_strided: operands must be 16-byte aligned");
-    return attn_bwd_impl(dtype, B, H, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, lays, workspace, workspace_bytes, stream);
+    return attn_bwd_impl(dtype, B, H, Hkv, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, lays, workspace, workspace_bytes, stream);
+}
+
+extern "C" int kf_attn_bwd_strided(int dtype, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
+                                   const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
+                                   const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
+                                   const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    return attn_bwd_strided_impl(dtype, B, H, H, Sq, Skv, D, scale, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq, dk, ldk, dv, ldv, workspace,
+                                 workspace_bytes, stream);
+}
+
+// ---- grouped-query attention (include/kfunca_hip.h: kf_attn_*_gqa) ----
+// Hq query heads share Hkv K/V heads: Hkv >= 1 divides Hq. The layouts are all NULL (contiguous tensors: every tier) or all given (the
+// _strided rules); Hkv = Hq takes exactly the code path of kf_attn_*_scaled / kf_attn_*_strided.
+static int gqa_args(const char *who, int64_t Hq, int64_t Hkv, const kf_attn_layout *const *lay, int nlay, bool &strided) {
+    KF_REQUIRE(Hkv >= 1 && Hkv <= Hq && Hq % Hkv == 0, KF_ERR_INVALID, "%s: Hkv %lld must divide Hq %lld (1 <= Hkv <= Hq)", who, (long long)Hkv,
+               (long long)Hq);
+    int given = 0;
+    for (int i = 0; i < nlay; ++i) given += lay[i] != nullptr;
+    KF_REQUIRE(given == 0 || given == nlay, KF_ERR_INVALID, "%s: the layouts are all NULL (contiguous tensors) or all given, not %d of %d", who, given, nlay);
+    strided = given == nlay;
+    return KF_OK;
+}
+
+extern "C" int kf_attn_fwd_gqa(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
+                               const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, void *o,
+                               const kf_attn_layout *lo, float *lse, void *stream) {
+    int rc = check_common("kf_attn_fwd_gqa", dtype, B, Hq, Sq, Skv, D);
+    if (rc != KF_OK) return rc;
+    const kf_attn_layout *lay[4] = {lq, lk, lv, lo};
+    bool strided = false;
+    if ((rc = gqa_args("kf_attn_fwd_gqa", Hq, Hkv, lay, 4, strided)) != KF_OK) return rc;
+    KF_REQUIRE(q && k && v && o, KF_ERR_INVALID, "kf_attn_fwd_gqa: null operand");
+    if (strided) return attn_fwd_strided_impl(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, lq, k, lk, v, lv, o, lo, lse, stream);
+    return attn_fwd_impl(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, k, v, o, lse, nullptr, stream);
+}
+
+extern "C" int kf_attn_bwd_gqa_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D,
+                                               size_t *recommended, size_t *minimum) {
+    KF_REQUIRE(recommended, KF_ERR_INVALID, "kf_attn_bwd_gqa_workspace_bytes: null out pointer");
+    int rc = check_common("kf_attn_bwd_gqa_workspace_bytes", dtype, B, Hq, Sq, Skv, D);
+    if (rc != KF_OK) return rc;
+    bool strided = false;
+    if ((rc = gqa_args("kf_attn_bwd_gqa_workspace_bytes", Hq, Hkv, nullptr, 0, strided)) != KF_OK) return rc;
+    size_t mha = 0;
+    if ((rc = kf_attn_bwd_workspace_bytes(dtype, B, Hq, Sq, Skv, D, &mha)) != KF_OK) return rc;
+    const size_t parts = 2 * gqa_part_bytes(dtype, B, Hq, Hkv, Skv, D);
+    *recommended = mha + parts; // the multi-head call's statistics + dS for B Hq pairs, and the partials
+    if (minimum) *minimum = bwd_stats_bytes(B * Hq, Sq) + parts;
+    return KF_OK;
+}
+
+extern "C" int kf_attn_bwd_gqa(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const void *q,
+                               const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, const void *o,
+                               const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq,
+                               void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+    int rc = check_common("kf_attn_bwd_gqa", dtype, B, Hq, Sq, Skv, D);
+    if (rc != KF_OK) return rc;
+    const kf_attn_layout *lay[8] = {lq, lk, lv, lo, ldo, ldq, ldk, ldv};
+    bool strided = false;
+    if ((rc = gqa_args("kf_attn_bwd_gqa", Hq, Hkv, lay, 8, strided)) != KF_OK) return rc;
+    KF_REQUIRE(q && k && v && o && lse && d_o && dq && dk && dv, KF_ERR_INVALID, "kf_attn_bwd_gqa: null operand");
+    const size_t minimum = bwd_stats_bytes(B * Hq, Sq) + 2 * gqa_part_bytes(dtype, B, Hq, Hkv, Skv, D);
+    KF_REQUIRE((workspace || minimum == 0) && workspace_bytes >= minimum, KF_ERR_INVALID,
+               "kf_attn_bwd_gqa: workspace of at least %zu bytes required (kf_attn_bwd_gqa_workspace_bytes), got %zu", minimum, workspace_bytes);
+    if (strided)
+        return attn_bwd_strided_impl(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq, dk, ldk, dv, ldv, workspace,
+                                     workspace_bytes, stream);
+    return attn_bwd_impl(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, nullptr, workspace, workspace_bytes, stream);
 }
 
 #ifdef KF_ATTN_TIMELINE

@@ -49,7 +49,8 @@ EXPORTS = [
     "kf_adamw_workspace_bytes", "kf_adamw_step",
     "kf_rope", "kf_rope_table",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
-    "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
+    "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
+    "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
 ]
 
 
@@ -182,6 +183,10 @@ def lib():
         _lib.kf_attn_fwd_strided.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
         _lib.kf_attn_bwd_strided.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp, vp, lp, vp, lp,
                                              vp, lp, vp, sz, vp]
+        _lib.kf_attn_fwd_gqa.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
+        _lib.kf_attn_bwd_gqa_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.POINTER(sz), C.POINTER(sz)]
+        _lib.kf_attn_bwd_gqa.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp, vp, lp, vp, lp,
+                                         vp, lp, vp, sz, vp]
         _lib.kf_rope.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, vp, vp, lp, vp, lp, vp]
         _lib.kf_rope_table.argtypes = [C.c_double, i64, i64, vp, vp, vp]
         _lib.kf_comm_unique_id.argtypes = [C.c_char_p]
@@ -594,6 +599,33 @@ def attn_bwd_strided(dtype, B, H, Sq, Skv, D, scale, q, lq, k, lk, v, lv, o, lo,
     L = [AttnLayout(*t) for t in (lq, lk, lv, lo, ldo, ldq, ldk, ldv)]
     check(lib().kf_attn_bwd_strided(dtype, B, H, Sq, Skv, D, scale, q, C.byref(L[0]), k, C.byref(L[1]), v, C.byref(L[2]), o, C.byref(L[3]), lse,
                                     d_o, C.byref(L[4]), dq, C.byref(L[5]), dk, C.byref(L[6]), dv, C.byref(L[7]), workspace, workspace_bytes, stream))
+
+
+def _gqa_layouts(lays, n):
+    """None, or n (batch, head, row) element-stride triples -> n kf_attn_layout pointers (NULL for None, for every operand)"""
+    if lays is None:
+        return [None] * n
+    return [None if t is None else C.byref(AttnLayout(*t)) for t in lays]
+
+
+def attn_fwd_gqa(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, k, v, o, lse=None, layouts=None, stream=None):
+    """Grouped-query attention forward (kf_attn_fwd_gqa). layouts: None (contiguous tensors) or (lq, lk, lv, lo) stride triples."""
+    L = _gqa_layouts(layouts, 4)
+    check(lib().kf_attn_fwd_gqa(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, L[0], k, L[1], v, L[2], o, L[3], lse, stream))
+
+
+def attn_bwd_gqa_workspace_bytes(dtype, B, Hq, Hkv, Sq, Skv, D):
+    """(recommended, minimum) bytes of the GQA backward's workspace."""
+    rec, mn = C.c_size_t(0), C.c_size_t(0)
+    check(lib().kf_attn_bwd_gqa_workspace_bytes(dtype, B, Hq, Hkv, Sq, Skv, D, C.byref(rec), C.byref(mn)))
+    return rec.value, mn.value
+
+
+def attn_bwd_gqa(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, workspace, workspace_bytes, layouts=None, stream=None):
+    """Grouped-query attention backward (kf_attn_bwd_gqa). layouts: None or (lq, lk, lv, lo, ldo, ldq, ldk, ldv) stride triples."""
+    L = _gqa_layouts(layouts, 8)
+    check(lib().kf_attn_bwd_gqa(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, L[0], k, L[1], v, L[2], o, L[3], lse, d_o, L[4], dq, L[5], dk, L[6],
+                                dv, L[7], workspace, workspace_bytes, stream))
 
 
 def rope(dtype, B, H, S, D, x, lx, y=None, ly=None, cos=None, sin=None, table_rows=None, rotary_dim=None, h_rot=None, positions=None,
