@@ -181,6 +181,9 @@ enum {
  * reduced dims are the ones where the OUTPUT stride is 0 and shape > 1.
  * The caller supplies scratch of at least kf_reduce_workspace_bytes(desc) bytes (may be 0);
  * it needs no initialisation.
+ * A descriptor with a dim of extent 0 writes nothing, even where the output has elements (a reduced
+ * dim of extent 0): the caller owns the identity (the operator API writes sum 0, floating mean NaN).
+ * The same holds for kf_reduce_moments (the operator API writes NaN to both outputs).
  */
 int kf_reduce_workspace_bytes(const kf_iter_desc *desc, size_t *bytes);
 int kf_reduce(int op, const kf_iter_desc *desc, void *workspace, size_t workspace_bytes, void *stream);

@@ -39,8 +39,19 @@ Tensor &binary_out(int op, Tensor &out, const Tensor &left, const Tensor &right)
     return out;
 }
 
+// A reduction over a dim of extent 0 has outputs but no input elements: the device call writes nothing then, so the identity is
+// written here - PyTorch's values (sum 0, floating mean / variance / invstd NaN). The reference refuses these calls
+// (gpu_reduce_kernel: CHECK_FAIL(iter.numel() > 0)); this host accepts them, so it defines the values.
+bool fill_empty_reduction(TensorIterator &iter, double value) {
+    if (iter.numel() != 0) return false;
+    for (int i = 0; i < iter.noutputs(); ++i)
+        if (iter.outputs(i).numel() > 0) fill_(iter.outputs(i), any_t{value});
+    return true;
+}
+
 void run_reduce(TensorIterator &iter, int op) {
-    if (iter.num_output_elements() == 0) return;
+    const double empty_value = op == KF_RED_MEAN && is_floating_type(iter.dtype(0)) ? std::numeric_limits<double>::quiet_NaN() : 0.0;
+    if (fill_empty_reduction(iter, empty_value)) return;
     CHECK_FAIL(iter.can_use_32bit_indexing(), "reduction over more than 2^31 bytes per operand is not supported yet");
     kf_iter_desc d;
     iter.geometry().to_desc(d);
@@ -55,7 +66,7 @@ void run_reduce(TensorIterator &iter, int op) {
 
 // two-output statistics reduction: iterator outputs are (variance-like, mean) as in reduce_ops.cpp:24
 void run_moments(TensorIterator &iter, int mode, double correction, double eps) {
-    if (iter.num_output_elements() == 0) return;
+    if (fill_empty_reduction(iter, std::numeric_limits<double>::quiet_NaN())) return;
     CHECK_FAIL(iter.can_use_32bit_indexing(), "reduction over more than 2^31 bytes per operand is not supported yet");
     kf_iter_desc d;
     iter.geometry().to_desc(d);

@@ -69,3 +69,51 @@ def test_attention_degenerate_extents_c_abi():
     H.device_sync()
     assert np.allclose(o.to_numpy((4,), np.float32), one.ravel())
     assert np.allclose(l.to_numpy((1,), np.float32), (one ** 2).sum() / 2.0)
+
+
+@pytest.mark.parametrize("name", ["f32", "f64", "bf16", "f16", "i32", "bool"])
+def test_reduction_over_an_empty_dim_writes_the_identity(name):
+    """A reduced dim of extent 0 with outputs that have elements: the outputs hold PyTorch's values - sum 0, mean NaN for floating
+    dtypes and 0 for integers (the kernel's integer factor), mean_var and norm_stat NaN in both outputs - not what the caching
+    allocator left in the block. Each call first frees a block of the output's size filled with 7 so a missing write shows."""
+    npdt = {"f32": np.float32, "f64": np.float64, "bf16": np.uint16, "f16": np.float16, "i32": np.int32, "bool": np.bool_}[name]
+    floating = name in ("f32", "f64", "bf16", "f16")
+
+    def tensor(a):
+        return kfunca.from_numpy_bf16(a, 0) if name == "bf16" else kfunca.from_numpy(a, 0)
+
+    def values(t):
+        a = t.numpy()
+        return (a.astype(np.uint32) << 16).view(np.float32) if name == "bf16" else a.astype(np.float64)
+
+    def stale(nbytes):  # leave a freed block of 7s of exactly this size at the head of the cache
+        fill = np.full(nbytes, 7, dtype=np.uint8)
+        t = kfunca.from_numpy(fill, 0)
+        kfunca.synchronize()
+        del t
+
+    for shape in ((0, 3, 5), (3, 0, 5), (3, 5, 0)):
+        dim = shape.index(0)
+        x = tensor(np.zeros(shape, dtype=npdt))
+        out_shape = [s if i != dim else 1 for i, s in enumerate(shape)]
+        nout = int(np.prod(out_shape))
+        stale(nout * np.dtype(npdt).itemsize)
+        s = x.sum(dim)
+        assert s.sizes() == out_shape and not values(s).any(), (shape, values(s))
+        stale(nout * np.dtype(npdt).itemsize)
+        m = values(x.mean(dim))
+        assert (np.isnan(m).all() if floating else not m.any()), (shape, m)
+        if not floating:
+            continue
+        for take_sqrt in (False, True):
+            stale(nout * np.dtype(npdt).itemsize)
+            mean, var = x.mean_var(dim, take_sqrt)
+            assert mean.sizes() == var.sizes() == out_shape
+            assert np.isnan(values(mean)).all() and np.isnan(values(var)).all(), (shape, take_sqrt)
+        stale(nout * 4 if name != "f64" else nout * 8)
+        mean, invstd = x.norm_stat(dim)
+        assert mean.sizes() == invstd.sizes() == out_shape
+        assert np.isnan(mean.numpy()).all() and np.isnan(invstd.numpy()).all(), shape
+    # an empty output stays a no-op: the existing [3, 0].sum(0) -> [1, 0]
+    e = tensor(np.zeros((3, 0), dtype=npdt))
+    assert e.sum(0).sizes() == [1, 0] and e.mean(0).sizes() == [1, 0]
