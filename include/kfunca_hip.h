@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table, kf_attn_fwd_gqa, kf_attn_bwd_gqa_workspace_bytes, kf_attn_bwd_gqa):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
+#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table, kf_attn_fwd_gqa, kf_attn_bwd_gqa_workspace_bytes, kf_attn_bwd_gqa, kf_glu_fwd, kf_glu_bwd, KF_ACT_*):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
 
 /* ---- status ------------------------------------------------------------------------------ */
 enum {
@@ -539,6 +539,37 @@ int kf_rope(int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t h_rot
             const float *cos, const float *sin, int64_t table_rows, const int64_t *positions, const void *x, const kf_attn_layout *lx,
             void *y, const kf_attn_layout *ly, void *stream);
 int kf_rope_table(double base, int64_t rotary_dim, int64_t rows, float *cos, float *sin, void *stream);
+
+/* ---- gated activations (no reference counterpart: the non-linearity of a SwiGLU / GeGLU MLP between its two projections) ---- */
+enum {
+    KF_ACT_SILU = 0,      /* g / (1 + exp(-g))                                                              */
+    KF_ACT_GELU_TANH = 1, /* 0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3))): torch's approximate = 'tanh'  */
+    KF_ACT_GELU_ERF = 2   /* g 0.5 (1 + erf(g / sqrt 2))                                                    */
+};
+/*
+ * gate, up, h, dh, dgate, dup: [rows, F] row-major with leading dimensions in elements, each >= F; one dtype in {KF_F32, KF_BF16,
+ * KF_F16} for all of them. The packed projection [rows, 2F] (columns gate | up: what ONE GEMM against the concatenated weights
+ * writes) is gate = x, up = x + F, ldg = ldu = 2F, and the backward writes one packed gradient the same way: no split, no concat, no
+ * copy on either side.
+ *     forward    h = act(g) u                                   (up == NULL: the ungated h = act(g); ldu is ignored)
+ *     backward   dup = dh act(g),  dgate = dh u act'(g)         (up == NULL needs dup == NULL: dgate = dh act'(g))
+ * evaluated in f32 on the stored values with one rounding per output element; the backward recomputes act from gate and up, the
+ * forward keeps nothing. Every finite input gives a finite result unless the product itself leaves the dtype's range: where exp
+ * would overflow the result is the limit (0, or g u). NaN in gives NaN out; g = +inf gives inf * u; g = -inf gives NaN (-inf * 0,
+ * as torch's x * sigmoid(x) and its GELU do).
+ * Allowed aliases, bitwise equal to the out-of-place call: h == gate or h == up; dgate == gate and / or dup == up; each with the same
+ * leading dimension (the backward then overwrites the projection with its gradient). Anything else must not overlap. Columns F .. ld
+ * of an output row are never written. Any element-aligned base, F and leading dimensions work; 16-byte aligned bases with F and all
+ * leading dimensions multiples of 16 / sizeof(T) take the path with 16-byte loads and stores, and both paths give the same bits.
+ * Row offsets are 64-bit (rows * ld may exceed 2^31). One launch, no workspace, no atomics, no allocation, no synchronisation:
+ * calls can be captured with kf_graph_*; rows == 0 or F == 0 is KF_OK without a launch. Every argument is checked before any device
+ * call: KF_ERR_INVALID (act, dtype, negative extents, a leading dimension < F, null gate / h / dh / dgate, dup without up or up
+ * without dup, a base not aligned to its element, an alias with another leading dimension).
+ */
+int kf_glu_fwd(int act, int dtype, int64_t rows, int64_t F, const void *gate, int64_t ldg, const void *up, int64_t ldu,
+               void *h, int64_t ldh, void *stream);
+int kf_glu_bwd(int act, int dtype, int64_t rows, int64_t F, const void *gate, int64_t ldg, const void *up, int64_t ldu,
+               const void *dh, int64_t lddh, void *dgate, int64_t lddg, void *dup, int64_t lddu, void *stream);
 
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128

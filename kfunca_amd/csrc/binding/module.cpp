@@ -12,6 +12,7 @@
 #include "allocator.h"
 #include "comm.h"
 #include "device_api.h"
+#include "glu.h"
 #include "ops.h"
 #include "optim.h"
 #include "rope.h"
@@ -401,6 +402,19 @@ PYBIND11_MODULE(_C, m) {
     m.def("rope", [](const Tensor &x, const Tensor &cos, const Tensor &sin, py::object positions, bool interleaved) {
         return gpu::rope(x, cos, sin, positions.is_none() ? Tensor() : positions.cast<Tensor>(), interleaved);
     }, py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("positions") = py::none(), py::arg("interleaved") = false);
+    // gated activations (one launch each way; the packed [..., 2F] gate | up projection is read in place): torch's F.gelu argument name
+    auto gelu_kind = [](const std::string &approximate) {
+        CHECK_FAIL(approximate == "none" || approximate == "tanh", approximate, " is not a valid value for approximate ('none' or 'tanh')");
+        return approximate == "tanh" ? KF_ACT_GELU_TANH : KF_ACT_GELU_ERF;
+    };
+    m.def("swiglu", [](const Tensor &gate, py::object up) { return gpu::glu(KF_ACT_SILU, gate, up.is_none() ? Tensor() : up.cast<Tensor>()); },
+          py::arg("gate"), py::arg("up") = py::none());
+    m.def("geglu", [gelu_kind](const Tensor &gate, py::object up, const std::string &approximate) {
+        return gpu::glu(gelu_kind(approximate), gate, up.is_none() ? Tensor() : up.cast<Tensor>());
+    }, py::arg("gate"), py::arg("up") = py::none(), py::arg("approximate") = "none");
+    m.def("silu", [](const Tensor &x) { return gpu::activation(KF_ACT_SILU, x); }, py::arg("x"));
+    m.def("gelu", [gelu_kind](const Tensor &x, const std::string &approximate) { return gpu::activation(gelu_kind(approximate), x); },
+          py::arg("x"), py::arg("approximate") = "none");
     // from_numpy for bfloat16: uint16 bit patterns in, a BFloat16 tensor out (the inverse of to_numpy's uint16 view)
     m.def("from_numpy_bf16", [](py::array array, int device) {
         CHECK_FAIL(array.dtype().kind() == 'u' && array.dtype().itemsize() == 2, "from_numpy_bf16 expects uint16 bit patterns");

@@ -27,6 +27,7 @@ MOM_VAR, MOM_STD, MOM_INVSTD = range(3)
 EPI_NONE, EPI_BIAS_ROW = range(2)
 NORM_RMS, NORM_LAYER = range(2)
 CE_NONE, CE_SUM, CE_MEAN = range(3)
+ACT_SILU, ACT_GELU_TANH, ACT_GELU_ERF = range(3)
 MAX_DIMS, MAX_TENSORS = 12, 8
 KF_OK, KF_ERR_HIP, KF_ERR_INVALID, KF_ERR_UNSUPPORTED, KF_ERR_INDEX_RANGE, KF_ERR_WORKSPACE, KF_ERR_COMM, KF_ERR_OOM = range(8)
 COMM_ID_BYTES = 128
@@ -48,6 +49,7 @@ EXPORTS = [
     "kf_cross_entropy_workspace_bytes", "kf_cross_entropy_fwd", "kf_cross_entropy_bwd",
     "kf_adamw_workspace_bytes", "kf_adamw_step",
     "kf_rope", "kf_rope_table",
+    "kf_glu_fwd", "kf_glu_bwd",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
     "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
@@ -189,6 +191,8 @@ def lib():
                                          vp, lp, vp, sz, vp]
         _lib.kf_rope.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, vp, vp, lp, vp, lp, vp]
         _lib.kf_rope_table.argtypes = [C.c_double, i64, i64, vp, vp, vp]
+        _lib.kf_glu_fwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp]
+        _lib.kf_glu_bwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
         _lib.kf_comm_unique_id.argtypes = [C.c_char_p]
         _lib.kf_comm_init.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int, C.c_int]
         _lib.kf_comm_destroy.argtypes = [vp]
@@ -643,6 +647,18 @@ def rope(dtype, B, H, S, D, x, lx, y=None, ly=None, cos=None, sin=None, table_ro
 def rope_table(base, rotary_dim, rows, cos, sin, stream=None):
     """kf_rope_table: cos / sin = f32 [rows, rotary_dim / 2] device buffers, cos(p base^(-2i/R)) from f64."""
     check(lib().kf_rope_table(float(base), rotary_dim, rows, cos, sin, stream))
+
+
+def glu_fwd(act, dtype, rows, F, gate, ldg, up, ldu, h, ldh, stream=None):
+    """Gated activation forward (kf_glu_fwd): h = act(gate) * up on [rows, F] operands with leading dimensions in elements; up = None is
+    the ungated act(gate). The packed [rows, 2F] projection: gate = x, up = x + F * itemsize, ldg = ldu = 2F."""
+    check(lib().kf_glu_fwd(act, dtype, rows, F, gate, ldg, up, ldu, h, ldh, stream))
+
+
+def glu_bwd(act, dtype, rows, F, gate, ldg, up, ldu, dh, lddh, dgate, lddg, dup=None, lddu=0, stream=None):
+    """Gated activation backward (kf_glu_bwd): dup = dh act(gate), dgate = dh up act'(gate), recomputed from gate and up (up = dup = None:
+    dgate = dh act'(gate)). dgate may be gate and dup may be up (same leading dimension): the projection is overwritten with its gradient."""
+    check(lib().kf_glu_bwd(act, dtype, rows, F, gate, ldg, up, ldu, dh, lddh, dgate, lddg, dup, lddu, stream))
 
 
 def device_sync():
