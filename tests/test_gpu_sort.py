@@ -142,3 +142,43 @@ def test_many_tiles_and_segments():
     for code, shape in ((H.F32, (1, 3_000_000)), (H.I32, (5, 400_003)), (H.F64, (2, 700_001)), (H.U8, (3, 300_000)), (H.BF16, (2, 1_000_000)), (H.I64, (7, 70_000))):
         for desc in (False, True):
             check(draw(rng, shape, code), code, desc)
+
+
+def _extreme_keys(code):
+    """(MIN, MAX, mid values) as bit patterns of the key's width: the keys that sort first and last of all. Integers: the type's limits.
+    Floats: the NaN with every mantissa bit set, sign bit set (first) and clear (last: its ordered key is all ones)."""
+    w = np.dtype(NP_OF[code]).itemsize
+    ut = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[w]
+    if code in (H.F16, H.BF16, H.F32, H.F64):
+        mids = np.array([0.0, 1.0, -1.0, np.inf, -np.inf])
+        mids = O.f32_to_bf16(mids.astype(np.float32)) if code == H.BF16 else mids.astype(NP_OF[code]).view(ut)
+        return ut(~ut(0)), ut(~ut(0)) >> ut(1), mids.astype(ut)
+    ii = np.iinfo(NP_OF[code])
+    mids = np.array([0, 1, ii.max // 2, ii.min // 2 + 1, ii.max - 1, ii.min + 1], dtype=NP_OF[code]).view(ut)
+    return np.array([ii.min], dtype=NP_OF[code]).view(ut)[0], np.array([ii.max], dtype=NP_OF[code]).view(ut)[0], mids
+
+
+@pytest.mark.parametrize("code", [H.I8, H.U8, H.I16, H.I32, H.I64, H.F16, H.BF16, H.F32, H.F64])
+def test_keys_at_the_extremes_of_the_type(code):
+    """A real key EQUAL to a padding key. The register bitonic network pads with ~(U)0 behind position bit 31, the block-local radix sort with
+    KeyBits::all behind the segment's end: ascending, the type's MAX (integers: INT_MAX, 255; floats: +NaN with all mantissa bits set) has
+    exactly that ordered key, descending the type's MIN has. Only the position tie-break / the stability of the passes keeps the real keys in
+    front and in input order. Lengths that leave padding slots in every small path (1, 3, 7, 13, 20, 33, 63: register rows of 2 to 64 slots; 65, 100, 300,
+    511: one segment per wave; 513, 1000, 2000, 4097, 8191: each instantiation of the block-local radix) and the global radix path with a ragged last tile (8193, 20000). Six segments
+    per launch: all MAX, all MIN, and four that are mostly copies of MIN and MAX with a few values between."""
+    lo, hi, mids = _extreme_keys(code)
+    ut = mids.dtype.type
+    rng = np.random.default_rng(900 + code)
+    pool = np.concatenate([[lo, hi], mids]).astype(ut)
+    prob = np.concatenate([[0.44, 0.44], np.full(mids.size, 0.12 / mids.size)])
+    for n in (1, 3, 7, 13, 20, 33, 63, 65, 100, 300, 511, 513, 1000, 2000, 4097, 8191, 8193, 20000):
+        keys = rng.choice(pool, size=(6, n), p=prob).astype(ut)
+        keys[0, :] = hi
+        keys[1, :] = lo
+        keys = keys.view(NP_OF[code])
+        for desc in (False, True):
+            got_k, got_p = H.sort_segments(keys, desc, code=code)
+            want_k, want_p = O.sort_stable(keys, 1, desc, code=code)
+            assert np.array_equal(want_p[:2], np.tile(np.arange(n), (2, 1)))   # all-equal segments: the identity
+            assert np.array_equal(got_p, want_p), (code, n, desc, np.argwhere(got_p != want_p)[:4].tolist())
+            assert np.array_equal(got_k.view(np.uint8), want_k.view(np.uint8)), (code, n, desc)
