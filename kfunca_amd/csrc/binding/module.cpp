@@ -507,6 +507,7 @@ PYBIND11_MODULE(_C, m) {
         .def("half", &Tensor::_half)
         .def("bfloat16", &Tensor::_bfloat16)
         .def("float", &Tensor::_float)
+        .def("double", &Tensor::_double) // extension: the reference converts to half, bfloat16 and float only
         .def("requires_grad", &Tensor::requires_grad)
         .def("set_requires_grad", &Tensor::set_requires_grad)
         .def("backward", &Tensor::backward)

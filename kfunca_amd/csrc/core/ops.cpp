@@ -91,14 +91,33 @@ Tensor &mul_(Tensor &self, const Tensor &other) { return mul_out(self, self, oth
 Tensor &div_(Tensor &self, const Tensor &other) { return div_out(self, self, other); }
 
 namespace {
-// d(a+b) = (g, g): the reference's only GradFunction (binary_ops.cpp:16-33)
+// The gradient of one operand of a broadcasting binary operator, from the gradient `g` of the operator's output: summed over the dims
+// broadcasting stretched (the operand's extent-1 dims: operands of another rank than the output's never get this far, TensorIterator refuses
+// them), in the operand's dtype. An operand of the output's shape and dtype gets g itself: the same-shape path launches nothing. One
+// reduction per stretched dim: a cold path.
+Tensor grad_like_operand(Tensor g, const Tensor &operand) {
+    if (g.sizes() != operand.sizes()) {
+        CHECK_FAIL(g.dim() == operand.dim(), "gradient of rank ", g.dim(), " for an operand of rank ", operand.dim());
+        for (int d = 0; d < g.dim(); ++d) {
+            const int64_t own = operand.shape(d);
+            if (g.shape(d) == own) continue;
+            CHECK_FAIL(own == 1, "gradient extent ", g.shape(d), " does not broadcast from the operand's ", own, " in dim ", d);
+            g = sum(g, d); // keeps the dim, extent 1
+        }
+        g = g.dense().view(operand.sizes());
+    }
+    return g.dtype() == operand.dtype() ? g : convert(g, operand.dtype());
+}
+
+// d(a+b) = (g, g), each reduced to its operand's shape (the reference's only GradFunction, binary_ops.cpp:16-33, hands g itself to both:
+// it has same-shape operands in mind)
 class AddGradFunction : public GradFunction {
 public:
     AddGradFunction(const Tensor &l, const Tensor &r) { inputs = {l, r}; }
     std::vector<Tensor> backward(Tensor g) override {
         std::vector<Tensor> out(2);
-        if (inputs[0].requires_grad()) out[0] = g;
-        if (inputs[1].requires_grad()) out[1] = g;
+        if (inputs[0].requires_grad()) out[0] = grad_like_operand(g, inputs[0]);
+        if (inputs[1].requires_grad()) out[1] = grad_like_operand(g, inputs[1]);
         return out;
     }
 };
@@ -189,15 +208,20 @@ Tensor &mul_(Tensor &self, double s) { return binary_scalar_out(KF_EW_MUL, self,
 Tensor &div_(Tensor &self, double s) { return binary_scalar_out(KF_EW_DIV, self, self, s); }
 
 namespace {
-// d(a - b) = (g, -g); d(a * b) = (g * b, g * a). Same-shape operands only: a broadcast operand's gradient would need the
-// matching reduction, which nothing on the path (residual adds, gating) asks for.
+// d(a - b) = (g, -g); d(a * b) = (g * b, g * a); d(a / b) = (g / b, -g * a / b^2). Operands may broadcast against each other: each
+// operand's gradient is then summed over the stretched dims back to the operand's own shape (grad_like_operand). Same-shape operands
+// (residual adds, gating) take no reduction and launch what they always did.
 class SubGradFunction : public GradFunction {
 public:
     SubGradFunction(const Tensor &l, const Tensor &r) { inputs = {l, r}; }
     std::vector<Tensor> backward(Tensor g) override {
         std::vector<Tensor> out(2);
-        if (inputs[0].requires_grad()) out[0] = g;
-        if (inputs[1].requires_grad()) binary_scalar_out(KF_EW_MUL, out[1], g, -1.0);
+        if (inputs[0].requires_grad()) out[0] = grad_like_operand(g, inputs[0]);
+        if (inputs[1].requires_grad()) {
+            Tensor neg;
+            binary_scalar_out(KF_EW_MUL, neg, g, -1.0);
+            out[1] = grad_like_operand(neg, inputs[1]);
+        }
         return out;
     }
 };
@@ -206,32 +230,62 @@ public:
     MulGradFunction(const Tensor &l, const Tensor &r) { inputs = {l, r}; }
     std::vector<Tensor> backward(Tensor g) override {
         std::vector<Tensor> out(2);
-        if (inputs[0].requires_grad()) mul_out(out[0], g, inputs[1]);
-        if (inputs[1].requires_grad()) mul_out(out[1], g, inputs[0]);
+        for (int i = 0; i < 2; ++i) {
+            if (!inputs[i].requires_grad()) continue;
+            Tensor full;
+            mul_out(full, g, inputs[1 - i]);
+            out[i] = grad_like_operand(full, inputs[i]);
+        }
         return out;
     }
 };
-bool same_shape(const Tensor &a, const Tensor &b) { return a.sizes() == b.sizes(); }
+class DivGradFunction : public GradFunction {
+public:
+    DivGradFunction(const Tensor &l, const Tensor &r) { inputs = {l, r}; }
+    std::vector<Tensor> backward(Tensor g) override {
+        const Tensor &a = inputs[0], &b = inputs[1];
+        std::vector<Tensor> out(2);
+        if (a.requires_grad()) {
+            Tensor full;
+            div_out(full, g, b);
+            out[0] = grad_like_operand(full, a);
+        }
+        if (b.requires_grad()) { // ((g a) / b) / b, negated: every step in the output's shape
+            Tensor ga, q1, q2, full;
+            mul_out(ga, g, a);
+            div_out(q1, ga, b);
+            div_out(q2, q1, b);
+            binary_scalar_out(KF_EW_MUL, full, q2, -1.0);
+            out[1] = grad_like_operand(full, b);
+        }
+        return out;
+    }
+};
+template <class Fn> void attach_binary_grad(Tensor &out, const Tensor &l, const Tensor &r) {
+    if (l.requires_grad() || r.requires_grad()) {
+        out.set_requires_grad(true);
+        out.set_grad_fn(new Fn(l, r));
+    }
+}
 } // namespace
 Tensor sub(const Tensor &l, const Tensor &r) {
     Tensor out;
     sub_out(out, l, r);
-    if ((l.requires_grad() || r.requires_grad()) && same_shape(l, r)) {
-        out.set_requires_grad(true);
-        out.set_grad_fn(new SubGradFunction(l, r));
-    }
+    attach_binary_grad<SubGradFunction>(out, l, r);
     return out;
 }
 Tensor mul(const Tensor &l, const Tensor &r) {
     Tensor out;
     mul_out(out, l, r);
-    if ((l.requires_grad() || r.requires_grad()) && same_shape(l, r)) {
-        out.set_requires_grad(true);
-        out.set_grad_fn(new MulGradFunction(l, r));
-    }
+    attach_binary_grad<MulGradFunction>(out, l, r);
     return out;
 }
-Tensor div(const Tensor &l, const Tensor &r) { Tensor out; div_out(out, l, r); return out; }
+Tensor div(const Tensor &l, const Tensor &r) {
+    Tensor out;
+    div_out(out, l, r);
+    attach_binary_grad<DivGradFunction>(out, l, r);
+    return out;
+}
 
 // ---- unary / nullary (unary_ops.cpp:7-24, nullary_ops.cpp:6-14) --------------------------------------
 Tensor &copy_(Tensor &self, const Tensor &other) {
@@ -1240,7 +1294,11 @@ public:
         int64_t at = 0;
         for (size_t i = 0; i < inputs.size(); ++i) {
             const int64_t len = inputs[i].shape(dim_);
-            if (inputs[i].requires_grad()) out[i] = g.narrow(dim_, at, len);
+            if (inputs[i].requires_grad()) {
+                out[i] = g.narrow(dim_, at, len);
+                // concat converts every input to the first one's dtype: the gradient goes back in the input's own
+                if (out[i].dtype() != inputs[i].dtype()) out[i] = convert(out[i], inputs[i].dtype());
+            }
             at += len;
         }
         return out;

@@ -315,6 +315,7 @@ std::vector<Tensor> Tensor::split(std::vector<int64_t> indices, int64_t dim) con
 Tensor Tensor::_half() const { return gpu::convert(*this, ScalarType::Half); }
 Tensor Tensor::_bfloat16() const { return gpu::convert(*this, ScalarType::BFloat16); }
 Tensor Tensor::_float() const { return gpu::convert(*this, ScalarType::Float); }
+Tensor Tensor::_double() const { return gpu::convert(*this, ScalarType::Double); }
 
 Tensor Tensor::operator+(const Tensor &o) const { return gpu::add(*this, o); }
 Tensor &Tensor::operator+=(const Tensor &o) { return gpu::add_(*this, o); }

@@ -211,6 +211,7 @@ public:
     Tensor _half() const;
     Tensor _bfloat16() const;
     Tensor _float() const;
+    Tensor _double() const;
 
     Tensor operator+(const Tensor &other) const;
     Tensor &operator+=(const Tensor &other);

@@ -170,6 +170,77 @@ def test_view_slice_mul_scalar_cat_gradients():
     assert np.allclose(kb.grad().numpy(), tb.grad.numpy(), atol=1e-6)
 
 
+def _leaf(a, requires=True):
+    t = kfunca.from_numpy(a, 0)
+    t.set_requires_grad(requires)
+    return t
+
+
+def _same_bits(got, want):
+    return got.shape == want.shape and got.dtype == want.dtype and np.array_equal(got.view(np.uint8), want.view(np.uint8))
+
+
+def test_broadcast_operand_gets_its_gradient_summed_to_its_own_shape():
+    """x[M, N] (op) b[1, N], b[M, 1], b[1, 1] and a b[N] viewed as [1, N] (operands of different rank are refused, as on the host this one was
+    modelled on) for + - * /: b's gradient is the sum over the stretched dims, in b's shape - not the [M, N] tensor the engine used to hand
+    over (add) and not a graph cut without a word (sub, mul, div). Small integers and divisors that are powers of two: exact in any summation
+    order, so torch's bits."""
+    rng = np.random.default_rng(921)
+    x = rng.integers(-3, 4, (4, 6)).astype(np.float32)
+    g = rng.integers(-2, 3, (4, 6)).astype(np.float32)
+    ops = {"add": lambda a, b: a + b, "sub": lambda a, b: a - b, "mul": lambda a, b: a * b, "div": lambda a, b: a / b, "rsub": lambda a, b: b - a,
+           "rdiv": lambda a, b: b / a}
+    for shape in ((6,), (1, 6), (4, 1), (1, 1)):
+        for name, op in ops.items():
+            f = op if len(shape) == 2 else (lambda a, b, op=op: op(a, b.view(1, 6)))   # noqa: E731  (torch's view and this host's agree)
+            b = rng.choice([0.5, 1.0, 2.0, 4.0], size=shape).astype(np.float32) * rng.choice([-1.0, 1.0], size=shape).astype(np.float32)
+            xs = rng.choice([1.0, 2.0, 4.0], size=x.shape).astype(np.float32) if name == "rdiv" else x   # a divisor: powers of two
+            tx, tb = torch.tensor(xs, requires_grad=True), torch.tensor(b, requires_grad=True)
+            f(tx, tb).backward(torch.tensor(g))
+            kx, kb = _leaf(xs), _leaf(b)
+            y = f(kx, kb)
+            assert y.requires_grad(), (name, shape)
+            y.backward(kfunca.from_numpy(g, 0))
+            assert kb.grad().sizes() == list(shape), (name, shape, kb.grad().sizes())
+            assert _same_bits(kb.grad().numpy(), tb.grad.numpy()) and _same_bits(kx.grad().numpy(), tx.grad.numpy()), (name, shape)
+
+
+def test_broadcast_intermediate_feeds_the_next_backward_in_its_own_shape():
+    """The broadcast operand is an INTERMEDIATE: its [1, N] gradient goes on into a GradFunction that assumes [1, N] (a scale, a view), and a leaf
+    reached both ways accumulates tensors of one shape."""
+    rng = np.random.default_rng(922)
+    x, w = rng.integers(-3, 4, (5, 4)).astype(np.float32), rng.integers(-3, 4, (1, 4)).astype(np.float32)
+    g = rng.integers(-2, 3, (5, 2)).astype(np.float32)
+
+    def expr(X, W):
+        s = W * 2.0                      # [1, 4], an intermediate
+        return (X * s + s)[:, 1:3] - X[:, 1:3] * W[:, 1:3]
+
+    tx, tw = torch.tensor(x, requires_grad=True), torch.tensor(w, requires_grad=True)
+    expr(tx, tw).backward(torch.tensor(g))
+    kx, kw = _leaf(x), _leaf(w)
+    expr(kx, kw).backward(kfunca.from_numpy(g, 0))
+    assert _same_bits(kw.grad().numpy(), tw.grad.numpy()) and _same_bits(kx.grad().numpy(), tx.grad.numpy())
+
+
+def test_gradient_dtype_behind_a_mixed_dtype_cat_and_a_promoting_add():
+    """cat converts its inputs to the first one's dtype and f32 + f64 promotes: each leaf's gradient comes back in the LEAF's dtype."""
+    rng = np.random.default_rng(923)
+    a, b = rng.integers(-3, 4, (3, 4)).astype(np.float64), rng.integers(-3, 4, (3, 2)).astype(np.float32)
+    g = rng.integers(-2, 3, (3, 10)).astype(np.float64)
+    ta, tb = torch.tensor(a, requires_grad=True), torch.tensor(b, requires_grad=True)
+    (torch.cat([ta, tb.double(), ta], 1) * 2.0).backward(torch.tensor(g))
+    ka, kb = _leaf(a), _leaf(b)
+    (kfunca.cat([ka, kb, ka], 1) * 2.0).backward(kfunca.from_numpy(g, 0))
+    assert _same_bits(ka.grad().numpy(), ta.grad.numpy()) and _same_bits(kb.grad().numpy(), tb.grad.numpy())
+    c = rng.integers(-3, 4, (3, 2)).astype(np.float64)
+    tb2, tc = torch.tensor(b, requires_grad=True), torch.tensor(c, requires_grad=True)
+    (tb2 + tc).backward(torch.tensor(g[:, :2].copy()))
+    kb2, kc = _leaf(b), _leaf(c)
+    (kb2 + kc).backward(kfunca.from_numpy(g[:, :2].copy(), 0))
+    assert _same_bits(kb2.grad().numpy(), tb2.grad.numpy()) and _same_bits(kc.grad().numpy(), tc.grad.numpy())
+
+
 def test_block_step_replays_from_a_hip_graph():
     """A whole forward + backward step of the block recorded from the operator API (kfunca.graph_begin / graph_end) and replayed
     with one submission: the replay's output and gradients are bit-identical to the eager step's."""
