@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table, kf_attn_fwd_gqa, kf_attn_bwd_gqa_workspace_bytes, kf_attn_bwd_gqa, kf_glu_fwd, kf_glu_bwd, KF_ACT_*):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
+#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table, kf_attn_fwd_gqa, kf_attn_bwd_gqa_workspace_bytes, kf_attn_bwd_gqa, kf_glu_fwd, kf_glu_bwd, KF_ACT_*, kf_attn_full_fwd, kf_attn_full_bwd_workspace_bytes, kf_attn_full_bwd):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
 
 /* ---- status ------------------------------------------------------------------------------ */
 enum {
@@ -514,6 +514,36 @@ int kf_attn_bwd_gqa(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, i
                     const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo,
                     void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Full (non-causal) softmax attention with an optional per-batch key length: the attention of an encoder, of a cross-attention layer
+ * (Sq and Skv in either size order) and of a padded batch. Operands, grouped K/V heads (g = h / (Hq / Hkv)) and the layout rule are
+ * those of kf_attn_*_gqa above. kv_len: int64 [B] on the device, or NULL; len_b = clamp(kv_len[b], 0, Skv), NULL: Skv.
+ *     s[m, n] = scale <q[b,h,m,:], k[b,g,n,:]>   for n < len_b (keys n >= len_b do not exist)
+ *     o[b,h,m,:] = sum_n softmax_n(s[m,:])[n] v[b,g,n,:],   lse[b,h,m] = log sum_n exp s[m,n]   (natural log, f32, contiguous [B,Hq,Sq])
+ * A batch with len_b == 0 has o = 0 and lse = -inf and contributes zero to every gradient. K and V rows at n >= len_b are never
+ * read: padding may hold NaN or Inf. Backward: delta = rowsum(dO o O), dS = P o (dP - delta), dq = scale dS K, dk = scale dS^T Q and
+ * dv = P^T dO summed over the G query heads of a K/V head in ascending order inside one kernel (f32 accumulators, no partial arrays);
+ * rows n >= len_b of dk and dv are written as zeros. No atomics: bitwise reproducible run to run.
+ * Kernels: bf16 / f16 with D = 64 or 128 and 16-byte aligned bases run the matrix-core kernels (any Sq, Skv >= 1; profile labels
+ * attn_full_fwd_mfma_d64 / _d128, attn_full_bwd_delta, attn_full_bwd_dq_mfma_*, attn_full_bwd_dkv_mfma_*); f32 and every other head
+ * size <= 256 run plain vector-ALU kernels (attn_full_*_generic: correct, not fast). Layouts: ALL NULL - contiguous [B,H,S,D], every
+ * path - or ALL given - element strides, multiples of 8, 16-byte aligned bases, matrix-core path only (else KF_ERR_UNSUPPORTED); a mix
+ * is KF_ERR_INVALID. lse may be NULL in the forward. The workspace (kf_attn_full_bwd_workspace_bytes: delta, O(B Hq Sq)) needs no
+ * initialisation. Every argument is checked before any device call: KF_ERR_INVALID for a dtype outside {KF_F32, KF_BF16, KF_F16},
+ * D < 1 or D > 256, Hkv < 1, Hkv > Hq, Hq % Hkv != 0, Skv < 1, negative extents, a scale that is not positive and finite, null
+ * operands, bad strides or alignment and a workspace that is too small. B, Hq or Sq equal to 0 is KF_OK without a launch. No entry
+ * synchronises or allocates: the calls can be captured with kf_graph_*.
+ */
+int kf_attn_full_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                     const int64_t *kv_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
+                     const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream);
+int kf_attn_full_bwd_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, size_t *bytes);
+int kf_attn_full_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                     const int64_t *kv_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
+                     const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse,
+                     const void *d_o, const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk,
+                     void *dv, const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- rotary position embeddings (no reference counterpart: the position signal between the QKV projection and attention) ---- */
 /*

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "allocator.h"
+#include "attn_full.h"
 #include "comm.h"
 #include "device_api.h"
 #include "glu.h"
@@ -388,6 +389,13 @@ PYBIND11_MODULE(_C, m) {
         return gpu::causal_attention_qkv(qkv, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>());
     }, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none());
     m.def("causal_attention_gqa", &gpu::causal_attention_gqa, py::arg("q"), py::arg("k"), py::arg("v"));
+    // full (non-causal) attention with an optional per-batch key length (Long [B]): encoder self-attention, cross-attention, padded batches
+    m.def("attention", [](const Tensor &q, const Tensor &k, const Tensor &v, py::object kv_len) {
+        return gpu::attention(q, k, v, kv_len.is_none() ? Tensor() : kv_len.cast<Tensor>());
+    }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kv_len") = py::none());
+    m.def("attention_qkv", [](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object kv_len) {
+        return gpu::attention_qkv(qkv, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>(), kv_len.is_none() ? Tensor() : kv_len.cast<Tensor>());
+    }, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none(), py::arg("kv_len") = py::none());
     // rotary position embeddings: f64-accurate tables, and the rotation of q and k in place in the packed projection (one launch each way)
     m.def("rope_table", [](int64_t max_positions, int64_t rotary_dim, double base, int device) {
         auto [c, sn] = gpu::rope_table(max_positions, rotary_dim, base, device);

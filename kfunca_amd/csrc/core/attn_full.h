@@ -1,0 +1,23 @@
+// namespace gpu: full (non-causal) softmax attention with an optional per-batch key length (kf_attn_full_fwd, kf_attn_full_bwd), with
+// autograd. No reference counterpart: the self-attention of a vision / audio encoder (every token sees every token), cross-attention
+// (Sq text queries over Skv image keys, in either size order) and padded batches (keys beyond a sample's own length are invisible).
+#pragma once
+
+#include <cstdint>
+
+#include "tensor.h"
+
+namespace gpu {
+
+// attention(q, k, v, kv_len): q [B, Hq, Sq, D], k and v [B, Hkv, Skv, D] (Hkv divides Hq: query head h reads K/V head h / (Hq / Hkv)),
+// float, half or bfloat16. kv_len: undefined (every key is visible) or Long [B] on the operands' device; batch b sees keys
+// n < clamp(kv_len[b], 0, Skv), and K / V rows beyond that are never read (they may hold NaN). A batch without a visible key gives
+// zeros and a zero gradient. The gradients are shaped like their inputs; dk and dv are summed over each group and are zero at the
+// invisible keys. 16-bit head sizes other than 64 and 128 (D <= 128) are zero-padded to 64 or 128, with the softmax scale of the real
+// head size, so they run the matrix-core kernels too.
+Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len);
+// attention_qkv(qkv, B, S, H, kv_heads, kv_len): the packed projection [B*S, (H + 2*Hkv)*D] (columns q | k | v; kv_heads < 0: Hkv = H)
+// is read in place, the result is [B*S, H*D] and the backward writes one packed gradient - the layouts causal_attention_qkv builds.
+Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len);
+
+} // namespace gpu

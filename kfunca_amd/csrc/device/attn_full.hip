@@ -1,0 +1,1013 @@
+// Full (non-causal) softmax attention with an optional per-batch key length and grouped K/V heads, forward + backward, for gfx950
+// (include/kfunca_hip.h: kf_attn_full_*). No reference counterpart: the reference has the causal kernel only
+// (src/device/causal_attention_kernel.cu); this is the attention of an encoder, of a cross-attention layer and of a padded batch.
+//
+//   len_b  = clamp(kv_len[b], 0, Skv)   (kv_len == NULL: Skv)
+//   s[m,n] = scale <q[b,h,m], k[b,h/G,n]>  for n < len_b;  o = softmax_n(s) v;  lse = log sum_n exp s  (len_b == 0: o = 0, lse = -inf)
+//
+// Two implementations behind one ABI:
+//  * matrix-core path (bf16 / f16, D = 64 | 128, any Sq, Skv >= 1, strided operands): v_mfma_f32_32x32x16 in the operands' type, in
+//    the orientation of attention.hip ("query on the lane" for the forward and dQ, "key on the lane" for dK/dV), with its LDS image
+//    (256-byte rows, XOR swizzle, conflict-free for row reads and for ds_read_b64_tr_b16). The fragment types, the swizzle, the
+//    transposed reads, the per-wave epilogue slab and the unmasked tile bodies are COPIES of attention.hip's (attn_fwd_v3_kernel,
+//    attn_bwd_dq_v2_kernel): that file is part of the benchmark path and stays untouched.
+//      forward  one 128-query block per workgroup (4 waves x 32 queries), 64-key tiles, K | V double-buffered in LDS
+//      delta    rowsum(dO o O)
+//      dQ       one 128-query block per workgroup, 64-key tiles; S and dP recomputed
+//      dK/dV    one (batch, K/V head, 128-key block) per workgroup (4 waves x 32 keys, K and V fragments in registers); loops over the
+//               group's G query heads in ascending order and over 64-query tiles of Q | dO, f32 accumulators: the group sum needs
+//               no partial arrays, no second kernel and no atomics
+//    Tiles are staged global -> registers -> LDS with a row predicate, not by LDS-DMA: a K / V row at n >= len_b (and a Q / dO row at
+//    m >= Sq) is never LOADED - its LDS image is zeros - so padding that holds NaN or Inf cannot enter an MFMA operand, and the tile
+//    loops stop at ceil(len_b / 64). Only the last key tile of a batch runs the masked tile body.
+//  * generic path (f32; 16-bit with D <= 256 other than 64 and 128; bases that are not 16-byte aligned): plain vector-ALU kernels,
+//    one workgroup per output row, f32 accumulation, the same semantics. They are meant to be correct, not fast; an f32 matrix-core
+//    tier is out of scope.
+// No kernel uses atomics; every result is bitwise reproducible run to run.
+#include <math.h>
+
+#include <algorithm>
+#include <type_traits>
+
+#include "common.h"
+
+namespace kf {
+namespace full {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+struct Lay { int64_t sb, sh, sr; }; // byte strides of batch, head and row (the last dim is contiguous)
+
+struct FullArgs {
+    const char *q, *k, *v, *o, *d_o;
+    char *out, *dq, *dk, *dv;
+    float *lse;          // forward: written (may be null)
+    const float *lse_r;  // backward: read
+    float *delta;        // backward: rowsum(dO o O), [B, Hq, Sq]
+    const int64_t *kv_len; // [B] on the device, or null
+    int64_t B, H, Hkv, Sq, Skv, D;
+    int G;               // query heads per K/V head
+    float scale;
+    Lay lq, lk, lv, lo, ldo, ldq, ldk, ldv;
+};
+
+__device__ __forceinline__ int64_t key_len(const FullArgs &a, int64_t b) {
+    if (!a.kv_len) return a.Skv;
+    const int64_t l = a.kv_len[b];
+    return l < 0 ? 0 : (l > a.Skv ? a.Skv : l);
+}
+
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kLn2 = 0.6931471805599453f;
+
+// ==========================================================================================
+// matrix-core path (idioms of attention.hip; the LDS images are laid out for D = 128 at both head sizes)
+// ==========================================================================================
+constexpr int AD = 128;
+constexpr int AROW = AD * 2;       // bytes per row of a 16-bit tile
+constexpr int OPAD = AROW + 8;     // epilogue staging row stride (bytes)
+constexpr int TQ = 128;            // forward / dQ: queries per workgroup; dK/dV: keys per workgroup
+constexpr int TK = 64;             // forward / dQ: keys per tile; dK/dV: queries per tile
+constexpr int NT = 256;            // threads per workgroup (4 waves, one per SIMD)
+constexpr int TILE = TK * AROW;    // bytes of one 64-row tile (16 KiB)
+constexpr int SLOT = 2 * TILE;     // K | V   (dK/dV: Q | dO)
+constexpr float kDeferMax = 8.0f;
+constexpr float kPShiftLog2 = 14.f, kPShiftF16 = 16384.f; // f16 dK/dV: P is carried as P 2^14 into the dV product (attention.hip: kPShiftF16)
+
+template <bool BF> struct AFrag { using type = f16x8; };
+template <> struct AFrag<true> { using type = bf16x8; };
+
+template <bool BF>
+__device__ __forceinline__ f32x16 a_mfma(typename AFrag<BF>::type a, typename AFrag<BF>::type b, f32x16 c) {
+    if constexpr (BF)
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+
+// 16-B chunk `ch` of row `row` lives at chunk position ch ^ (((row & 3) << 2) | ((row >> 2) & 3))
+__device__ __forceinline__ int a_off(int row, int ch) { return row * AROW + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4); }
+
+// registers 8s..8s+7 of an accumulator -> 16-bit B fragment of k-step s
+template <bool BF>
+__device__ __forceinline__ typename AFrag<BF>::type a_pack(const f32x16 &x, int s) {
+    typename AFrag<BF>::type r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if constexpr (BF)
+            r[j] = (__bf16)x[8 * s + j];
+        else
+            r[j] = (_Float16)x[8 * s + j];
+    }
+    return r;
+}
+
+// accumulator row index of register e for lane half h
+__device__ __forceinline__ int a_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+
+template <bool BF>
+__device__ __forceinline__ uint32_t a_cvt16(float v) { return BF ? f32_to_bf16(v).x : f32_to_f16(v).x; }
+
+// a wave's 32 x D result held as X^T accumulators (lane = row, registers = columns) -> 16-bit rows of dst, via a per-wave LDS slab
+template <bool BF, int DB>
+__device__ __forceinline__ void a_store_rows(char *slab, char *dst, const f32x16 (&acc)[DB], float mul, int64_t rs, int nrows) {
+    const int lane = threadIdx.x & 63, xl = lane & 31, hl = lane >> 5;
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+            const uint32_t h0 = a_cvt16<BF>(acc[db][4 * gq + 0] * mul), h1 = a_cvt16<BF>(acc[db][4 * gq + 1] * mul);
+            const uint32_t h2 = a_cvt16<BF>(acc[db][4 * gq + 2] * mul), h3 = a_cvt16<BF>(acc[db][4 * gq + 3] * mul);
+            uint2 w;
+            w.x = h0 | (h1 << 16);
+            w.y = h2 | (h3 << 16);
+            const int col = db * 32 + 8 * gq + 4 * hl;
+            *(uint2 *)(slab + xl * OPAD + col * 2) = w;
+        }
+    // same wave reads back what it wrote: LDS ops of one wave complete in order
+#pragma unroll
+    for (int i = 0; i < 4 * DB; ++i) {
+        const int id = lane + 64 * i;
+        const int row = id / (8 * DB), piece = id % (8 * DB);
+        const uint2 w = *(const uint2 *)(slab + row * OPAD + piece * 8);
+        if (row < nrows) *(uint2 *)(dst + (int64_t)row * rs + piece * 8) = w;
+    }
+}
+
+// per-lane byte offset (relative to the tile, for a 16-row-aligned r0) of the two transposed reads
+__device__ __forceinline__ int a_tr_lane_off(int col0, int second) {
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 4, i = lane & 15, qq = i >> 2, p = i & 3, h = g >> 1;
+    const int ch = ((col0 + 16 * (g & 1)) >> 3) + (p >> 1);
+    return a_off(4 * h + qq + 8 * second, ch) + 8 * (p & 1);
+}
+
+// transposed reads issued from inline asm (attention.hip: tr4_issue / tr4_wait1 / tr4_wait_next)
+template <int DB> struct TrN { s16x4 lo[DB], hi[DB]; };
+using Tr4 = TrN<4>;
+using Tr2 = TrN<2>;
+template <int ROFF>
+__device__ __forceinline__ void tr4_issue(const char *tile, const int (&vo)[2][2], Tr2 &t) {
+    const unsigned base = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)tile;
+    asm volatile("ds_read_b64_tr_b16 %0, %4 offset:%c8\n\tds_read_b64_tr_b16 %1, %5 offset:%c8\n\t"
+                 "ds_read_b64_tr_b16 %2, %6 offset:%c8\n\tds_read_b64_tr_b16 %3, %7 offset:%c8"
+                 : "=&v"(t.lo[0]), "=&v"(t.hi[0]), "=&v"(t.lo[1]), "=&v"(t.hi[1])
+                 : "v"(base + vo[0][0]), "v"(base + vo[0][1]), "v"(base + vo[1][0]), "v"(base + vo[1][1]), "i"(ROFF)
+                 : "memory");
+}
+__device__ __forceinline__ void tr4_wait1(Tr2 &a) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.lo[0]), "+v"(a.hi[0]), "+v"(a.lo[1]), "+v"(a.hi[1]) : : "memory");
+}
+template <int ROFF>
+__device__ __forceinline__ void tr4_issue(const char *tile, const int (&vo)[4][2], Tr4 &t) {
+    const unsigned base = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)tile;
+    asm volatile("ds_read_b64_tr_b16 %0, %8 offset:%c16\n\tds_read_b64_tr_b16 %1, %9 offset:%c16\n\t"
+                 "ds_read_b64_tr_b16 %2, %10 offset:%c16\n\tds_read_b64_tr_b16 %3, %11 offset:%c16\n\t"
+                 "ds_read_b64_tr_b16 %4, %12 offset:%c16\n\tds_read_b64_tr_b16 %5, %13 offset:%c16\n\t"
+                 "ds_read_b64_tr_b16 %6, %14 offset:%c16\n\tds_read_b64_tr_b16 %7, %15 offset:%c16"
+                 : "=&v"(t.lo[0]), "=&v"(t.hi[0]), "=&v"(t.lo[1]), "=&v"(t.hi[1]), "=&v"(t.lo[2]), "=&v"(t.hi[2]), "=&v"(t.lo[3]), "=&v"(t.hi[3])
+                 : "v"(base + vo[0][0]), "v"(base + vo[0][1]), "v"(base + vo[1][0]), "v"(base + vo[1][1]), "v"(base + vo[2][0]),
+                   "v"(base + vo[2][1]), "v"(base + vo[3][0]), "v"(base + vo[3][1]), "i"(ROFF)
+                 : "memory");
+}
+__device__ __forceinline__ void tr4_wait1(Tr4 &a) {
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(a.lo[0]), "+v"(a.hi[0]), "+v"(a.lo[1]), "+v"(a.hi[1]), "+v"(a.lo[2]), "+v"(a.hi[2]), "+v"(a.lo[3]), "+v"(a.hi[3])
+                 :
+                 : "memory");
+}
+__device__ __forceinline__ void tr4_wait_next(Tr2 &a) {
+    asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(a.lo[0]), "+v"(a.hi[0]), "+v"(a.lo[1]), "+v"(a.hi[1]) : : "memory");
+}
+__device__ __forceinline__ void tr4_wait_next(Tr4 &a) {
+    asm volatile("s_waitcnt lgkmcnt(8)"
+                 : "+v"(a.lo[0]), "+v"(a.hi[0]), "+v"(a.lo[1]), "+v"(a.hi[1]), "+v"(a.lo[2]), "+v"(a.hi[2]), "+v"(a.lo[3]), "+v"(a.hi[3])
+                 :
+                 : "memory");
+}
+template <bool BF, int DB>
+__device__ __forceinline__ typename AFrag<BF>::type tr4_frag(const TrN<DB> &t, int d) {
+    s16x8 r;
+    r[0] = t.lo[d][0]; r[1] = t.lo[d][1]; r[2] = t.lo[d][2]; r[3] = t.lo[d][3];
+    r[4] = t.hi[d][0]; r[5] = t.hi[d][1]; r[6] = t.hi[d][2]; r[7] = t.hi[d][3];
+    return __builtin_bit_cast(typename AFrag<BF>::type, r);
+}
+
+__device__ __forceinline__ float a_half_max(float x) {
+    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+}
+__device__ __forceinline__ float a_half_sum(float x) {
+    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+}
+
+// Staging of one 64-row tile pair (K | V, or Q | dO): global -> registers (t_load, issued a tile ahead) -> swizzled LDS image (t_store).
+// 64 rows x D / 8 pieces of 16 bytes over 256 threads: D / 32 pieces of each tensor per thread. A row at or beyond `nrows` is NOT
+// loaded: its image is zeros (the key-length bound and the ragged last tile in one predicate).
+template <int D> struct TileRegs { uint4 x[D / 32], y[D / 32]; };
+template <int D>
+__device__ __forceinline__ void t_load(TileRegs<D> &r, const char *xg, const char *yg, int64_t xrs, int64_t yrs, int64_t nrows) {
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) {
+        const int id = threadIdx.x + NT * i, row = id / (D / 8), ch = id % (D / 8);
+        r.x[i] = r.y[i] = uint4{0, 0, 0, 0};
+        if (row < nrows) {
+            r.x[i] = *(const uint4 *)(xg + row * xrs + ch * 16);
+            r.y[i] = *(const uint4 *)(yg + row * yrs + ch * 16);
+        }
+    }
+}
+template <int D>
+__device__ __forceinline__ void t_store(const TileRegs<D> &r, char *slot) {
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) {
+        const int id = threadIdx.x + NT * i, row = id / (D / 8), ch = id % (D / 8);
+        *(uint4 *)(slot + a_off(row, ch)) = r.x[i];
+        *(uint4 *)(slot + TILE + a_off(row, ch)) = r.y[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// forward
+// ------------------------------------------------------------------------------------------
+// S^T = K Q^T (A = K rows from LDS, B = Q fragments in registers), online softmax with a deferred running maximum. MASK: the last
+// tile of a batch whose key count is no multiple of 64 - keys at kv0 + row >= len get -inf (their K rows are zeros in LDS)
+template <bool BF, bool MASK, int D>
+__device__ __forceinline__ void f_qk_sm(const char *buf, const typename AFrag<BF>::type (&qf)[D / 16], const int (&ko)[D / 16], f32x16 (&o)[D / 32],
+                                        typename AFrag<BF>::type (&pf)[4], float &m_i, float &l_i, float c, int64_t kv0, int64_t len, int hl) {
+    using frag_t = typename AFrag<BF>::type;
+    f32x16 s[2];
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[sub][e] = 0.f;
+#pragma unroll
+        for (int kg = 0; kg < D / 64; ++kg) {
+#pragma unroll
+            for (int kk = 4 * kg; kk < 4 * kg + 4; ++kk)
+                s[sub] = a_mfma<BF>(*(const frag_t *)(buf + sub * 32 * AROW + ko[kk]), qf[kk], s[sub]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            if (MASK && kv0 + sub * 32 + a_row(e, hl) >= len) s[sub][e] = -INFINITY;
+            mx = fmaxf(mx, s[sub][e]);
+        }
+    mx = a_half_max(mx); // finite: key kv0 of every visited tile is visible
+    // deferred running maximum (attention.hip: s_qk_sm): a larger one is adopted, and O and l rescaled, only when some query of the
+    // wave exceeds the maximum in use by more than kDeferMax exponent units
+    if (__builtin_amdgcn_ballot_w64((mx - m_i) * c > kDeferMax) != 0) {
+        const float m_new = fmaxf(m_i, mx);
+        const float alpha = __builtin_amdgcn_exp2f((m_i - m_new) * c);
+        l_i *= alpha;
+#pragma unroll
+        for (int d = 0; d < D / 32; ++d)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[d][e] *= alpha;
+        m_i = m_new;
+    }
+    const float mc = m_i * c;
+    float rs = 0.f;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[sub][e], c, -mc));
+            s[sub][e] = p;
+            rs += p;
+        }
+    rs = a_half_sum(rs);
+    l_i += rs;
+    pf[0] = a_pack<BF>(s[0], 0);
+    pf[1] = a_pack<BF>(s[0], 1);
+    pf[2] = a_pack<BF>(s[1], 0);
+    pf[3] = a_pack<BF>(s[1], 1);
+}
+
+// acc^T += T^T X^T over the 64 rows of the row-major LDS tile `vt` (A = T^T through transposed reads, B = the four packed k-steps)
+template <bool BF, int DB>
+__device__ __forceinline__ void f_pv(const char *vt, const int (&vo)[DB][2], const typename AFrag<BF>::type (&pf)[4], f32x16 (&o)[DB]) {
+    TrN<DB> ta, tb;
+    tr4_issue<0>(vt, vo, ta);
+    tr4_issue<16 * AROW>(vt, vo, tb);
+    tr4_wait_next(ta);
+#pragma unroll
+    for (int d = 0; d < DB; ++d) o[d] = a_mfma<BF>(tr4_frag<BF, DB>(ta, d), pf[0], o[d]);
+    __builtin_amdgcn_sched_barrier(0);
+    tr4_issue<32 * AROW>(vt, vo, ta);
+    tr4_wait_next(tb);
+#pragma unroll
+    for (int d = 0; d < DB; ++d) o[d] = a_mfma<BF>(tr4_frag<BF, DB>(tb, d), pf[1], o[d]);
+    __builtin_amdgcn_sched_barrier(0);
+    tr4_issue<48 * AROW>(vt, vo, tb);
+    tr4_wait_next(ta);
+#pragma unroll
+    for (int d = 0; d < DB; ++d) o[d] = a_mfma<BF>(tr4_frag<BF, DB>(ta, d), pf[2], o[d]);
+    __builtin_amdgcn_sched_barrier(0);
+    tr4_wait1(tb);
+#pragma unroll
+    for (int d = 0; d < DB; ++d) o[d] = a_mfma<BF>(tr4_frag<BF, DB>(tb, d), pf[3], o[d]);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+template <bool BF, int D>
+__global__ __launch_bounds__(NT) void attn_full_fwd_kernel(const FullArgs a) {
+    using frag_t = typename AFrag<BF>::type;
+    constexpr int KS = D / 16, DB = D / 32;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
+    const int64_t nxb = (a.Sq + TQ - 1) / TQ;
+    const int64_t xb = blockIdx.x % nxb, bh = blockIdx.x / nxb, b = bh / a.H, h = bh % a.H, g = h / a.G;
+    const int64_t len = key_len(a, b);
+    const int nt = (int)((len + TK - 1) / TK);
+    const char *Kg = a.k + b * a.lk.sb + g * a.lk.sh;
+    const char *Vg = a.v + b * a.lv.sb + g * a.lv.sh;
+    int ko[KS], vo[DB][2];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) ko[kk] = a_off(xl, kk * 2 + hl);
+#pragma unroll
+    for (int d = 0; d < DB; ++d) {
+        vo[d][0] = a_tr_lane_off(d * 32, 0);
+        vo[d][1] = a_tr_lane_off(d * 32, 1);
+    }
+    const float c = a.scale * kLog2e;
+    const int64_t qw = xb * TQ + wid * 32, m = qw + xl;
+    const bool active = qw < a.Sq; // wave-uniform
+
+    frag_t qf[KS];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[kk][j] = 0;
+    if (m < a.Sq) { // a query row beyond Sq is neither read nor stored
+        const char *Qg = a.q + b * a.lq.sb + h * a.lq.sh + m * a.lq.sr;
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) qf[kk] = *(const frag_t *)(Qg + (kk * 16 + 8 * hl) * 2);
+    }
+    f32x16 o[DB];
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[d][e] = 0.f;
+    float m_i = -INFINITY, l_i = 0.f;
+    frag_t pf[4];
+
+    TileRegs<D> tr;
+    if (nt > 0) {
+        t_load<D>(tr, Kg, Vg, a.lk.sr, a.lv.sr, len);
+        t_store<D>(tr, smem);
+    }
+    for (int t = 0; t < nt; ++t) {
+        const int64_t kv0 = (int64_t)t * TK;
+        if (t + 1 < nt) t_load<D>(tr, Kg + (kv0 + TK) * a.lk.sr, Vg + (kv0 + TK) * a.lv.sr, a.lk.sr, a.lv.sr, len - kv0 - TK);
+        __syncthreads(); // tile t is in its slot; slot (t + 1) & 1 is no longer read
+        const char *cur = smem + (t & 1) * SLOT;
+        if (active) {
+            if (kv0 + TK > len) f_qk_sm<BF, true, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
+            else f_qk_sm<BF, false, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
+            f_pv<BF, DB>(cur + TILE, vo, pf, o);
+        }
+        if (t + 1 < nt) t_store<D>(tr, smem + ((t + 1) & 1) * SLOT);
+    }
+    __syncthreads();
+    if (active) {
+        const int64_t left = a.Sq - qw;
+        const float inv = l_i > 0.f ? 1.f / l_i : 0.f; // no visible key: o = 0, lse = -inf
+        a_store_rows<BF, DB>(smem + wid * 32 * OPAD, a.out + b * a.lo.sb + h * a.lo.sh + qw * a.lo.sr, o, inv, a.lo.sr, left < 32 ? (int)left : 32);
+        if (a.lse && hl == 0 && m < a.Sq) a.lse[bh * a.Sq + m] = l_i > 0.f ? (m_i * c + __builtin_amdgcn_logf(l_i)) * kLn2 : -INFINITY;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// backward pre-pass: delta[q] = sum_d dO[q][d] * O[q][d]   (16 lanes per row, 16-B loads)
+// ------------------------------------------------------------------------------------------
+template <bool BF>
+__global__ __launch_bounds__(NT) void attn_full_delta_kernel(const char *o, const char *d_o, float *delta, int64_t nrows, Lay lo, Lay ldo, int64_t S, int64_t H,
+                                                             int nparts) {
+    const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int part = threadIdx.x & 15;
+    uint4 x = uint4{0, 0, 0, 0}, y = x;
+    if (row < nrows && part < nparts) {
+        const int64_t bh = row / S, sq = row - bh * S, bb = bh / H, hh = bh % H;
+        x = *(const uint4 *)(o + bb * lo.sb + hh * lo.sh + sq * lo.sr + part * 16);
+        y = *(const uint4 *)(d_o + bb * ldo.sb + hh * ldo.sh + sq * ldo.sr + part * 16);
+    }
+    float acc = 0.f;
+    const uint32_t xw[4] = {x.x, x.y, x.z, x.w}, yw[4] = {y.x, y.y, y.z, y.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float a0, a1, b0, b1;
+        if constexpr (BF) {
+            a0 = __uint_as_float(xw[j] << 16); a1 = __uint_as_float(xw[j] & 0xffff0000u);
+            b0 = __uint_as_float(yw[j] << 16); b1 = __uint_as_float(yw[j] & 0xffff0000u);
+        } else {
+            a0 = f16_to_f32(f16_t{(uint16_t)(xw[j] & 0xffff)}); a1 = f16_to_f32(f16_t{(uint16_t)(xw[j] >> 16)});
+            b0 = f16_to_f32(f16_t{(uint16_t)(yw[j] & 0xffff)}); b1 = f16_to_f32(f16_t{(uint16_t)(yw[j] >> 16)});
+        }
+        acc += a0 * b0 + a1 * b1;
+    }
+    for (int msk = 8; msk > 0; msk >>= 1) acc += __shfl_xor(acc, msk, 64);
+    if (row < nrows && part == 0) delta[row] = acc;
+}
+
+// ------------------------------------------------------------------------------------------
+// backward: dQ. Per 32-key sub-tile: S^T = K Q^T, dP^T = V dO^T, dS^T = P^T o (dP^T - delta), dQ^T += K^T dS^T
+// ------------------------------------------------------------------------------------------
+template <bool BF, bool MASK, int D>
+__device__ __forceinline__ void q_tile(const char *buf, const char *doslab, const typename AFrag<BF>::type (&qf)[D / 16], const int (&ko)[D / 16],
+                                       const int (&vo)[D / 32][2], f32x16 (&dq)[D / 32], float c, float lse2, float dlt, int64_t kv0, int64_t len, int hl) {
+    using frag_t = typename AFrag<BF>::type;
+    constexpr int DB = D / 32;
+    const char *vt = buf + TILE;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+        f32x16 s, dp;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { s[e] = 0.f; dp[e] = 0.f; }
+#pragma unroll
+        for (int kg = 0; kg < D / 64; ++kg) {
+#pragma unroll
+            for (int kk = 4 * kg; kk < 4 * kg + 4; ++kk) s = a_mfma<BF>(*(const frag_t *)(buf + sub * 32 * AROW + ko[kk]), qf[kk], s);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int kg = 0; kg < D / 64; ++kg) {
+#pragma unroll
+            for (int kk = 4 * kg; kk < 4 * kg + 4; ++kk)
+                dp = a_mfma<BF>(*(const frag_t *)(vt + sub * 32 * AROW + ko[kk]), *(const frag_t *)(doslab + ko[kk]), dp);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], c, -lse2));
+            if (MASK && kv0 + sub * 32 + a_row(e, hl) >= len) p = 0.f;
+            s[e] = p * (dp[e] - dlt);
+        }
+        TrN<DB> ta;
+        if (sub == 0) tr4_issue<0>(buf, vo, ta); else tr4_issue<32 * AROW>(buf, vo, ta);
+        tr4_wait1(ta);
+        { const frag_t df = a_pack<BF>(s, 0);
+#pragma unroll
+          for (int d = 0; d < DB; ++d) dq[d] = a_mfma<BF>(tr4_frag<BF, DB>(ta, d), df, dq[d]); }
+        __builtin_amdgcn_sched_barrier(0);
+        if (sub == 0) tr4_issue<16 * AROW>(buf, vo, ta); else tr4_issue<48 * AROW>(buf, vo, ta);
+        tr4_wait1(ta);
+        { const frag_t df = a_pack<BF>(s, 1);
+#pragma unroll
+          for (int d = 0; d < DB; ++d) dq[d] = a_mfma<BF>(tr4_frag<BF, DB>(ta, d), df, dq[d]); }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+constexpr int QSLAB = 32 * AROW;              // one wave's dO rows (8 KiB)
+constexpr int DQ_LDS = 2 * SLOT + 4 * QSLAB;  // two K | V slots + four dO slabs = 96 KiB
+
+template <bool BF, int D>
+__global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) {
+    using frag_t = typename AFrag<BF>::type;
+    constexpr int KS = D / 16, DB = D / 32;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
+    const int64_t nxb = (a.Sq + TQ - 1) / TQ;
+    const int64_t xb = blockIdx.x % nxb, bh = blockIdx.x / nxb, b = bh / a.H, h = bh % a.H, g = h / a.G;
+    const int64_t len = key_len(a, b);
+    const int nt = (int)((len + TK - 1) / TK);
+    const char *Kg = a.k + b * a.lk.sb + g * a.lk.sh;
+    const char *Vg = a.v + b * a.lv.sb + g * a.lv.sh;
+    char *doslab = smem + 2 * SLOT + wid * QSLAB; // this wave's dO rows, same swizzled image as a K tile (B operand of dP^T)
+    int ko[KS], vo[DB][2];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) ko[kk] = a_off(xl, kk * 2 + hl);
+#pragma unroll
+    for (int d = 0; d < DB; ++d) {
+        vo[d][0] = a_tr_lane_off(d * 32, 0);
+        vo[d][1] = a_tr_lane_off(d * 32, 1);
+    }
+    const float c = a.scale * kLog2e;
+    const int64_t qw = xb * TQ + wid * 32, m = qw + xl;
+    const bool active = qw < a.Sq;
+
+    frag_t qf[KS];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[kk][j] = 0;
+    float lse2 = 0.f, dlt = 0.f;
+    if (m < a.Sq) {
+        const char *Qg = a.q + b * a.lq.sb + h * a.lq.sh + m * a.lq.sr;
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) qf[kk] = *(const frag_t *)(Qg + (kk * 16 + 8 * hl) * 2);
+        lse2 = a.lse_r[bh * a.Sq + m] * kLog2e;
+        dlt = a.delta[bh * a.Sq + m];
+    }
+    if (active) {
+        const char *dOw = a.d_o + b * a.ldo.sb + h * a.ldo.sh + qw * a.ldo.sr;
+#pragma unroll
+        for (int i = 0; i < D / 16; ++i) { // 32 rows x D / 8 pieces of 16 B; a row beyond Sq is zeros
+            const int id = lane + 64 * i, row = id / (D / 8), ch = id % (D / 8);
+            uint4 w = uint4{0, 0, 0, 0};
+            if (qw + row < a.Sq) w = *(const uint4 *)(dOw + row * a.ldo.sr + ch * 16);
+            *(uint4 *)(doslab + a_off(row, ch)) = w;
+        }
+    }
+    f32x16 dq[DB];
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) dq[d][e] = 0.f;
+
+    TileRegs<D> tr;
+    if (nt > 0) {
+        t_load<D>(tr, Kg, Vg, a.lk.sr, a.lv.sr, len);
+        t_store<D>(tr, smem);
+    }
+    for (int t = 0; t < nt; ++t) {
+        const int64_t kv0 = (int64_t)t * TK;
+        if (t + 1 < nt) t_load<D>(tr, Kg + (kv0 + TK) * a.lk.sr, Vg + (kv0 + TK) * a.lv.sr, a.lk.sr, a.lv.sr, len - kv0 - TK);
+        __syncthreads();
+        const char *cur = smem + (t & 1) * SLOT;
+        if (active) {
+            if (kv0 + TK > len) q_tile<BF, true, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
+            else q_tile<BF, false, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
+        }
+        if (t + 1 < nt) t_store<D>(tr, smem + ((t + 1) & 1) * SLOT);
+    }
+    __syncthreads();
+    if (active) {
+        const int64_t left = a.Sq - qw;
+        a_store_rows<BF, DB>(smem + wid * 32 * OPAD, a.dq + b * a.ldq.sb + h * a.ldq.sh + qw * a.ldq.sr, dq, a.scale, a.ldq.sr, left < 32 ? (int)left : 32);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// backward: dK / dV, key on the lane. A wave owns 32 keys: their K and V rows are B fragments in registers for the whole kernel.
+// Per 64-query tile (Q | dO in LDS, the K | V image and offsets of the forward):
+//   S = Q K^T and dP = dO V^T   (A = Q / dO rows from LDS)        P = exp2(c S - lse log2 e),  dS = P o (dP - delta)
+//   dV^T += dO^T P,  dK^T += Q^T dS   (A = dO^T / Q^T through transposed reads, B = P / dS packed from the accumulators)
+// The row constants of the tile's 64 queries travel with it (two float[64] per slot). A query row beyond Sq has Q = dO = 0 and
+// lse = +inf, so P = 0 there. MASK: this wave holds keys at or beyond len (their K / V fragments are zeros): P = 0 on those lanes.
+// ------------------------------------------------------------------------------------------
+constexpr int KV_SLOT = SLOT + 512;       // Q | dO | lse log2(e) [64] | delta [64]
+constexpr int KV_LDS = 2 * KV_SLOT;
+
+template <bool BF, bool MASK, int D>
+__device__ __forceinline__ void kv_tile(const char *buf, const typename AFrag<BF>::type (&kf)[D / 16], const typename AFrag<BF>::type (&vf)[D / 16],
+                                        const int (&ko)[D / 16], const int (&vo)[D / 32][2], f32x16 (&dk)[D / 32], f32x16 (&dv)[D / 32], float c, bool dead,
+                                        int hl) {
+    using frag_t = typename AFrag<BF>::type;
+    constexpr int DB = D / 32;
+    const char *dot = buf + TILE;
+    const float *rc = (const float *)(buf + SLOT);
+    frag_t pf[4], df[4];
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+        f32x16 s, dp;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { s[e] = 0.f; dp[e] = 0.f; }
+#pragma unroll
+        for (int kg = 0; kg < D / 64; ++kg) {
+#pragma unroll
+            for (int kk = 4 * kg; kk < 4 * kg + 4; ++kk) s = a_mfma<BF>(*(const frag_t *)(buf + sub * 32 * AROW + ko[kk]), kf[kk], s);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int kg = 0; kg < D / 64; ++kg) {
+#pragma unroll
+            for (int kk = 4 * kg; kk < 4 * kg + 4; ++kk) dp = a_mfma<BF>(*(const frag_t *)(dot + sub * 32 * AROW + ko[kk]), vf[kk], dp);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { // registers 4 j .. 4 j + 3 <-> queries sub 32 + 8 j + 4 hl + 0..3
+            const float4 l4 = *(const float4 *)(rc + sub * 32 + 8 * j + 4 * hl);
+            const float4 d4 = *(const float4 *)(rc + 64 + sub * 32 + 8 * j + 4 * hl);
+            const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dl[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = 4 * j + i;
+                // f16: P travels as P 2^14 into the dV product (small weights would be subnormal f16 values), dS at its own scale
+                float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], c, (BF ? 0.f : kPShiftLog2) - lv[i]));
+                if (MASK && dead) p = 0.f;
+                s[e] = p;
+                dp[e] = BF ? p * (dp[e] - dl[i]) : p * ((dp[e] - dl[i]) * (1.f / kPShiftF16));
+            }
+        }
+        pf[2 * sub] = a_pack<BF>(s, 0);
+        pf[2 * sub + 1] = a_pack<BF>(s, 1);
+        df[2 * sub] = a_pack<BF>(dp, 0);
+        df[2 * sub + 1] = a_pack<BF>(dp, 1);
+    }
+    f_pv<BF, DB>(dot, vo, pf, dv);
+    f_pv<BF, DB>(buf, vo, df, dk);
+}
+
+template <bool BF, int D>
+__global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a) {
+    using frag_t = typename AFrag<BF>::type;
+    constexpr int KS = D / 16, DB = D / 32;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
+    const int64_t nkb = (a.Skv + TQ - 1) / TQ;
+    const int64_t kb = blockIdx.x % nkb, bg = blockIdx.x / nkb, b = bg / a.Hkv, g = bg % a.Hkv;
+    const int64_t len = key_len(a, b);
+    const int64_t k0 = kb * TQ, kw = k0 + wid * 32, n = kw + xl;
+    char *dKg = a.dk + b * a.ldk.sb + g * a.ldk.sh;
+    char *dVg = a.dv + b * a.ldv.sb + g * a.ldv.sh;
+    if (k0 >= len) { // (workgroup-uniform) a key block beyond the batch's length: its dK and dV rows are zeros
+        const int64_t rows = a.Skv - k0 < TQ ? a.Skv - k0 : TQ;
+        for (int id = threadIdx.x; id < rows * (D / 8); id += NT) {
+            const int row = id / (D / 8), ch = id % (D / 8);
+            *(uint4 *)(dKg + (k0 + row) * a.ldk.sr + ch * 16) = uint4{0, 0, 0, 0};
+            *(uint4 *)(dVg + (k0 + row) * a.ldv.sr + ch * 16) = uint4{0, 0, 0, 0};
+        }
+        return;
+    }
+    int ko[KS], vo[DB][2];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) ko[kk] = a_off(xl, kk * 2 + hl);
+#pragma unroll
+    for (int d = 0; d < DB; ++d) {
+        vo[d][0] = a_tr_lane_off(d * 32, 0);
+        vo[d][1] = a_tr_lane_off(d * 32, 1);
+    }
+    const float c = a.scale * kLog2e;
+    const bool dead = n >= len;        // this lane's key does not exist
+    const bool work = kw < len;        // wave-uniform: the wave has a visible key
+    const bool ragged = kw + 32 > len; // wave-uniform: some lane's key is beyond len
+
+    frag_t kf[KS], vf[KS];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { kf[kk][j] = 0; vf[kk][j] = 0; }
+    if (!dead) { // K / V rows at n >= len are never read
+        const char *Kr = a.k + b * a.lk.sb + g * a.lk.sh + n * a.lk.sr;
+        const char *Vr = a.v + b * a.lv.sb + g * a.lv.sh + n * a.lv.sr;
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) {
+            kf[kk] = *(const frag_t *)(Kr + (kk * 16 + 8 * hl) * 2);
+            vf[kk] = *(const frag_t *)(Vr + (kk * 16 + 8 * hl) * 2);
+        }
+    }
+    f32x16 dk[DB], dv[DB];
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { dk[d][e] = 0.f; dv[d][e] = 0.f; }
+
+    const int nqt = (int)((a.Sq + TK - 1) / TK);
+    const int64_t nit = (int64_t)a.G * nqt; // query heads g G .. g G + G - 1 in ascending order, each over all its query tiles
+    TileRegs<D> tr;
+    float rcv = 0.f;
+    auto load = [&](int64_t it) {
+        const int64_t hh = g * a.G + it / nqt, q0 = (it % nqt) * TK, bh = b * a.H + hh;
+        t_load<D>(tr, a.q + b * a.lq.sb + hh * a.lq.sh + q0 * a.lq.sr, a.d_o + b * a.ldo.sb + hh * a.ldo.sh + q0 * a.ldo.sr, a.lq.sr, a.ldo.sr, a.Sq - q0);
+        if (threadIdx.x < 128) {
+            const int64_t mq = q0 + (threadIdx.x & 63);
+            if (threadIdx.x < 64) rcv = mq < a.Sq ? a.lse_r[bh * a.Sq + mq] * kLog2e : INFINITY;
+            else rcv = mq < a.Sq ? a.delta[bh * a.Sq + mq] : 0.f;
+        }
+    };
+    auto store = [&](char *slot) {
+        t_store<D>(tr, slot);
+        if (threadIdx.x < 128) ((float *)(slot + SLOT))[threadIdx.x] = rcv;
+    };
+    load(0);
+    store(smem);
+    for (int64_t it = 0; it < nit; ++it) {
+        if (it + 1 < nit) load(it + 1);
+        __syncthreads();
+        const char *cur = smem + (it & 1) * KV_SLOT;
+        if (work) {
+            if (ragged) kv_tile<BF, true, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
+            else kv_tile<BF, false, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
+        }
+        if (it + 1 < nit) store(smem + ((it + 1) & 1) * KV_SLOT);
+    }
+    __syncthreads();
+    if (kw < a.Skv) { // a wave without a visible key stores its zeros: rows n >= len of dK and dV are zeros
+        const int64_t left = a.Skv - kw;
+        const int nrows = left < 32 ? (int)left : 32;
+        a_store_rows<BF, DB>(smem + wid * 32 * OPAD, dKg + kw * a.ldk.sr, dk, a.scale, a.ldk.sr, nrows);
+        a_store_rows<BF, DB>(smem + wid * 32 * OPAD, dVg + kw * a.ldv.sr, dv, BF ? 1.f : 1.f / kPShiftF16, a.ldv.sr, nrows);
+    }
+}
+
+// ==========================================================================================
+// generic path: contiguous tensors, one workgroup of 256 threads per output row, 256 partners per step
+// ==========================================================================================
+template <typename T> __device__ __forceinline__ float g_ld(const T *p) { return (float)*p; }
+template <> __device__ __forceinline__ float g_ld<bf16_t>(const bf16_t *p) { return bf16_to_f32(*p); }
+template <> __device__ __forceinline__ float g_ld<f16_t>(const f16_t *p) { return f16_to_f32(*p); }
+template <typename T> __device__ __forceinline__ void g_st(T *p, float v) { *p = (T)v; }
+template <> __device__ __forceinline__ void g_st<bf16_t>(bf16_t *p, float v) { *p = f32_to_bf16(v); }
+template <> __device__ __forceinline__ void g_st<f16_t>(f16_t *p, float v) { *p = f32_to_f16(v); }
+
+template <bool MAX>
+__device__ __forceinline__ float g_block_reduce(float v, float *red) { // every thread gets the result; red: 4 floats, reusable after return
+    for (int msk = 32; msk > 0; msk >>= 1) {
+        const float w = __shfl_xor(v, msk, 64);
+        v = MAX ? fmaxf(v, w) : v + w;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return MAX ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void attn_full_fwd_generic_kernel(const FullArgs a) {
+    __shared__ float qs[256], ps[256], red[4];
+    const int tid = threadIdx.x, D = (int)a.D;
+    const int64_t bh = blockIdx.x / a.Sq, m = blockIdx.x % a.Sq, b = bh / a.H, h = bh % a.H, g = h / a.G;
+    const int64_t len = key_len(a, b);
+    const T *Q = (const T *)a.q + (bh * a.Sq + m) * D;
+    const T *K = (const T *)a.k + (b * a.Hkv + g) * a.Skv * D;
+    const T *V = (const T *)a.v + (b * a.Hkv + g) * a.Skv * D;
+    if (tid < D) qs[tid] = g_ld(Q + tid);
+    __syncthreads();
+    float acc = 0.f, mrun = -INFINITY, lrun = 0.f;
+    for (int64_t c0 = 0; c0 < len; c0 += NT) {
+        const int64_t n = c0 + tid;
+        float s = -INFINITY;
+        if (n < len) {
+            float dot = 0.f;
+            for (int d = 0; d < D; ++d) dot += qs[d] * g_ld(K + n * D + d);
+            s = dot * a.scale;
+        }
+        const float mnew = fmaxf(mrun, g_block_reduce<true>(s, red)); // finite: key c0 exists
+        const float alpha = expf(mrun - mnew), p = n < len ? expf(s - mnew) : 0.f;
+        ps[tid] = p;
+        lrun = lrun * alpha + g_block_reduce<false>(p, red); // (its barriers publish ps)
+        if (tid < D) {
+            const int cnt = (int)(len - c0 < NT ? len - c0 : NT);
+            float t = 0.f;
+            for (int j = 0; j < cnt; ++j) t += ps[j] * g_ld(V + (c0 + j) * D + tid);
+            acc = acc * alpha + t;
+        }
+        mrun = mnew;
+        __syncthreads();
+    }
+    if (tid < D) g_st((T *)a.out + (bh * a.Sq + m) * D + tid, lrun > 0.f ? acc / lrun : 0.f);
+    if (tid == 0 && a.lse) a.lse[bh * a.Sq + m] = lrun > 0.f ? mrun + logf(lrun) : -INFINITY;
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void attn_full_delta_generic_kernel(const T *o, const T *d_o, float *delta, int64_t nrows, int D) {
+    const int64_t row = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (row >= nrows) return;
+    float acc = 0.f;
+    for (int d = 0; d < D; ++d) acc += g_ld(o + row * D + d) * g_ld(d_o + row * D + d);
+    delta[row] = acc;
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const FullArgs a) {
+    __shared__ float qs[256], dos[256], dss[256];
+    const int tid = threadIdx.x, D = (int)a.D;
+    const int64_t bh = blockIdx.x / a.Sq, m = blockIdx.x % a.Sq, b = bh / a.H, h = bh % a.H, g = h / a.G;
+    const int64_t len = key_len(a, b);
+    const T *K = (const T *)a.k + (b * a.Hkv + g) * a.Skv * D;
+    const T *V = (const T *)a.v + (b * a.Hkv + g) * a.Skv * D;
+    if (tid < D) {
+        qs[tid] = g_ld((const T *)a.q + (bh * a.Sq + m) * D + tid);
+        dos[tid] = g_ld((const T *)a.d_o + (bh * a.Sq + m) * D + tid);
+    }
+    const float lse = a.lse_r[bh * a.Sq + m], dlt = a.delta[bh * a.Sq + m];
+    __syncthreads();
+    float acc = 0.f;
+    for (int64_t c0 = 0; c0 < len; c0 += NT) {
+        const int64_t n = c0 + tid;
+        float ds = 0.f;
+        if (n < len) {
+            float dot = 0.f, dp = 0.f;
+            for (int d = 0; d < D; ++d) {
+                dot += qs[d] * g_ld(K + n * D + d);
+                dp += dos[d] * g_ld(V + n * D + d);
+            }
+            ds = expf(dot * a.scale - lse) * (dp - dlt);
+        }
+        dss[tid] = ds;
+        __syncthreads();
+        if (tid < D) {
+            const int cnt = (int)(len - c0 < NT ? len - c0 : NT);
+            for (int j = 0; j < cnt; ++j) acc += dss[j] * g_ld(K + (c0 + j) * D + tid);
+        }
+        __syncthreads();
+    }
+    if (tid < D) g_st((T *)a.dq + (bh * a.Sq + m) * D + tid, acc * a.scale);
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const FullArgs a) {
+    __shared__ float ks[256], vs[256], ps[256], dss[256];
+    const int tid = threadIdx.x, D = (int)a.D;
+    const int64_t bg = blockIdx.x / a.Skv, n = blockIdx.x % a.Skv, b = bg / a.Hkv, g = bg % a.Hkv;
+    const int64_t len = key_len(a, b);
+    T *dK = (T *)a.dk + (bg * a.Skv + n) * D, *dV = (T *)a.dv + (bg * a.Skv + n) * D;
+    if (n >= len) { // (workgroup-uniform)
+        if (tid < D) { g_st(dK + tid, 0.f); g_st(dV + tid, 0.f); }
+        return;
+    }
+    if (tid < D) {
+        ks[tid] = g_ld((const T *)a.k + (bg * a.Skv + n) * D + tid);
+        vs[tid] = g_ld((const T *)a.v + (bg * a.Skv + n) * D + tid);
+    }
+    __syncthreads();
+    float ak = 0.f, av = 0.f;
+    for (int hh = 0; hh < a.G; ++hh) {
+        const int64_t bh = b * a.H + g * a.G + hh;
+        const T *Q = (const T *)a.q + bh * a.Sq * D, *dO = (const T *)a.d_o + bh * a.Sq * D;
+        for (int64_t c0 = 0; c0 < a.Sq; c0 += NT) {
+            const int64_t m = c0 + tid;
+            float p = 0.f, ds = 0.f;
+            if (m < a.Sq) {
+                float dot = 0.f, dp = 0.f;
+                for (int d = 0; d < D; ++d) {
+                    dot += ks[d] * g_ld(Q + m * D + d);
+                    dp += vs[d] * g_ld(dO + m * D + d);
+                }
+                p = expf(dot * a.scale - a.lse_r[bh * a.Sq + m]);
+                ds = p * (dp - a.delta[bh * a.Sq + m]);
+            }
+            ps[tid] = p;
+            dss[tid] = ds;
+            __syncthreads();
+            if (tid < D) {
+                const int cnt = (int)(a.Sq - c0 < NT ? a.Sq - c0 : NT);
+                for (int j = 0; j < cnt; ++j) {
+                    av += ps[j] * g_ld(dO + (c0 + j) * D + tid);
+                    ak += dss[j] * g_ld(Q + (c0 + j) * D + tid);
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid < D) { g_st(dK + tid, ak * a.scale); g_st(dV + tid, av); }
+}
+
+// ==========================================================================================
+// host
+// ==========================================================================================
+static inline size_t a_align(size_t v) { return (v + 255) / 256 * 256; }
+static size_t ws_bytes(int64_t B, int64_t Hq, int64_t Sq) { return a_align((size_t)B * Hq * Sq * sizeof(float)); } // delta [B, Hq, Sq]
+
+static Lay lay_contig(int64_t H, int64_t S, int64_t D, int es) { return {H * S * D * es, S * D * es, D * es}; }
+static bool lay_from(const kf_attn_layout *l, int es, Lay &out) {
+    if (!l || l->batch < 0 || l->head < 0 || l->row < 0) return false;
+    out = {l->batch * es, l->head * es, l->row * es};
+    return l->batch % 8 == 0 && l->head % 8 == 0 && l->row % 8 == 0;
+}
+
+enum Plan { PLAN_NONE, PLAN_MFMA, PLAN_GENERIC };
+
+// Everything that can be refused, in one place and before any device call. `ops`: the operand pointers in the order of `lay`
+// (forward: q k v o; backward: + dO dQ dK dV). plan == PLAN_NONE with KF_OK: nothing to do (B, Hq or Sq is 0).
+static int full_check(const char *who, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                      const void *const *ops, const kf_attn_layout *const *lay, int nlay, FullArgs &a, Plan &plan) {
+    plan = PLAN_NONE;
+    KF_REQUIRE(dtype == KF_F32 || dtype == KF_BF16 || dtype == KF_F16, KF_ERR_INVALID, "%s: dtype %d is not f32, bf16 or f16", who, dtype);
+    KF_REQUIRE(B >= 0 && Hq >= 0 && Sq >= 0 && Skv >= 0, KF_ERR_INVALID, "%s: negative extent", who);
+    KF_REQUIRE(D >= 1 && D <= 256, KF_ERR_INVALID, "%s: head size %lld outside [1, 256]", who, (long long)D);
+    KF_REQUIRE(Skv >= 1, KF_ERR_INVALID, "%s: Skv must be positive", who);
+    KF_REQUIRE(scale > 0.f && scale < INFINITY, KF_ERR_INVALID, "%s: the softmax scale must be positive and finite", who);
+    if (Hq == 0) return KF_OK;
+    KF_REQUIRE(Hkv >= 1 && Hkv <= Hq && Hq % Hkv == 0, KF_ERR_INVALID, "%s: Hkv %lld must divide Hq %lld (1 <= Hkv <= Hq)", who, (long long)Hkv,
+               (long long)Hq);
+    int given = 0;
+    for (int i = 0; i < nlay; ++i) given += lay[i] != nullptr;
+    KF_REQUIRE(given == 0 || given == nlay, KF_ERR_INVALID, "%s: the layouts are all NULL (contiguous tensors) or all given, not %d of %d", who, given, nlay);
+    const bool strided = nlay > 0 && given == nlay;
+    Lay L[8];
+    const int es = dtype_size(dtype);
+    uintptr_t bits = 0;
+    for (int i = 0; i < nlay; ++i) {
+        const bool key_rows = i == 1 || i == 2 || i >= 6; // k, v, dK, dV: Hkv heads of Skv rows
+        if (strided) KF_REQUIRE(lay_from(lay[i], es, L[i]), KF_ERR_INVALID, "%s: strides must be non-negative multiples of 8 elements", who);
+        else L[i] = lay_contig(key_rows ? Hkv : Hq, key_rows ? Skv : Sq, D, es);
+    }
+    if (B == 0 || Sq == 0) return KF_OK;
+    for (int i = 0; i < nlay; ++i) {
+        KF_REQUIRE(ops[i], KF_ERR_INVALID, "%s: null operand", who);
+        bits |= (uintptr_t)ops[i];
+    }
+    const bool mfma_shape = (dtype == KF_BF16 || dtype == KF_F16) && (D == 64 || D == 128);
+    if (strided) {
+        KF_REQUIRE(bits % 16 == 0, KF_ERR_INVALID, "%s: strided operands must be 16-byte aligned", who);
+        KF_REQUIRE(mfma_shape, KF_ERR_UNSUPPORTED, "%s: strided layouts are served by the 16-bit matrix-core kernels only (D = 64 or 128)", who);
+    }
+    KF_REQUIRE(bits % es == 0, KF_ERR_INVALID, "%s: an operand is not aligned to its element", who);
+    plan = mfma_shape && bits % 16 == 0 ? PLAN_MFMA : PLAN_GENERIC;
+    const int64_t blocks = plan == PLAN_MFMA ? (B * Hq * Sq + 15) / 16 /* the delta kernel: 16 rows per workgroup */ : B * Hq * Sq, kblocks = plan == PLAN_MFMA ? B * Hkv * ((Skv + TQ - 1) / TQ) : B * Hkv * Skv;
+    KF_REQUIRE(B * Hq <= (1ll << 24) && Sq <= (1ll << 31) && Skv <= (1ll << 31) && blocks < (1ll << 31) && kblocks < (1ll << 31), KF_ERR_UNSUPPORTED,
+               "%s: the problem needs more than 2^31 workgroups", who);
+    memset(&a, 0, sizeof(a));
+    a.B = B; a.H = Hq; a.Hkv = Hkv; a.Sq = Sq; a.Skv = Skv; a.D = D;
+    a.G = (int)(Hq / Hkv);
+    a.scale = scale;
+    Lay *const out[8] = {&a.lq, &a.lk, &a.lv, &a.lo, &a.ldo, &a.ldq, &a.ldk, &a.ldv};
+    for (int i = 0; i < nlay; ++i) *out[i] = L[i];
+    return KF_OK;
+}
+
+} // namespace full
+} // namespace kf
+
+using namespace kf;
+using namespace kf::full;
+
+extern "C" int kf_attn_full_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
+                                const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
+                                void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+    const void *ops[4] = {q, k, v, o};
+    const kf_attn_layout *lay[4] = {lq, lk, lv, lo};
+    FullArgs a;
+    Plan plan;
+    int rc = full_check("kf_attn_full_fwd", dtype, B, Hq, Hkv, Sq, Skv, D, scale, ops, lay, 4, a, plan);
+    if (rc != KF_OK || plan == PLAN_NONE) return rc;
+    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.out = (char *)o; a.lse = lse; a.kv_len = kv_len;
+    hipStream_t st = as_stream(stream);
+    const bool bf = dtype == KF_BF16, d64 = D == 64;
+    if (plan == PLAN_MFMA) {
+        const unsigned grid = (unsigned)(B * Hq * ((Sq + TQ - 1) / TQ));
+        KF_PROF(d64 ? "attn_full_fwd_mfma_d64" : "attn_full_fwd_mfma_d128", st);
+        return with_flags([&](auto BF, auto D64) { return launch(attn_full_fwd_kernel<BF, D64 ? 64 : 128>, grid, NT, 2 * SLOT, st, a); }, bf, d64);
+    }
+    KF_PROF("attn_full_fwd_generic", st);
+    return launch(dtype == KF_F32 ? attn_full_fwd_generic_kernel<float> : bf ? attn_full_fwd_generic_kernel<bf16_t> : attn_full_fwd_generic_kernel<f16_t>,
+                  (unsigned)(B * Hq * Sq), NT, 0, st, a);
+}
+
+extern "C" int kf_attn_full_bwd_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, size_t *bytes) {
+    KF_REQUIRE(bytes, KF_ERR_INVALID, "kf_attn_full_bwd_workspace_bytes: null out pointer");
+    FullArgs a;
+    Plan plan;
+    int rc = full_check("kf_attn_full_bwd_workspace_bytes", dtype, B, Hq, Hkv, Sq, Skv, D, 1.f, nullptr, nullptr, 0, a, plan);
+    if (rc != KF_OK) return rc;
+    *bytes = ws_bytes(B, Hq, Sq);
+    return KF_OK;
+}
+
+extern "C" int kf_attn_full_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
+                                const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
+                                const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
+                                const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv, void *workspace,
+                                size_t workspace_bytes, void *stream) {
+    const void *ops[8] = {q, k, v, o, d_o, dq, dk, dv};
+    const kf_attn_layout *lay[8] = {lq, lk, lv, lo, ldo, ldq, ldk, ldv};
+    FullArgs a;
+    Plan plan;
+    int rc = full_check("kf_attn_full_bwd", dtype, B, Hq, Hkv, Sq, Skv, D, scale, ops, lay, 8, a, plan);
+    if (rc != KF_OK || plan == PLAN_NONE) return rc;
+    KF_REQUIRE(lse, KF_ERR_INVALID, "kf_attn_full_bwd: null operand");
+    const size_t need = ws_bytes(B, Hq, Sq);
+    KF_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % sizeof(float) == 0, KF_ERR_INVALID,
+               "kf_attn_full_bwd: workspace of at least %zu bytes required (kf_attn_full_bwd_workspace_bytes), got %zu", need, workspace_bytes);
+    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.o = (const char *)o; a.d_o = (const char *)d_o;
+    a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv;
+    a.lse_r = lse; a.delta = (float *)workspace; a.kv_len = kv_len;
+    hipStream_t st = as_stream(stream);
+    const bool bf = dtype == KF_BF16, d64 = D == 64;
+    const int64_t nrows = B * Hq * Sq;
+    if (plan == PLAN_MFMA) {
+        {
+            KF_PROF("attn_full_bwd_delta", st);
+            rc = with_flags([&](auto BF) { return launch(attn_full_delta_kernel<BF>, (unsigned)((nrows + 15) / 16), NT, 0, st, a.o, a.d_o, a.delta, nrows, a.lo, a.ldo, Sq, Hq, (int)(D / 8)); }, bf);
+            if (rc != KF_OK) return rc;
+        }
+        {
+            KF_PROF(d64 ? "attn_full_bwd_dq_mfma_d64" : "attn_full_bwd_dq_mfma_d128", st);
+            const unsigned grid = (unsigned)(B * Hq * ((Sq + TQ - 1) / TQ));
+            rc = with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dq_kernel<BF, D64 ? 64 : 128>, grid, NT, DQ_LDS, st, a); }, bf, d64);
+            if (rc != KF_OK) return rc;
+        }
+        KF_PROF(d64 ? "attn_full_bwd_dkv_mfma_d64" : "attn_full_bwd_dkv_mfma_d128", st);
+        const unsigned grid = (unsigned)(B * Hkv * ((Skv + TQ - 1) / TQ));
+        return with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dkv_kernel<BF, D64 ? 64 : 128>, grid, NT, KV_LDS, st, a); }, bf, d64);
+    }
+    {
+        KF_PROF("attn_full_bwd_delta_generic", st);
+        const unsigned grid = (unsigned)((nrows + NT - 1) / NT);
+        if (dtype == KF_F32) rc = launch(attn_full_delta_generic_kernel<float>, grid, NT, 0, st, (const float *)o, (const float *)d_o, a.delta, nrows, (int)D);
+        else if (bf) rc = launch(attn_full_delta_generic_kernel<bf16_t>, grid, NT, 0, st, (const bf16_t *)o, (const bf16_t *)d_o, a.delta, nrows, (int)D);
+        else rc = launch(attn_full_delta_generic_kernel<f16_t>, grid, NT, 0, st, (const f16_t *)o, (const f16_t *)d_o, a.delta, nrows, (int)D);
+        if (rc != KF_OK) return rc;
+    }
+    {
+        KF_PROF("attn_full_bwd_dq_generic", st);
+        rc = launch(dtype == KF_F32 ? attn_full_bwd_dq_generic_kernel<float> : bf ? attn_full_bwd_dq_generic_kernel<bf16_t> : attn_full_bwd_dq_generic_kernel<f16_t>,
+                    (unsigned)nrows, NT, 0, st, a);
+        if (rc != KF_OK) return rc;
+    }
+    KF_PROF("attn_full_bwd_dkv_generic", st);
+    return launch(dtype == KF_F32 ? attn_full_bwd_dkv_generic_kernel<float> : bf ? attn_full_bwd_dkv_generic_kernel<bf16_t> : attn_full_bwd_dkv_generic_kernel<f16_t>,
+                  (unsigned)(B * Hkv * Skv), NT, 0, st, a);
+}
