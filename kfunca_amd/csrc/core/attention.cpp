@@ -1,0 +1,341 @@
+// namespace gpu: the attention operators over the C ABI's attention entries - causal_attention, causal_attention_gqa and
+// causal_attention_qkv (ops.h; nn_ops.cpp:6-8 + the checks of causal_attention_kernel.cu:9-20), attention and attention_qkv (attn_full.h).
+// Three families of entries, one host path: check, plan the padding, pad, allocate, call, un-pad.
+#include <cmath>
+
+#include "allocator.h"
+#include "attn_full.h"
+#include "device_api.h"
+#include "ops.h"
+
+namespace gpu {
+
+using utils::memory::DataPtr;
+using utils::memory::DeviceAllocator;
+
+namespace {
+
+int code(ScalarType t) { return static_cast<int>(t); }
+bool h16(ScalarType t) { return t == ScalarType::Half || t == ScalarType::BFloat16; }
+
+enum class Family {
+    CausalMha, // kf_attn_fwd / kf_attn_bwd, their _scaled forms for padded operands, their _strided forms for the packed projection
+    CausalGqa, // kf_attn_fwd_gqa / kf_attn_bwd_gqa: query head h reads K/V head h / (Hq / Hkv)
+    Full,      // kf_attn_full_fwd / kf_attn_full_bwd: no mask but an optional per-batch key length
+};
+
+// One call as the C ABI takes it: the sizes handed down (padded ones where the host pads), the scale of the REAL head size, and the
+// layouts of q, k, v and their gradients (lx) and of out and its gradient (lo); NULL: contiguous [B, H, S, D].
+struct Call {
+    Family family;
+    int dt, device;
+    int64_t B, Hq, Hkv, Sq, Skv, D;
+    float scale;
+    const int64_t *kv_len;
+    const kf_attn_layout *lx, *lo;
+    bool padded;
+};
+
+void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o, float *lse) {
+    void *st = dev::stream(c.device);
+    switch (c.family) {
+    case Family::CausalMha:
+        if (c.lx) DEV_CALL(kf_attn_fwd_strided(c.dt, c.B, c.Hq, c.Sq, c.Skv, c.D, c.scale, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        else if (c.padded) DEV_CALL(kf_attn_fwd_scaled(c.dt, c.B, c.Hq, c.Sq, c.Skv, c.D, c.scale, q, k, v, o, lse, st));
+        else DEV_CALL(kf_attn_fwd(c.dt, c.B, c.Hq, c.Sq, c.Skv, c.D, q, k, v, o, lse, st));
+        break;
+    case Family::CausalGqa:
+        DEV_CALL(kf_attn_fwd_gqa(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        break;
+    case Family::Full:
+        DEV_CALL(kf_attn_full_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        break;
+    }
+}
+
+void run_bwd(const Call &c, const void *q, const void *k, const void *v, const void *o, const float *lse, const void *go, void *dq, void *dk, void *dv,
+             void *ws, size_t bytes) {
+    void *st = dev::stream(c.device);
+    switch (c.family) {
+    case Family::CausalMha:
+        if (c.lx)
+            DEV_CALL(kf_attn_bwd_strided(c.dt, c.B, c.Hq, c.Sq, c.Skv, c.D, c.scale, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq, c.lx, dk, c.lx,
+                                         dv, c.lx, ws, bytes, st));
+        else if (c.padded) DEV_CALL(kf_attn_bwd_scaled(c.dt, c.B, c.Hq, c.Sq, c.Skv, c.D, c.scale, q, k, v, o, lse, go, dq, dk, dv, ws, bytes, st));
+        else DEV_CALL(kf_attn_bwd(c.dt, c.B, c.Hq, c.Sq, c.Skv, c.D, q, k, v, o, lse, go, dq, dk, dv, ws, bytes, st));
+        break;
+    case Family::CausalGqa:
+        DEV_CALL(kf_attn_bwd_gqa(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq, c.lx, dk, c.lx,
+                                 dv, c.lx, ws, bytes, st));
+        break;
+    case Family::Full:
+        DEV_CALL(kf_attn_full_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq, c.lx,
+                                  dk, c.lx, dv, c.lx, ws, bytes, st));
+        break;
+    }
+}
+
+// Backward scratch of the causal families: the size the device library recommends (statistics + dS of as many (batch, head) pairs as
+// its cap allows); when the allocator cannot supply that, halve the part above `floor_` (the dS part) until it can - the library accepts
+// anything down to its minimum (then the recomputing dQ kernel runs: kf_attn_bwd, include/kfunca_hip.h).
+DataPtr alloc_shrinking(size_t need, size_t floor_, int device, size_t &bytes) {
+    for (;;) {
+        try {
+            bytes = need;
+            return DeviceAllocator::GetInstance()->allocate(need, device);
+        } catch (const utils::OutOfMemory &) { // only that: any other failure is not cured by asking for less
+            if (need <= floor_) throw;
+            need = floor_ + (need - floor_) / 2;
+            if (need - floor_ < ((size_t)1 << 20)) need = floor_;
+        }
+    }
+}
+DataPtr bwd_scratch(const Call &c, size_t &bytes) {
+    size_t need = 0, floor_ = 0;
+    switch (c.family) {
+    case Family::CausalMha:
+        DEV_CALL(kf_attn_bwd_workspace_bytes(c.dt, c.B, c.Hq, c.Sq, c.Skv, c.D, &need));
+        floor_ = 3 * (((size_t)c.B * c.Hq * c.Sq * sizeof(float) + 255) / 256 * 256);
+        break;
+    case Family::CausalGqa: // the library's minimum (statistics + the dK / dV partials) is the floor of the OOM retries
+        DEV_CALL(kf_attn_bwd_gqa_workspace_bytes(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, &need, &floor_));
+        break;
+    case Family::Full: // one size, no smaller form to retry with
+        DEV_CALL(kf_attn_full_bwd_workspace_bytes(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, &bytes));
+        return DeviceAllocator::GetInstance()->allocate(bytes > 0 ? bytes : 1, c.device);
+    }
+    return alloc_shrinking(need, floor_, c.device, bytes);
+}
+
+// The refusals of causal_attention_gqa and attention carry their operator's name; causal_attention's carry no text but the dtype's.
+void check_operands(Family f, const Tensor &q, const Tensor &k, const Tensor &v) {
+    const char *op = f == Family::Full ? "attention" : "causal_attention_gqa";
+    auto text = [&](auto... parts) { return f == Family::CausalMha ? std::string() : utils::concat(op, parts...); };
+    CHECK_FAIL(q.defined() && k.defined() && v.defined() && q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
+               text(" expects q [B, Hq, Sq, D] and k, v [B, Hkv, Skv, D]"));
+    CHECK_FAIL(k.shape(0) == q.shape(0) && k.shape(3) == q.shape(3) && k.sizes() == v.sizes(), text(": shapes of q, k, v do not match"));
+    CHECK_FAIL(f == Family::CausalMha ? k.shape(1) == q.shape(1) : k.shape(1) >= 1 && k.shape(1) <= q.shape(1) && q.shape(1) % k.shape(1) == 0,
+               text(": the K/V head count ", k.shape(1), " must divide the query head count ", q.shape(1)));
+    CHECK_FAIL(q.dtype() == k.dtype() && q.dtype() == v.dtype(), text(": q, k, v must share a dtype"));
+    CHECK_FAIL(q.dtype() == ScalarType::Float || h16(q.dtype()),
+               f == Family::Full ? std::string("attention supports float, half and bfloat16") : utils::concat("Unsupported ScalarType ", q.dtype()));
+    if (f == Family::Full) {
+        CHECK_FAIL(q.shape(3) >= 1 && q.shape(3) <= 256, "attention: head size ", q.shape(3), " outside [1, 256]");
+        CHECK_FAIL(k.shape(2) >= 1, "attention: keys are empty");
+    }
+    CHECK_FAIL(q.is_dense() && k.is_dense() && v.is_dense(), text(" expects dense tensors"));
+    CHECK_FAIL(q.device() == k.device() && q.device() == v.device(), text(": q, k, v must be on one device"));
+}
+// the kernels read kv_len as a dense int64 array
+Tensor check_len(const Tensor &kv_len, int64_t B, int device) {
+    if (!kv_len.defined()) return Tensor();
+    CHECK_FAIL(kv_len.dtype() == ScalarType::Long, "attention: kv_len must be of type Long");
+    CHECK_FAIL(kv_len.numel() == B && kv_len.device() == device, "attention: kv_len must hold B = ", B, " elements on the operands' device");
+    return kv_len.dense();
+}
+const int64_t *len_ptr(const Tensor &kv_len) { return kv_len.defined() ? static_cast<const int64_t *>(kv_len.data_ptr()) : nullptr; }
+
+// The extents handed down. The MFMA kernels want D = 64 or 128 (and, f32, whole tiles of 32 rows); everything else takes the generic
+// vector-ALU kernel (two orders of magnitude slower). Zero columns change neither Q K^T nor P V (the softmax scale stays 1 / sqrt(D) of
+// the real head size), so a 16-bit head size up to 128 is padded in every family; f32 is padded in the causal families only (the
+// exact-f32 MFMA kernels), and only there rows are padded, when Skv >= Sq > 0: a padded key n >= Skv >= Sq > m is above the diagonal
+// of every real query; a padded query has q = 0 and dO = 0, so it contributes exactly zero to dK and dV. The 16-bit kernels take any
+// sequence lengths themselves (rows beyond a tensor's end are zero-filled / dropped by their buffer descriptors).
+struct PadPlan { int64_t Sq, Skv, D; };
+PadPlan pad_plan(Family f, const Tensor &q, const Tensor &k) {
+    const int64_t Sq = q.shape(2), Skv = k.shape(2), D = q.shape(3);
+    PadPlan p{Sq, Skv, D};
+    if (f == Family::Full) {
+        if (h16(q.dtype()) && D != 64 && D <= 128) p.D = D < 64 ? 64 : 128;
+        return p;
+    }
+    if (!(D > 0 && D <= 128 && Skv >= Sq && Sq > 0) || !(h16(q.dtype()) || q.dtype() == ScalarType::Float)) return p;
+    const int64_t rows = h16(q.dtype()) ? 1 : 32;
+    return {(Sq + rows - 1) / rows * rows, (Skv + rows - 1) / rows * rows, D <= 64 ? 64 : 128};
+}
+bool same_extents(const Tensor &t, int64_t rows, int64_t cols) { return t.shape(2) == rows && (t.dim() == 3 || t.shape(3) == cols); }
+Tensor pad(const Tensor &t, int64_t rows, int64_t cols) { // [B,H,S,D] -> [B,H,rows,cols] (or [B,H,S] -> [B,H,rows]), zero-filled; t itself when nothing grows
+    if (same_extents(t, rows, cols)) return t;
+    auto shape = t.sizes();
+    shape[2] = rows;
+    if (shape.size() == 4) shape[3] = cols;
+    Tensor p = zeros(shape, t.dtype(), t.device());
+    Tensor head = p.narrow(2, 0, t.shape(2));
+    if (shape.size() == 4) head = head.narrow(3, 0, t.shape(3));
+    copy_(head, t);
+    return p;
+}
+Tensor unpad(const Tensor &t, int64_t rows, int64_t cols) {
+    if (same_extents(t, rows, cols)) return t;
+    Tensor v = t.narrow(2, 0, rows);
+    if (t.dim() == 4) v = v.narrow(3, 0, cols);
+    return v.dense();
+}
+
+Call contiguous_call(Family f, const Tensor &q, const Tensor &k, const PadPlan &pp, const Tensor &kv_len) {
+    const bool padded = pp.Sq != q.shape(2) || pp.Skv != k.shape(2) || pp.D != q.shape(3);
+    return {f, code(q.dtype()), q.device(), q.shape(0), q.shape(1), k.shape(1), pp.Sq, pp.Skv, pp.D, 1.0f / std::sqrt((float)q.shape(3)),
+            len_ptr(kv_len), nullptr, nullptr, padded};
+}
+
+std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len) {
+    const int64_t B = q.shape(0), Hq = q.shape(1), Sq = q.shape(2), D = q.shape(3);
+    if (f == Family::CausalGqa) {
+        if (q.numel() == 0) return {empty_like(q), empty({B, Hq, Sq}, ScalarType::Float, q.device())};
+        CHECK_FAIL(k.shape(2) > 0, "causal_attention_gqa: keys are empty");
+    }
+    const PadPlan pp = pad_plan(f, q, k);
+    Tensor qp = pad(q, pp.Sq, pp.D), kp = pad(k, pp.Skv, pp.D), vp = pad(v, pp.Skv, pp.D);
+    Tensor outp = empty_like(qp);
+    Tensor lsep = empty({B, Hq, pp.Sq}, ScalarType::Float, q.device());
+    run_fwd(contiguous_call(f, q, k, pp, kv_len), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), outp.data_ptr(), static_cast<float *>(lsep.data_ptr()));
+    return {unpad(outp, Sq, D), unpad(lsep, Sq, 0)};
+}
+
+std::tuple<Tensor, Tensor, Tensor> attention_backward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, const Tensor &out,
+                                                      const Tensor &lse, const Tensor &grad_out) {
+    if (f == Family::CausalMha) check_operands(f, q, k, v); // causal_attention_bwd is an operator of its own (ops.h)
+    CHECK_FAIL(grad_out.sizes() == q.sizes() && grad_out.dtype() == q.dtype(), f == Family::Full ? "attention: the gradient does not match the output" : "");
+    const int64_t Sq = q.shape(2), Skv = k.shape(2), D = q.shape(3);
+    if (f == Family::CausalGqa && (q.numel() == 0 || k.numel() == 0)) // nothing attends: every gradient is zero
+        return {zeros(q.sizes(), q.dtype(), q.device()), zeros(k.sizes(), k.dtype(), k.device()), zeros(v.sizes(), v.dtype(), v.device())};
+    const PadPlan pp = pad_plan(f, q, k);
+    Tensor qp = pad(q, pp.Sq, pp.D), kp = pad(k, pp.Skv, pp.D), vp = pad(v, pp.Skv, pp.D), op = pad(out, pp.Sq, pp.D);
+    Tensor lp = pad(lse, pp.Sq, 0), gp = pad(grad_out.dense(), pp.Sq, pp.D);
+    Tensor dqp = empty_like(qp), dkp = empty_like(kp), dvp = empty_like(vp);
+    if (f == Family::Full && dqp.numel() == 0) // no query: dk and dv are zero
+        return {unpad(dqp, Sq, D), unpad(zeros(kp.sizes(), k.dtype(), k.device()), Skv, D), unpad(zeros(vp.sizes(), v.dtype(), v.device()), Skv, D)};
+    const Call c = contiguous_call(f, q, k, pp, kv_len);
+    size_t bytes = 0;
+    DataPtr scratch = bwd_scratch(c, bytes);
+    run_bwd(c, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), static_cast<const float *>(lp.data_ptr()), gp.data_ptr(), dqp.data_ptr(),
+            dkp.data_ptr(), dvp.data_ptr(), scratch.get(), bytes);
+    return {unpad(dqp, Sq, D), unpad(dkp, Skv, D), unpad(dvp, Skv, D)};
+}
+
+class AttentionGradFunction : public GradFunction {
+public:
+    AttentionGradFunction(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, const Tensor &out, const Tensor &lse)
+        : family_(f), kv_len_(kv_len), out_(out), lse_(lse) {
+        inputs = {q, k, v};
+    }
+    std::vector<Tensor> backward(Tensor g) override {
+        auto [dq, dk, dv] = attention_backward(family_, inputs[0], inputs[1], inputs[2], kv_len_, out_, lse_, g);
+        return {dq, dk, dv};
+    }
+
+private:
+    Family family_;
+    Tensor kv_len_, out_, lse_;
+};
+
+// kv_len is checked and made dense once; the backward keeps that tensor
+Tensor contiguous_attention(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len) {
+    check_operands(f, q, k, v);
+    const Tensor len = check_len(kv_len, q.shape(0), q.device());
+    auto [out, lse] = attention_forward(f, q, k, v, len);
+    out.set_requires_grad(q.requires_grad() || k.requires_grad() || v.requires_grad());
+    if (out.requires_grad()) out.set_grad_fn(new AttentionGradFunction(f, q, k, v, len, out, lse));
+    return out;
+}
+
+// ---- the packed QKV projection (README.md:32), read in place: [B*S, W], W = (H + 2 Hkv) D, columns q | k | v; the output is [B*S, H D] ----
+struct PackedLay { kf_attn_layout qkv, flat; };
+PackedLay packed_layouts(int64_t S, int64_t H, int64_t Hkv, int64_t D) {
+    const int64_t d = H * D, W = (H + 2 * Hkv) * D;
+    return {{S * W, D, W}, {S * d, D, d}};
+}
+// family CausalMha is Hkv = H here: K at column H D, V at 2 H D (the strided entries); otherwise K at H D, V at (H + Hkv) D
+Call packed_call(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D, const PackedLay &L, const Tensor &kv_len) {
+    return {f, code(qkv.dtype()), qkv.device(), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), len_ptr(kv_len), &L.qkv, &L.flat, false};
+}
+
+class PackedAttentionGradFunction : public GradFunction {
+public:
+    PackedAttentionGradFunction(Family f, const Tensor &qkv, const Tensor &kv_len, const Tensor &out, const Tensor &lse, int64_t B, int64_t S, int64_t H,
+                                int64_t Hkv)
+        : family_(f), kv_len_(kv_len), out_(out), lse_(lse), B_(B), S_(S), H_(H), Hkv_(Hkv) {
+        inputs = {qkv};
+    }
+    std::vector<Tensor> backward(Tensor g) override { // one packed gradient; dk, dv summed over each group
+        const Tensor &qkv = inputs[0];
+        const int64_t D = qkv.shape(1) / (H_ + 2 * Hkv_), es = qkv.element_size_in_bytes(), k_at = H_ * D * es, v_at = (H_ + Hkv_) * D * es;
+        Tensor gc = g.dense();
+        Tensor dqkv = empty(qkv.sizes(), qkv.dtype(), qkv.device());
+        const PackedLay L = packed_layouts(S_, H_, Hkv_, D);
+        const Call c = packed_call(family_, qkv, B_, S_, H_, Hkv_, D, L, kv_len_);
+        const char *p = static_cast<const char *>(qkv.data_ptr());
+        char *gp = static_cast<char *>(dqkv.data_ptr());
+        size_t bytes = 0;
+        DataPtr scratch = bwd_scratch(c, bytes);
+        run_bwd(c, p, p + k_at, p + v_at, out_.data_ptr(), static_cast<const float *>(lse_.data_ptr()), gc.data_ptr(), gp, gp + k_at, gp + v_at,
+                scratch.get(), bytes);
+        return {dqkv};
+    }
+
+private:
+    Family family_;
+    Tensor kv_len_, out_, lse_;
+    int64_t B_, S_, H_, Hkv_;
+};
+
+// f: CausalMha for causal_attention_qkv(qkv, B, S, H) (Hkv = H, the [B*S, 3*H*D] texts), CausalGqa for its kv_heads form, Full for attention_qkv
+Tensor packed_attention(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, const Tensor &kv_len) {
+    const char *op = f == Family::Full ? "attention_qkv" : "causal_attention_qkv";
+    CHECK_FAIL(qkv.defined() && qkv.dim() == 2 && qkv.is_dense(), op,
+               f == Family::CausalMha ? " expects a contiguous [B*S, 3*H*D] tensor" : " expects a contiguous [B*S, (H + 2*kv_heads)*D] tensor");
+    if (f == Family::CausalMha) {
+        CHECK_FAIL(B > 0 && S > 0 && H > 0 && qkv.shape(0) == B * S && qkv.shape(1) % (3 * H) == 0, "causal_attention_qkv: shape does not match B, S, H");
+    } else {
+        CHECK_FAIL(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, op, ": kv_heads ", Hkv, " must divide H ", H);
+        CHECK_FAIL(qkv.shape(0) == B * S && (f != Family::Full || qkv.shape(1) > 0) && qkv.shape(1) % (H + 2 * Hkv) == 0, op,
+                   ": shape does not match B, S, H, kv_heads");
+    }
+    const int64_t D = qkv.shape(1) / (H + 2 * Hkv), d = H * D, dkv = Hkv * D;
+    if (!(h16(qkv.dtype()) && (D == 64 || D == 128))) {
+        // off the strided kernels' shapes: split heads and the contiguous operator of the family (which carries its own autograd)
+        auto parts = tensor_split(qkv, {d, dkv, dkv}, 1);
+        const int64_t nh[3] = {H, Hkv, Hkv};
+        std::vector<Tensor> heads;
+        for (int i = 0; i < 3; ++i) heads.push_back(parts[i].dense().view({B, S, nh[i], D}).permute({0, 2, 1, 3}).dense());
+        Tensor a = contiguous_attention(f, heads[0], heads[1], heads[2], kv_len);
+        return a.permute({0, 2, 1, 3}).dense().view({B * S, d});
+    }
+    const Tensor len = check_len(kv_len, B, qkv.device());
+    const int64_t es = qkv.element_size_in_bytes();
+    Tensor out = empty({B * S, d}, qkv.dtype(), qkv.device());
+    Tensor lse = empty({B, H, S}, ScalarType::Float, qkv.device());
+    const PackedLay L = packed_layouts(S, H, Hkv, D);
+    const char *p = static_cast<const char *>(qkv.data_ptr());
+    run_fwd(packed_call(f, qkv, B, S, H, Hkv, D, L, len), p, p + d * es, p + (d + dkv) * es, out.data_ptr(), static_cast<float *>(lse.data_ptr()));
+    if (qkv.requires_grad()) {
+        out.set_requires_grad(true);
+        out.set_grad_fn(new PackedAttentionGradFunction(f, qkv, len, out, lse, B, S, H, Hkv));
+    }
+    return out;
+}
+
+} // namespace
+
+std::tuple<Tensor, Tensor> causal_attention_fwd(const Tensor &q, const Tensor &k, const Tensor &v) {
+    check_operands(Family::CausalMha, q, k, v);
+    return attention_forward(Family::CausalMha, q, k, v, Tensor());
+}
+std::tuple<Tensor, Tensor, Tensor> causal_attention_bwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse,
+                                                        const Tensor &grad_out) {
+    return attention_backward(Family::CausalMha, q, k, v, Tensor(), out, lse, grad_out);
+}
+Tensor causal_attention(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalMha, q, k, v, Tensor()); }
+Tensor causal_attention_gqa(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalGqa, q, k, v, Tensor()); }
+Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len) { return contiguous_attention(Family::Full, q, k, v, kv_len); }
+
+Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H) { return packed_attention(Family::CausalMha, qkv, B, S, H, H, Tensor()); }
+Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads) {
+    if (kv_heads >= 0 && kv_heads != H) return packed_attention(Family::CausalGqa, qkv, B, S, H, kv_heads, Tensor());
+    return causal_attention_qkv(qkv, B, S, H);
+}
+Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len) {
+    return packed_attention(Family::Full, qkv, B, S, H, kv_heads < 0 ? H : kv_heads, kv_len);
+}
+
+} // namespace gpu

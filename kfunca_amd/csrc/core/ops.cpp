@@ -720,246 +720,6 @@ Tensor gemm_ex(const Tensor &a, bool trans_a, const Tensor &b, bool trans_b, flo
     return out;
 }
 
-// ---- causal attention (nn_ops.cpp:6-8 + the checks of causal_attention_kernel.cu:9-20) ---------------------
-namespace {
-
-void check_attention(const Tensor &q, const Tensor &k, const Tensor &v) {
-    CHECK_FAIL(q.dim() == 4 && k.dim() == 4 && v.dim() == 4);
-    CHECK_FAIL(k.shape(0) == q.shape(0) && k.shape(1) == q.shape(1) && k.shape(3) == q.shape(3));
-    CHECK_FAIL(k.sizes() == v.sizes());
-    CHECK_FAIL(q.dtype() == k.dtype() && q.dtype() == v.dtype());
-    CHECK_FAIL(q.dtype() == ScalarType::Float || q.dtype() == ScalarType::Half || q.dtype() == ScalarType::BFloat16,
-               "Unsupported ScalarType ", q.dtype());
-    CHECK_FAIL(q.is_dense() && k.is_dense() && v.is_dense());
-    CHECK_FAIL(q.device() == k.device() && q.device() == v.device());
-}
-
-// The MFMA kernels want D = 64 or 128 (and, f32 or Skv < Sq, whole tiles of rows); everything else takes the generic
-// vector-ALU kernel (two orders of magnitude slower). For 16-bit tensors with D <= 128 and Skv >= Sq both can be padded
-// with zeros at no cost in results: zero columns change neither Q K^T nor P V (the softmax scale stays 1 / sqrt(D) of the
-// real head size: kf_attn_*_scaled); a padded key n >= Skv >= Sq > m is above the diagonal of every real query; a padded
-// query has q = 0 and dO = 0, so it contributes exactly zero to dK and dV.
-// The same holds for f32 tensors and the exact-f32 MFMA kernels (head size 64 or 128, rows in multiples of 32).
-struct PadPlan {
-    bool pad = false;
-    int64_t Sqp = 0, Skp = 0, Dp = 0;
-};
-PadPlan pad_for_mfma(const Tensor &q, const Tensor &k) {
-    const int64_t Sq = q.shape(2), Skv = k.shape(2), D = q.shape(3);
-    PadPlan p;
-    if (!(D > 0 && D <= 128 && Skv >= Sq && Sq > 0)) return p;
-    const bool h16 = q.dtype() == ScalarType::Half || q.dtype() == ScalarType::BFloat16;
-    if (!h16 && q.dtype() != ScalarType::Float) return p;
-    // round 6: the 16-bit matrix-core kernels take ANY sequence lengths with Skv >= Sq at the C ABI itself (rows beyond a tensor's end are
-    // zero-filled / dropped by the kernels' buffer descriptors - no padded copies); only a head size off 64 / 128 is still padded here
-    const int64_t rows = h16 ? 1 : 32;
-    p.Dp = D <= 64 ? 64 : 128;
-    p.Sqp = (Sq + rows - 1) / rows * rows;
-    p.Skp = (Skv + rows - 1) / rows * rows;
-    p.pad = p.Dp != D || p.Sqp != Sq || p.Skp != Skv;
-    return p;
-}
-Tensor pad_to(const Tensor &t, int64_t rows, int64_t cols) { // [B,H,S,D] -> [B,H,rows,cols] (or [B,H,S] -> [B,H,rows]), zero-filled
-    auto shape = t.sizes();
-    const int64_t S = shape[2];
-    shape[2] = rows;
-    if (shape.size() == 4) shape[3] = cols;
-    Tensor p = zeros(shape, t.dtype(), t.device());
-    Tensor head = p.narrow(2, 0, S);
-    if (shape.size() == 4) head = head.narrow(3, 0, t.shape(3));
-    copy_(head, t);
-    return p;
-}
-Tensor unpad(const Tensor &t, int64_t rows, int64_t cols) {
-    Tensor v = t.narrow(2, 0, rows);
-    if (t.dim() == 4) v = v.narrow(3, 0, cols);
-    return v.dense();
-}
-
-class AttentionGradFunction : public GradFunction {
-public:
-    AttentionGradFunction(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse) : out_(out), lse_(lse) {
-        inputs = {q, k, v};
-    }
-    std::vector<Tensor> backward(Tensor g) override {
-        auto [dq, dk, dv] = causal_attention_bwd(inputs[0], inputs[1], inputs[2], out_, lse_, g);
-        return {dq, dk, dv};
-    }
-
-private:
-    Tensor out_, lse_;
-};
-
-} // namespace
-
-std::tuple<Tensor, Tensor> causal_attention_fwd(const Tensor &q, const Tensor &k, const Tensor &v) {
-    check_attention(q, k, v);
-    const int64_t B = q.shape(0), H = q.shape(1), Sq = q.shape(2), D = q.shape(3), Skv = k.shape(2);
-    if (const PadPlan pp = pad_for_mfma(q, k); pp.pad) {
-        const int64_t Sqp = pp.Sqp, Skp = pp.Skp, Dp = pp.Dp;
-        Tensor qp = pad_to(q, Sqp, Dp), kp = pad_to(k, Skp, Dp), vp = pad_to(v, Skp, Dp);
-        Tensor outp = empty_like(qp);
-        Tensor lsep = empty({B, H, Sqp}, ScalarType::Float, q.device());
-        DEV_CALL(kf_attn_fwd_scaled(code(q.dtype()), B, H, Sqp, Skp, Dp, 1.0f / std::sqrt((float)D), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(),
-                                    outp.data_ptr(), static_cast<float *>(lsep.data_ptr()), dev::stream(q.device())));
-        return {unpad(outp, Sq, D), unpad(lsep, Sq, 0)};
-    }
-    Tensor out = empty_like(q);
-    Tensor lse = empty({B, H, Sq}, ScalarType::Float, q.device());
-    DEV_CALL(kf_attn_fwd(code(q.dtype()), B, H, Sq, Skv, D, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                         static_cast<float *>(lse.data_ptr()), dev::stream(q.device())));
-    return {out, lse};
-}
-
-// Backward scratch: the size the device library recommends (statistics + dS of as many (batch, head) pairs as its cap allows); when
-// the allocator cannot supply that, halve the part above `floor_` (the dS part) until it can - the library accepts anything down to
-// its minimum (then the recomputing dQ kernel runs: kf_attn_bwd, include/kfunca_hip.h).
-static DataPtr alloc_shrinking(size_t need, size_t floor_, int device, size_t &bytes) {
-    for (;;) {
-        try {
-            bytes = need;
-            return DeviceAllocator::GetInstance()->allocate(need, device);
-        } catch (const utils::OutOfMemory &) { // only that: any other failure is not cured by asking for less
-            if (need <= floor_) throw;
-            need = floor_ + (need - floor_) / 2;
-            if (need - floor_ < ((size_t)1 << 20)) need = floor_;
-        }
-    }
-}
-static DataPtr attn_bwd_scratch(int dt, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t D, int device, size_t &bytes) {
-    size_t need = 0;
-    DEV_CALL(kf_attn_bwd_workspace_bytes(dt, B, H, Sq, Skv, D, &need));
-    return alloc_shrinking(need, 3 * (((size_t)B * H * Sq * sizeof(float) + 255) / 256 * 256), device, bytes);
-}
-
-std::tuple<Tensor, Tensor, Tensor> causal_attention_bwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out,
-                                                        const Tensor &lse, const Tensor &grad_out) {
-    check_attention(q, k, v);
-    CHECK_FAIL(grad_out.sizes() == q.sizes() && grad_out.dtype() == q.dtype());
-    const int64_t B = q.shape(0), H = q.shape(1), Sq = q.shape(2), D = q.shape(3), Skv = k.shape(2);
-    if (const PadPlan pp = pad_for_mfma(q, k); pp.pad) {
-        const int64_t Sqp = pp.Sqp, Skp = pp.Skp, Dp = pp.Dp;
-        Tensor qp = pad_to(q, Sqp, Dp), kp = pad_to(k, Skp, Dp), vp = pad_to(v, Skp, Dp), op = pad_to(out, Sqp, Dp);
-        Tensor lp = pad_to(lse, Sqp, 0), gp = pad_to(grad_out.dense(), Sqp, Dp);
-        Tensor dqp = empty_like(qp), dkp = empty_like(kp), dvp = empty_like(vp);
-        size_t need = 0;
-        DataPtr scratch = attn_bwd_scratch(code(q.dtype()), B, H, Sqp, Skp, Dp, q.device(), need);
-        DEV_CALL(kf_attn_bwd_scaled(code(q.dtype()), B, H, Sqp, Skp, Dp, 1.0f / std::sqrt((float)D), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(),
-                                    op.data_ptr(), static_cast<const float *>(lp.data_ptr()), gp.data_ptr(), dqp.data_ptr(), dkp.data_ptr(),
-                                    dvp.data_ptr(), scratch.get(), need, dev::stream(q.device())));
-        return {unpad(dqp, Sq, D), unpad(dkp, Skv, D), unpad(dvp, Skv, D)};
-    }
-    Tensor go = grad_out.dense();
-    Tensor dq = empty_like(q), dk = empty_like(k), dv = empty_like(v);
-    size_t need = 0;
-    DataPtr scratch = attn_bwd_scratch(code(q.dtype()), B, H, Sq, Skv, D, q.device(), need);
-    DEV_CALL(kf_attn_bwd(code(q.dtype()), B, H, Sq, Skv, D, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                         static_cast<const float *>(lse.data_ptr()), go.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                         scratch.get(), need, dev::stream(q.device())));
-    return {dq, dk, dv};
-}
-
-Tensor causal_attention(const Tensor &q, const Tensor &k, const Tensor &v) {
-    auto [out, lse] = causal_attention_fwd(q, k, v);
-    out.set_requires_grad(q.requires_grad() || k.requires_grad() || v.requires_grad());
-    if (out.requires_grad()) out.set_grad_fn(new AttentionGradFunction(q, k, v, out, lse));
-    return out;
-}
-
-// ---- grouped-query attention: q [B, Hq, Sq, D], k and v [B, Hkv, Skv, D], query head h reads K/V head h / (Hq / Hkv) (kf_attn_*_gqa) ----
-namespace {
-void check_attention_gqa(const Tensor &q, const Tensor &k, const Tensor &v) {
-    CHECK_FAIL(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "causal_attention_gqa expects q [B, Hq, Sq, D] and k, v [B, Hkv, Skv, D]");
-    CHECK_FAIL(k.shape(0) == q.shape(0) && k.shape(3) == q.shape(3) && k.sizes() == v.sizes(), "causal_attention_gqa: shapes of q, k, v do not match");
-    CHECK_FAIL(k.shape(1) >= 1 && k.shape(1) <= q.shape(1) && q.shape(1) % k.shape(1) == 0, "causal_attention_gqa: the K/V head count ", k.shape(1),
-               " must divide the query head count ", q.shape(1));
-    CHECK_FAIL(q.dtype() == k.dtype() && q.dtype() == v.dtype(), "causal_attention_gqa: q, k, v must share a dtype");
-    CHECK_FAIL(q.dtype() == ScalarType::Float || q.dtype() == ScalarType::Half || q.dtype() == ScalarType::BFloat16, "Unsupported ScalarType ", q.dtype());
-    CHECK_FAIL(q.is_dense() && k.is_dense() && v.is_dense(), "causal_attention_gqa expects dense tensors");
-    CHECK_FAIL(q.device() == k.device() && q.device() == v.device(), "causal_attention_gqa: q, k, v must be on one device");
-}
-
-// as attn_bwd_scratch, with the GQA workspace query: the library's minimum (statistics + the dK / dV partials) is the floor of the OOM retries
-DataPtr attn_bwd_gqa_scratch(int dt, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, int device, size_t &bytes) {
-    size_t need = 0, floor_ = 0;
-    DEV_CALL(kf_attn_bwd_gqa_workspace_bytes(dt, B, Hq, Hkv, Sq, Skv, D, &need, &floor_));
-    return alloc_shrinking(need, floor_, device, bytes);
-}
-
-std::tuple<Tensor, Tensor> causal_attention_gqa_fwd(const Tensor &q, const Tensor &k, const Tensor &v) {
-    const int64_t B = q.shape(0), Hq = q.shape(1), Sq = q.shape(2), D = q.shape(3), Hkv = k.shape(1), Skv = k.shape(2);
-    const float scale = 1.0f / std::sqrt((float)D);
-    if (q.numel() == 0) return {empty_like(q), empty({B, Hq, Sq}, ScalarType::Float, q.device())};
-    CHECK_FAIL(Skv > 0, "causal_attention_gqa: keys are empty");
-    if (const PadPlan pp = pad_for_mfma(q, k); pp.pad) { // as causal_attention_fwd: zero-padded head size (and f32 rows) keep the MFMA kernels
-        const int64_t Sqp = pp.Sqp, Skp = pp.Skp, Dp = pp.Dp;
-        Tensor qp = pad_to(q, Sqp, Dp), kp = pad_to(k, Skp, Dp), vp = pad_to(v, Skp, Dp);
-        Tensor outp = empty_like(qp);
-        Tensor lsep = empty({B, Hq, Sqp}, ScalarType::Float, q.device());
-        DEV_CALL(kf_attn_fwd_gqa(code(q.dtype()), B, Hq, Hkv, Sqp, Skp, Dp, scale, qp.data_ptr(), nullptr, kp.data_ptr(), nullptr, vp.data_ptr(), nullptr,
-                                 outp.data_ptr(), nullptr, static_cast<float *>(lsep.data_ptr()), dev::stream(q.device())));
-        return {unpad(outp, Sq, D), unpad(lsep, Sq, 0)};
-    }
-    Tensor out = empty_like(q);
-    Tensor lse = empty({B, Hq, Sq}, ScalarType::Float, q.device());
-    DEV_CALL(kf_attn_fwd_gqa(code(q.dtype()), B, Hq, Hkv, Sq, Skv, D, scale, q.data_ptr(), nullptr, k.data_ptr(), nullptr, v.data_ptr(), nullptr,
-                             out.data_ptr(), nullptr, static_cast<float *>(lse.data_ptr()), dev::stream(q.device())));
-    return {out, lse};
-}
-
-std::tuple<Tensor, Tensor, Tensor> causal_attention_gqa_bwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse,
-                                                            const Tensor &grad_out) {
-    CHECK_FAIL(grad_out.sizes() == q.sizes() && grad_out.dtype() == q.dtype());
-    const int64_t B = q.shape(0), Hq = q.shape(1), Sq = q.shape(2), D = q.shape(3), Hkv = k.shape(1), Skv = k.shape(2);
-    const float scale = 1.0f / std::sqrt((float)D);
-    if (q.numel() == 0 || k.numel() == 0) // nothing attends: every gradient is zero
-        return {zeros(q.sizes(), q.dtype(), q.device()), zeros(k.sizes(), k.dtype(), k.device()), zeros(v.sizes(), v.dtype(), v.device())};
-    const int dt = code(q.dtype());
-    void *st = dev::stream(q.device());
-    size_t need = 0;
-    if (const PadPlan pp = pad_for_mfma(q, k); pp.pad) {
-        const int64_t Sqp = pp.Sqp, Skp = pp.Skp, Dp = pp.Dp;
-        Tensor qp = pad_to(q, Sqp, Dp), kp = pad_to(k, Skp, Dp), vp = pad_to(v, Skp, Dp), op = pad_to(out, Sqp, Dp);
-        Tensor lp = pad_to(lse, Sqp, 0), gp = pad_to(grad_out.dense(), Sqp, Dp);
-        Tensor dqp = empty_like(qp), dkp = empty_like(kp), dvp = empty_like(vp);
-        DataPtr scratch = attn_bwd_gqa_scratch(dt, B, Hq, Hkv, Sqp, Skp, Dp, q.device(), need);
-        DEV_CALL(kf_attn_bwd_gqa(dt, B, Hq, Hkv, Sqp, Skp, Dp, scale, qp.data_ptr(), nullptr, kp.data_ptr(), nullptr, vp.data_ptr(), nullptr, op.data_ptr(),
-                                 nullptr, static_cast<const float *>(lp.data_ptr()), gp.data_ptr(), nullptr, dqp.data_ptr(), nullptr, dkp.data_ptr(), nullptr,
-                                 dvp.data_ptr(), nullptr, scratch.get(), need, st));
-        return {unpad(dqp, Sq, D), unpad(dkp, Skv, D), unpad(dvp, Skv, D)};
-    }
-    Tensor go = grad_out.dense();
-    Tensor dq = empty_like(q), dk = empty_like(k), dv = empty_like(v);
-    DataPtr scratch = attn_bwd_gqa_scratch(dt, B, Hq, Hkv, Sq, Skv, D, q.device(), need);
-    DEV_CALL(kf_attn_bwd_gqa(dt, B, Hq, Hkv, Sq, Skv, D, scale, q.data_ptr(), nullptr, k.data_ptr(), nullptr, v.data_ptr(), nullptr, out.data_ptr(), nullptr,
-                             static_cast<const float *>(lse.data_ptr()), go.data_ptr(), nullptr, dq.data_ptr(), nullptr, dk.data_ptr(), nullptr, dv.data_ptr(),
-                             nullptr, scratch.get(), need, st));
-    return {dq, dk, dv};
-}
-
-class GqaAttentionGradFunction : public GradFunction {
-public:
-    GqaAttentionGradFunction(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse) : out_(out), lse_(lse) {
-        inputs = {q, k, v};
-    }
-    std::vector<Tensor> backward(Tensor g) override {
-        auto [dq, dk, dv] = causal_attention_gqa_bwd(inputs[0], inputs[1], inputs[2], out_, lse_, g);
-        return {dq, dk, dv};
-    }
-
-private:
-    Tensor out_, lse_;
-};
-} // namespace
-
-Tensor causal_attention_gqa(const Tensor &q, const Tensor &k, const Tensor &v) {
-    check_attention_gqa(q, k, v);
-    auto [out, lse] = causal_attention_gqa_fwd(q, k, v);
-    out.set_requires_grad(q.requires_grad() || k.requires_grad() || v.requires_grad());
-    if (out.requires_grad()) out.set_grad_fn(new GqaAttentionGradFunction(q, k, v, out, lse));
-    return out;
-}
-
 // ---- index_put_ (index_ops.cpp:6-38) ----------------------------------------------------------------------------
 Tensor &index_put_(Tensor &self, const std::vector<Tensor> &indices, const Tensor &values) {
     CHECK_FAIL((int)indices.size() == self.dim(), "Number of indices must match the number of dimensions in the tensor.");
@@ -992,114 +752,6 @@ Tensor &index_put_(Tensor &self, const std::vector<Tensor> &indices, const Tenso
         DEV_CALL(kf_index_put(&d, (int)sizes.size(), sizes.data(), strides.data(), stream));
     });
     return self;
-}
-
-// ---- attention on the packed QKV projection (README.md:32) ---------------------------------------------------------------------
-namespace {
-struct PackedLay { kf_attn_layout qkv, flat; };
-PackedLay packed_layouts(int64_t S, int64_t H, int64_t Hkv, int64_t D) { // the projection [B*S, W], W = (H + 2 Hkv) D; the output [B*S, H D]
-    const int64_t d = H * D, W = (H + 2 * Hkv) * D;
-    return {{S * W, D, W}, {S * d, D, d}};
-}
-bool packed_fast(const Tensor &qkv, int64_t S, int64_t D) {
-    return (qkv.dtype() == ScalarType::Half || qkv.dtype() == ScalarType::BFloat16) && (D == 64 || D == 128) && S > 0;   // (any S since round 6: Sq == Skv)
-}
-
-class PackedAttentionGradFunction : public GradFunction {
-public:
-    PackedAttentionGradFunction(const Tensor &qkv, const Tensor &out, const Tensor &lse, int64_t B, int64_t S, int64_t H, int64_t Hkv)
-        : out_(out), lse_(lse), B_(B), S_(S), H_(H), Hkv_(Hkv) {
-        inputs = {qkv};
-    }
-    std::vector<Tensor> backward(Tensor g) override {
-        const Tensor &qkv = inputs[0];
-        const int64_t D = qkv.shape(1) / (H_ + 2 * Hkv_), d = H_ * D;
-        const int es = (int)qkv.element_size_in_bytes();
-        Tensor gc = g.dense();
-        Tensor dqkv = empty(qkv.sizes(), qkv.dtype(), qkv.device());
-        const PackedLay L = packed_layouts(S_, H_, Hkv_, D);
-        size_t need = 0;
-        const char *p = static_cast<const char *>(qkv.data_ptr());
-        char *gp = static_cast<char *>(dqkv.data_ptr());
-        if (Hkv_ != H_) { // grouped-query attention: k at column H D, v at (H + Hkv) D; dk, dv summed over each group into the packed gradient
-            const int64_t dkv = (H_ + Hkv_) * D;
-            DataPtr scratch = attn_bwd_gqa_scratch(code(qkv.dtype()), B_, H_, Hkv_, S_, S_, D, qkv.device(), need);
-            DEV_CALL(kf_attn_bwd_gqa(code(qkv.dtype()), B_, H_, Hkv_, S_, S_, D, 1.0f / std::sqrt((float)D), p, &L.qkv, p + d * es, &L.qkv, p + dkv * es,
-                                     &L.qkv, out_.data_ptr(), &L.flat, static_cast<const float *>(lse_.data_ptr()), gc.data_ptr(), &L.flat, gp, &L.qkv,
-                                     gp + d * es, &L.qkv, gp + dkv * es, &L.qkv, scratch.get(), need, dev::stream(qkv.device())));
-            return {dqkv};
-        }
-        DataPtr scratch = attn_bwd_scratch(code(qkv.dtype()), B_, H_, S_, S_, D, qkv.device(), need);
-        DEV_CALL(kf_attn_bwd_strided(code(qkv.dtype()), B_, H_, S_, S_, D, 1.0f / std::sqrt((float)D), p, &L.qkv, p + d * es, &L.qkv, p + 2 * d * es,
-                                     &L.qkv, out_.data_ptr(), &L.flat, static_cast<const float *>(lse_.data_ptr()), gc.data_ptr(), &L.flat, gp, &L.qkv,
-                                     gp + d * es, &L.qkv, gp + 2 * d * es, &L.qkv, scratch.get(), need, dev::stream(qkv.device())));
-        return {dqkv};
-    }
-
-private:
-    Tensor out_, lse_;
-    int64_t B_, S_, H_, Hkv_;
-};
-
-// causal_attention_qkv with Hkv < H K/V heads: the packed [B*S, (H + 2 Hkv) D] projection that rope_qkv(kv_heads = Hkv) rotates
-Tensor causal_attention_qkv_gqa(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv) {
-    CHECK_FAIL(qkv.defined() && qkv.dim() == 2 && qkv.is_dense(), "causal_attention_qkv expects a contiguous [B*S, (H + 2*kv_heads)*D] tensor");
-    CHECK_FAIL(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "causal_attention_qkv: kv_heads ", Hkv, " must divide H ", H);
-    CHECK_FAIL(qkv.shape(0) == B * S && qkv.shape(1) % (H + 2 * Hkv) == 0, "causal_attention_qkv: shape does not match B, S, H, kv_heads");
-    const int64_t D = qkv.shape(1) / (H + 2 * Hkv), d = H * D, dkv = Hkv * D;
-    if (!packed_fast(qkv, S, D)) {
-        // off the strided kernels' shapes: split heads and the contiguous GQA operator (which carries its own autograd)
-        auto parts = tensor_split(qkv, {d, dkv, dkv}, 1);
-        const int64_t nh[3] = {H, Hkv, Hkv};
-        std::vector<Tensor> heads;
-        for (int i = 0; i < 3; ++i) heads.push_back(parts[i].dense().view({B, S, nh[i], D}).permute({0, 2, 1, 3}).dense());
-        Tensor a = causal_attention_gqa(heads[0], heads[1], heads[2]);
-        return a.permute({0, 2, 1, 3}).dense().view({B * S, d});
-    }
-    const int es = (int)qkv.element_size_in_bytes();
-    Tensor out = empty({B * S, d}, qkv.dtype(), qkv.device());
-    Tensor lse = empty({B, H, S}, ScalarType::Float, qkv.device());
-    const PackedLay L = packed_layouts(S, H, Hkv, D);
-    const char *p = static_cast<const char *>(qkv.data_ptr());
-    DEV_CALL(kf_attn_fwd_gqa(code(qkv.dtype()), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), p, &L.qkv, p + d * es, &L.qkv, p + (d + dkv) * es, &L.qkv,
-                             out.data_ptr(), &L.flat, static_cast<float *>(lse.data_ptr()), dev::stream(qkv.device())));
-    if (qkv.requires_grad()) {
-        out.set_requires_grad(true);
-        out.set_grad_fn(new PackedAttentionGradFunction(qkv, out, lse, B, S, H, Hkv));
-    }
-    return out;
-}
-} // namespace
-
-Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads) {
-    if (kv_heads >= 0 && kv_heads != H) return causal_attention_qkv_gqa(qkv, B, S, H, kv_heads);
-    return causal_attention_qkv(qkv, B, S, H);
-}
-
-Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H) {
-    CHECK_FAIL(qkv.defined() && qkv.dim() == 2 && qkv.is_dense(), "causal_attention_qkv expects a contiguous [B*S, 3*H*D] tensor");
-    CHECK_FAIL(B > 0 && S > 0 && H > 0 && qkv.shape(0) == B * S && qkv.shape(1) % (3 * H) == 0, "causal_attention_qkv: shape does not match B, S, H");
-    const int64_t d = qkv.shape(1) / 3, D = d / H;
-    if (!packed_fast(qkv, S, D)) {
-        // off the strided kernels' shapes: the same result from the reference's own operators (which carry their own autograd)
-        auto parts = tensor_split(qkv, {d, d, d}, 1);
-        std::vector<Tensor> heads;
-        for (auto &t : parts) heads.push_back(t.dense().view({B, S, H, D}).permute({0, 2, 1, 3}).dense());
-        Tensor a = causal_attention(heads[0], heads[1], heads[2]);
-        return a.permute({0, 2, 1, 3}).dense().view({B * S, d});
-    }
-    const int es = (int)qkv.element_size_in_bytes();
-    Tensor out = empty({B * S, d}, qkv.dtype(), qkv.device());
-    Tensor lse = empty({B, H, S}, ScalarType::Float, qkv.device());
-    const PackedLay L = packed_layouts(S, H, H, D);
-    const char *p = static_cast<const char *>(qkv.data_ptr());
-    DEV_CALL(kf_attn_fwd_strided(code(qkv.dtype()), B, H, S, S, D, 1.0f / std::sqrt((float)D), p, &L.qkv, p + d * es, &L.qkv, p + 2 * d * es, &L.qkv,
-                                 out.data_ptr(), &L.flat, static_cast<float *>(lse.data_ptr()), dev::stream(qkv.device())));
-    if (qkv.requires_grad()) {
-        out.set_requires_grad(true);
-        out.set_grad_fn(new PackedAttentionGradFunction(qkv, out, lse, B, S, H, H));
-    }
-    return out;
 }
 
 // ---- rms_norm / layer_norm (README.md:28; statistics as norm_ops_kernel.cu:6-61 / welford_norm.h:170-187) ---------------------
