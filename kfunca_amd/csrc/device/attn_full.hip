@@ -29,7 +29,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "float_pack.h"
 
 namespace kf {
 namespace full {
@@ -704,13 +704,6 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a)
 // ==========================================================================================
 // generic path: contiguous tensors, one workgroup of 256 threads per output row, 256 partners per step
 // ==========================================================================================
-template <typename T> __device__ __forceinline__ float g_ld(const T *p) { return (float)*p; }
-template <> __device__ __forceinline__ float g_ld<bf16_t>(const bf16_t *p) { return bf16_to_f32(*p); }
-template <> __device__ __forceinline__ float g_ld<f16_t>(const f16_t *p) { return f16_to_f32(*p); }
-template <typename T> __device__ __forceinline__ void g_st(T *p, float v) { *p = (T)v; }
-template <> __device__ __forceinline__ void g_st<bf16_t>(bf16_t *p, float v) { *p = f32_to_bf16(v); }
-template <> __device__ __forceinline__ void g_st<f16_t>(f16_t *p, float v) { *p = f32_to_f16(v); }
-
 template <bool MAX>
 __device__ __forceinline__ float g_block_reduce(float v, float *red) { // every thread gets the result; red: 4 floats, reusable after return
     for (int msk = 32; msk > 0; msk >>= 1) {
@@ -732,7 +725,7 @@ __global__ __launch_bounds__(NT) void attn_full_fwd_generic_kernel(const FullArg
     const T *Q = (const T *)a.q + (bh * a.Sq + m) * D;
     const T *K = (const T *)a.k + (b * a.Hkv + g) * a.Skv * D;
     const T *V = (const T *)a.v + (b * a.Hkv + g) * a.Skv * D;
-    if (tid < D) qs[tid] = g_ld(Q + tid);
+    if (tid < D) qs[tid] = load_f32(Q + tid);
     __syncthreads();
     float acc = 0.f, mrun = -INFINITY, lrun = 0.f;
     for (int64_t c0 = 0; c0 < len; c0 += NT) {
@@ -740,7 +733,7 @@ __global__ __launch_bounds__(NT) void attn_full_fwd_generic_kernel(const FullArg
         float s = -INFINITY;
         if (n < len) {
             float dot = 0.f;
-            for (int d = 0; d < D; ++d) dot += qs[d] * g_ld(K + n * D + d);
+            for (int d = 0; d < D; ++d) dot += qs[d] * load_f32(K + n * D + d);
             s = dot * a.scale;
         }
         const float mnew = fmaxf(mrun, g_block_reduce<true>(s, red)); // finite: key c0 exists
@@ -750,13 +743,13 @@ __global__ __launch_bounds__(NT) void attn_full_fwd_generic_kernel(const FullArg
         if (tid < D) {
             const int cnt = (int)(len - c0 < NT ? len - c0 : NT);
             float t = 0.f;
-            for (int j = 0; j < cnt; ++j) t += ps[j] * g_ld(V + (c0 + j) * D + tid);
+            for (int j = 0; j < cnt; ++j) t += ps[j] * load_f32(V + (c0 + j) * D + tid);
             acc = acc * alpha + t;
         }
         mrun = mnew;
         __syncthreads();
     }
-    if (tid < D) g_st((T *)a.out + (bh * a.Sq + m) * D + tid, lrun > 0.f ? acc / lrun : 0.f);
+    if (tid < D) store_canonical((T *)a.out + (bh * a.Sq + m) * D + tid, lrun > 0.f ? acc / lrun : 0.f);
     if (tid == 0 && a.lse) a.lse[bh * a.Sq + m] = lrun > 0.f ? mrun + logf(lrun) : -INFINITY;
 }
 
@@ -765,7 +758,7 @@ __global__ __launch_bounds__(NT) void attn_full_delta_generic_kernel(const T *o,
     const int64_t row = (int64_t)blockIdx.x * NT + threadIdx.x;
     if (row >= nrows) return;
     float acc = 0.f;
-    for (int d = 0; d < D; ++d) acc += g_ld(o + row * D + d) * g_ld(d_o + row * D + d);
+    for (int d = 0; d < D; ++d) acc += load_f32(o + row * D + d) * load_f32(d_o + row * D + d);
     delta[row] = acc;
 }
 
@@ -778,8 +771,8 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const Full
     const T *K = (const T *)a.k + (b * a.Hkv + g) * a.Skv * D;
     const T *V = (const T *)a.v + (b * a.Hkv + g) * a.Skv * D;
     if (tid < D) {
-        qs[tid] = g_ld((const T *)a.q + (bh * a.Sq + m) * D + tid);
-        dos[tid] = g_ld((const T *)a.d_o + (bh * a.Sq + m) * D + tid);
+        qs[tid] = load_f32((const T *)a.q + (bh * a.Sq + m) * D + tid);
+        dos[tid] = load_f32((const T *)a.d_o + (bh * a.Sq + m) * D + tid);
     }
     const float lse = a.lse_r[bh * a.Sq + m], dlt = a.delta[bh * a.Sq + m];
     __syncthreads();
@@ -790,8 +783,8 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const Full
         if (n < len) {
             float dot = 0.f, dp = 0.f;
             for (int d = 0; d < D; ++d) {
-                dot += qs[d] * g_ld(K + n * D + d);
-                dp += dos[d] * g_ld(V + n * D + d);
+                dot += qs[d] * load_f32(K + n * D + d);
+                dp += dos[d] * load_f32(V + n * D + d);
             }
             ds = expf(dot * a.scale - lse) * (dp - dlt);
         }
@@ -799,11 +792,11 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const Full
         __syncthreads();
         if (tid < D) {
             const int cnt = (int)(len - c0 < NT ? len - c0 : NT);
-            for (int j = 0; j < cnt; ++j) acc += dss[j] * g_ld(K + (c0 + j) * D + tid);
+            for (int j = 0; j < cnt; ++j) acc += dss[j] * load_f32(K + (c0 + j) * D + tid);
         }
         __syncthreads();
     }
-    if (tid < D) g_st((T *)a.dq + (bh * a.Sq + m) * D + tid, acc * a.scale);
+    if (tid < D) store_canonical((T *)a.dq + (bh * a.Sq + m) * D + tid, acc * a.scale);
 }
 
 template <typename T>
@@ -814,12 +807,12 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
     const int64_t len = key_len(a, b);
     T *dK = (T *)a.dk + (bg * a.Skv + n) * D, *dV = (T *)a.dv + (bg * a.Skv + n) * D;
     if (n >= len) { // (workgroup-uniform)
-        if (tid < D) { g_st(dK + tid, 0.f); g_st(dV + tid, 0.f); }
+        if (tid < D) { store_canonical(dK + tid, 0.f); store_canonical(dV + tid, 0.f); }
         return;
     }
     if (tid < D) {
-        ks[tid] = g_ld((const T *)a.k + (bg * a.Skv + n) * D + tid);
-        vs[tid] = g_ld((const T *)a.v + (bg * a.Skv + n) * D + tid);
+        ks[tid] = load_f32((const T *)a.k + (bg * a.Skv + n) * D + tid);
+        vs[tid] = load_f32((const T *)a.v + (bg * a.Skv + n) * D + tid);
     }
     __syncthreads();
     float ak = 0.f, av = 0.f;
@@ -832,8 +825,8 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
             if (m < a.Sq) {
                 float dot = 0.f, dp = 0.f;
                 for (int d = 0; d < D; ++d) {
-                    dot += ks[d] * g_ld(Q + m * D + d);
-                    dp += vs[d] * g_ld(dO + m * D + d);
+                    dot += ks[d] * load_f32(Q + m * D + d);
+                    dp += vs[d] * load_f32(dO + m * D + d);
                 }
                 p = expf(dot * a.scale - a.lse_r[bh * a.Sq + m]);
                 ds = p * (dp - a.delta[bh * a.Sq + m]);
@@ -844,14 +837,14 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
             if (tid < D) {
                 const int cnt = (int)(a.Sq - c0 < NT ? a.Sq - c0 : NT);
                 for (int j = 0; j < cnt; ++j) {
-                    av += ps[j] * g_ld(dO + (c0 + j) * D + tid);
-                    ak += dss[j] * g_ld(Q + (c0 + j) * D + tid);
+                    av += ps[j] * load_f32(dO + (c0 + j) * D + tid);
+                    ak += dss[j] * load_f32(Q + (c0 + j) * D + tid);
                 }
             }
             __syncthreads();
         }
     }
-    if (tid < D) { g_st(dK + tid, ak * a.scale); g_st(dV + tid, av); }
+    if (tid < D) { store_canonical(dK + tid, ak * a.scale); store_canonical(dV + tid, av); }
 }
 
 // ==========================================================================================
@@ -942,8 +935,7 @@ extern "C" int kf_attn_full_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, i
         return with_flags([&](auto BF, auto D64) { return launch(attn_full_fwd_kernel<BF, D64 ? 64 : 128>, grid, NT, 2 * SLOT, st, a); }, bf, d64);
     }
     KF_PROF("attn_full_fwd_generic", st);
-    return launch(dtype == KF_F32 ? attn_full_fwd_generic_kernel<float> : bf ? attn_full_fwd_generic_kernel<bf16_t> : attn_full_fwd_generic_kernel<f16_t>,
-                  (unsigned)(B * Hq * Sq), NT, 0, st, a);
+    return with_dtype(dtype, [&](auto t) { return launch(attn_full_fwd_generic_kernel<decltype(t)>, (unsigned)(B * Hq * Sq), NT, 0, st, a); });
 }
 
 extern "C" int kf_attn_full_bwd_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, size_t *bytes) {
@@ -993,21 +985,19 @@ extern "C" int kf_attn_full_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, i
         const unsigned grid = (unsigned)(B * Hkv * ((Skv + TQ - 1) / TQ));
         return with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dkv_kernel<BF, D64 ? 64 : 128>, grid, NT, KV_LDS, st, a); }, bf, d64);
     }
-    {
-        KF_PROF("attn_full_bwd_delta_generic", st);
-        const unsigned grid = (unsigned)((nrows + NT - 1) / NT);
-        if (dtype == KF_F32) rc = launch(attn_full_delta_generic_kernel<float>, grid, NT, 0, st, (const float *)o, (const float *)d_o, a.delta, nrows, (int)D);
-        else if (bf) rc = launch(attn_full_delta_generic_kernel<bf16_t>, grid, NT, 0, st, (const bf16_t *)o, (const bf16_t *)d_o, a.delta, nrows, (int)D);
-        else rc = launch(attn_full_delta_generic_kernel<f16_t>, grid, NT, 0, st, (const f16_t *)o, (const f16_t *)d_o, a.delta, nrows, (int)D);
-        if (rc != KF_OK) return rc;
-    }
-    {
-        KF_PROF("attn_full_bwd_dq_generic", st);
-        rc = launch(dtype == KF_F32 ? attn_full_bwd_dq_generic_kernel<float> : bf ? attn_full_bwd_dq_generic_kernel<bf16_t> : attn_full_bwd_dq_generic_kernel<f16_t>,
-                    (unsigned)nrows, NT, 0, st, a);
-        if (rc != KF_OK) return rc;
-    }
-    KF_PROF("attn_full_bwd_dkv_generic", st);
-    return launch(dtype == KF_F32 ? attn_full_bwd_dkv_generic_kernel<float> : bf ? attn_full_bwd_dkv_generic_kernel<bf16_t> : attn_full_bwd_dkv_generic_kernel<f16_t>,
-                  (unsigned)(B * Hkv * Skv), NT, 0, st, a);
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        {
+            KF_PROF("attn_full_bwd_delta_generic", st);
+            rc = launch(attn_full_delta_generic_kernel<T>, (unsigned)((nrows + NT - 1) / NT), NT, 0, st, (const T *)o, (const T *)d_o, a.delta, nrows, (int)D);
+            if (rc != KF_OK) return rc;
+        }
+        {
+            KF_PROF("attn_full_bwd_dq_generic", st);
+            rc = launch(attn_full_bwd_dq_generic_kernel<T>, (unsigned)nrows, NT, 0, st, a);
+            if (rc != KF_OK) return rc;
+        }
+        KF_PROF("attn_full_bwd_dkv_generic", st);
+        return launch(attn_full_bwd_dkv_generic_kernel<T>, (unsigned)(B * Hkv * Skv), NT, 0, st, a);
+    });
 }

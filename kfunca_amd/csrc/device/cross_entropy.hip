@@ -32,7 +32,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "float_pack.h"
 
 // Every fused multiply-add here is written out (fmaf). Contraction would otherwise fuse m_old * log2e - h_new into one FMA, whose
 // exact product no longer cancels against the rounded h_old that s was taken relative to: 2^-11 of exponent at |x| ~ 1e4.
@@ -49,56 +49,6 @@ constexpr int64_t kCeShortRow = 4096;   // V up to this: one wave per row
 constexpr int64_t kCeManyRows = 1024;   // at least this many long rows: one block per row
 constexpr int64_t kCeSplitBlocks = 2048; // the split regime aims for this many blocks in all
 constexpr int64_t kCeMinChunk = 4096;   // elements per chunk, at least
-
-template <typename T> struct CePack;
-template <> struct CePack<float> { static constexpr int V = 4; };
-template <> struct CePack<bf16_t> { static constexpr int V = 8; };
-template <> struct CePack<f16_t> { static constexpr int V = 8; };
-
-template <typename T, int V>
-__device__ __forceinline__ void ce_unpack(const uint4 &p, float (&f)[V]) {
-    if constexpr (sizeof(T) == 4) {
-        f[0] = __uint_as_float(p.x); f[1] = __uint_as_float(p.y); f[2] = __uint_as_float(p.z); f[3] = __uint_as_float(p.w);
-    } else {
-        const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                f[2 * i] = __uint_as_float(w[i] << 16);
-                f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-            } else {
-                f[2 * i] = f16_to_f32(f16_t{(uint16_t)(w[i] & 0xffff)});
-                f[2 * i + 1] = f16_to_f32(f16_t{(uint16_t)(w[i] >> 16)});
-            }
-        }
-    }
-}
-template <typename T, int V>
-__device__ __forceinline__ uint4 ce_pack(const float (&f)[V]) {
-    uint4 p;
-    if constexpr (sizeof(T) == 4) {
-        p.x = __float_as_uint(f[0]); p.y = __float_as_uint(f[1]); p.z = __float_as_uint(f[2]); p.w = __float_as_uint(f[3]);
-    } else {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                w[i] = f32x2_to_bf16x2_hw(f[2 * i], f[2 * i + 1]);
-            } else {
-                const uint32_t lo = f32_to_f16(f[2 * i]).x, hi = f32_to_f16(f[2 * i + 1]).x;
-                w[i] = lo | (hi << 16);
-            }
-        }
-        p.x = w[0]; p.y = w[1]; p.z = w[2]; p.w = w[3];
-    }
-    return p;
-}
-template <typename T> __device__ __forceinline__ float ce_ld(const T *p) { return (float)*p; }
-template <> __device__ __forceinline__ float ce_ld<bf16_t>(const bf16_t *p) { return bf16_to_f32(*p); }
-template <> __device__ __forceinline__ float ce_ld<f16_t>(const f16_t *p) { return f16_to_f32(*p); }
-template <typename T> __device__ __forceinline__ void ce_st(T *p, float v) { *p = (T)v; }
-template <> __device__ __forceinline__ void ce_st<bf16_t>(bf16_t *p, float v) { *p = f32_to_bf16(v); }
-template <> __device__ __forceinline__ void ce_st<f16_t>(f16_t *p, float v) { *p = f32_to_f16(v); }
 
 // the online state: s = sum 2^(x log2e - h(m)), h(m) = m * log2e rounded to f32 (0 while m = -inf)
 struct CeState { float m, s, sx; };
@@ -139,14 +89,14 @@ __device__ __forceinline__ void ce_absorb(CeState &st, const float (&f)[N]) {
 // the state of the elements [c0, c1) of a row as seen by lane `lane` of the NT lanes that share the segment
 template <typename T, int NT, bool SMOOTH>
 __device__ __forceinline__ CeState ce_segment_state(const T *row, int64_t c0, int64_t c1, int lane) {
-    constexpr int V = CePack<T>::V, U = 2;
+    constexpr int V = kPack16<T>, U = 2;
     CeState st{-INFINITY, 0.f, 0.f};
     const T *p = row + c0;
     const int64_t n = c1 - c0;
     const int64_t head = std::min<int64_t>(n, (int64_t)((16u - ((uint32_t)(uintptr_t)p & 15u)) & 15u) / (int64_t)sizeof(T));
     const int64_t nb = (n - head) / V, t0 = head + nb * V;
-    if (lane < head) { const float f[1] = {ce_ld(p + lane)}; ce_absorb<1, SMOOTH>(st, f); }
-    if (t0 + lane < n) { const float f[1] = {ce_ld(p + t0 + lane)}; ce_absorb<1, SMOOTH>(st, f); }
+    if (lane < head) { const float f[1] = {load_f32(p + lane)}; ce_absorb<1, SMOOTH>(st, f); }
+    if (t0 + lane < n) { const float f[1] = {load_f32(p + t0 + lane)}; ce_absorb<1, SMOOTH>(st, f); }
     const uint4 *q = (const uint4 *)(p + head);
     for (int64_t k = lane; k < nb; k += (int64_t)NT * U) {
         uint4 raw[U];
@@ -156,7 +106,7 @@ __device__ __forceinline__ CeState ce_segment_state(const T *row, int64_t c0, in
         for (int u = 0; u < U; ++u) {
             if (k + (int64_t)u * NT < nb) {
                 float f[V];
-                ce_unpack<T, V>(raw[u], f);
+                unpack16<T>(raw[u], f);
                 ce_absorb<V, SMOOTH>(st, f);
             }
         }
@@ -207,7 +157,7 @@ __device__ __forceinline__ void ce_finish(const CeFwdArgs &a, int64_t row, const
     } else if (t < 0 || t >= a.V) {
         loss = __builtin_nanf("");
     } else {
-        const float xt = ce_ld((const T *)a.x + row * a.ld + t);
+        const float xt = load_f32((const T *)a.x + row * a.ld + t);
         loss = 0.f;
         if (a.eps < 1.f) loss = (1.f - a.eps) * ((st.m - xt) + lns);
         if (a.eps > 0.f) loss += a.eps * ((st.m - st.sx / (float)a.V) + lns);
@@ -296,13 +246,13 @@ struct CeBwdArgs {
 // dx over the elements [c0, c1) of a row, lane `lane` of NT
 template <typename T, int NT>
 __device__ __forceinline__ void ce_bwd_segment(const CeBwdArgs &a, int64_t row, int64_t c0, int64_t c1, int lane) {
-    constexpr int V = CePack<T>::V, U = 2;
+    constexpr int V = kPack16<T>, U = 2;
     const T *x = (const T *)a.x + row * a.ld + c0;
     T *dx = (T *)a.dx + row * a.ldd + c0;
     const int64_t n = c1 - c0;
     const int64_t t = a.target[row];
     if (t == a.ignore_index) { // a zero row, whatever the logits hold
-        for (int64_t i = lane; i < n; i += NT) ce_st(dx + i, 0.f);
+        for (int64_t i = lane; i < n; i += NT) store_canonical(dx + i, 0.f);
         return;
     }
     float g = a.reduction == KF_CE_NONE ? a.grad[row] : a.grad[0];
@@ -313,8 +263,8 @@ __device__ __forceinline__ void ce_bwd_segment(const CeBwdArgs &a, int64_t row, 
     const float gs = g * ce_exp2(-lo), c0s = g * a.eps / (float)a.V, c1s = g * (1.f - a.eps);
     const int64_t tl = t - c0; // the target's position inside the segment (may lie outside it)
     auto one = [&](int64_t i) __attribute__((always_inline)) {
-        const float v = fmaf(gs, ce_exp2(fmaf(ce_ld(x + i), kLog2e, -hl)), -c0s);
-        ce_st(dx + i, i == tl ? v - c1s : v);
+        const float v = fmaf(gs, ce_exp2(fmaf(load_f32(x + i), kLog2e, -hl)), -c0s);
+        store_canonical(dx + i, i == tl ? v - c1s : v);
     };
     const uint32_t px = (uint32_t)(uintptr_t)x & 15u, pd = (uint32_t)(uintptr_t)dx & 15u;
     if (px != pd) { // the two rows sit differently against 16-byte boundaries: element by element
@@ -336,7 +286,7 @@ __device__ __forceinline__ void ce_bwd_segment(const CeBwdArgs &a, int64_t row, 
             const int64_t kk = k + (int64_t)u * NT;
             if (kk < nb) {
                 float f[V];
-                ce_unpack<T, V>(raw[u], f);
+                unpack16<T>(raw[u], f);
 #pragma unroll
                 for (int i = 0; i < V; ++i) f[i] = fmaf(gs, ce_exp2(fmaf(f[i], kLog2e, -hl)), -c0s);
                 const int64_t e = tl - head - kk * V;
@@ -345,7 +295,7 @@ __device__ __forceinline__ void ce_bwd_segment(const CeBwdArgs &a, int64_t row, 
                     for (int i = 0; i < V; ++i)
                         if (i == e) f[i] -= c1s;
                 }
-                qd[kk] = ce_pack<T, V>(f);
+                qd[kk] = pack16<T>(f);
             }
         }
     }
@@ -406,13 +356,6 @@ extern "C" int kf_cross_entropy_workspace_bytes(int dtype, int64_t rows, int64_t
     return KF_OK;
 }
 
-#define KF_CE_BY_DTYPE(KERNEL, GRID, ...)                                                                         \
-    do {                                                                                                          \
-        if (dtype == KF_F32) KERNEL<float __VA_ARGS__><<<(GRID), kCeBlock, 0, st>>>(a);                          \
-        else if (dtype == KF_BF16) KERNEL<bf16_t __VA_ARGS__><<<(GRID), kCeBlock, 0, st>>>(a);                   \
-        else KERNEL<f16_t __VA_ARGS__><<<(GRID), kCeBlock, 0, st>>>(a);                                          \
-    } while (0)
-
 extern "C" int kf_cross_entropy_fwd(int dtype, int64_t rows, int64_t V, int64_t ld, const void *logits, const int64_t *target,
                                     int64_t ignore_index, float label_smoothing, int reduction, float *loss, float *lse, float *count,
                                     void *workspace, size_t workspace_bytes, void *stream) {
@@ -430,32 +373,32 @@ extern "C" int kf_cross_entropy_fwd(int dtype, int64_t rows, int64_t V, int64_t 
                 ignore_index, pl.chunk, pl.nchunk, label_smoothing};
     const bool smooth = label_smoothing > 0.f;
     if (rows > 0) {
-        if (pl.regime == CE_ROWS) {
-            KF_PROF("ce_fwd_rows", st);
-            const unsigned grid = (unsigned)((rows + kCeBlock / 64 - 1) / (kCeBlock / 64));
-            if (smooth) KF_CE_BY_DTYPE(ce_fwd_rows, grid, , true); else KF_CE_BY_DTYPE(ce_fwd_rows, grid, , false);
-            KF_LAUNCH_CHECK();
-        } else if (pl.regime == CE_BLOCK) {
-            KF_PROF("ce_fwd_block", st);
-            if (smooth) KF_CE_BY_DTYPE(ce_fwd_block, (unsigned)rows, , true); else KF_CE_BY_DTYPE(ce_fwd_block, (unsigned)rows, , false);
-            KF_LAUNCH_CHECK();
-        } else {
-            {
-                KF_PROF("ce_fwd_split", st);
-                const unsigned grid = (unsigned)(rows * pl.nchunk);
-                if (smooth) KF_CE_BY_DTYPE(ce_fwd_split, grid, , true); else KF_CE_BY_DTYPE(ce_fwd_split, grid, , false);
-                KF_LAUNCH_CHECK();
-            }
-            KF_PROF("ce_combine", st);
-            KF_CE_BY_DTYPE(ce_combine, (unsigned)((rows + kCeBlock - 1) / kCeBlock));
-            KF_LAUNCH_CHECK();
-        }
+        rc = with_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return with_flags([&](auto SMOOTH) {
+                if (pl.regime == CE_ROWS) {
+                    KF_PROF("ce_fwd_rows", st);
+                    return launch(ce_fwd_rows<T, SMOOTH>, (unsigned)((rows + kCeBlock / 64 - 1) / (kCeBlock / 64)), kCeBlock, 0, st, a);
+                }
+                if (pl.regime == CE_BLOCK) {
+                    KF_PROF("ce_fwd_block", st);
+                    return launch(ce_fwd_block<T, SMOOTH>, (unsigned)rows, kCeBlock, 0, st, a);
+                }
+                {
+                    KF_PROF("ce_fwd_split", st);
+                    const int rs = launch(ce_fwd_split<T, SMOOTH>, (unsigned)(rows * pl.nchunk), kCeBlock, 0, st, a);
+                    if (rs != KF_OK) return rs;
+                }
+                KF_PROF("ce_combine", st);
+                return launch(ce_combine<T>, (unsigned)((rows + kCeBlock - 1) / kCeBlock), kCeBlock, 0, st, a);
+            }, smooth);
+        });
+        if (rc != KF_OK) return rc;
     }
     if (reduction != KF_CE_NONE || count) {
         KF_PROF("ce_reduce", st);
-        ce_reduce<<<1, 1024, 0, st>>>(reduction == KF_CE_NONE ? nullptr : a.rowloss, target, rows, ignore_index, reduction == KF_CE_MEAN,
-                                      reduction == KF_CE_NONE ? nullptr : loss, count);
-        KF_LAUNCH_CHECK();
+        return launch(ce_reduce, 1, 1024, 0, st, reduction == KF_CE_NONE ? nullptr : a.rowloss, target, rows, ignore_index, (int)(reduction == KF_CE_MEAN),
+                      reduction == KF_CE_NONE ? nullptr : loss, count);
     }
     return KF_OK;
 }
@@ -475,8 +418,9 @@ extern "C" int kf_cross_entropy_bwd(int dtype, int64_t rows, int64_t V, int64_t 
     const CePlan pl = ce_plan(rows, V);
     CeBwdArgs a{logits, target, lse, grad, count, dlogits, rows, V, ld, ldd, ignore_index, pl.chunk, pl.nchunk, reduction, label_smoothing};
     KF_PROF("ce_bwd", st);
-    if (pl.regime == CE_ROWS) KF_CE_BY_DTYPE(ce_bwd_rows, (unsigned)((rows + kCeBlock / 64 - 1) / (kCeBlock / 64)));
-    else KF_CE_BY_DTYPE(ce_bwd, (unsigned)(rows * pl.nchunk));
-    KF_LAUNCH_CHECK();
-    return KF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return pl.regime == CE_ROWS ? launch(ce_bwd_rows<T>, (unsigned)((rows + kCeBlock / 64 - 1) / (kCeBlock / 64)), kCeBlock, 0, st, a)
+                                    : launch(ce_bwd<T>, (unsigned)(rows * pl.nchunk), kCeBlock, 0, st, a);
+    });
 }

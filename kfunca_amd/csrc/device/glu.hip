@@ -23,7 +23,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "float_pack.h"
 
 // the packed and the element path must round alike, bit for bit
 #pragma clang fp contract(off)
@@ -47,59 +47,25 @@ constexpr float kT1 = (float)(kW1d * kLog2ed), kT3 = (float)(kW3d * kLog2ed);
 // g^2 is capped where sigma (1 - sigma) is long zero, so that w'(g) stays finite for every finite g (inf * 0 otherwise)
 constexpr float kG2Cap = 1.0e30f;
 
+// V elements at p: one 16-byte pack, or one element (V = 1)
 template <typename T, int V>
 __device__ __forceinline__ void glu_load(const T *p, float (&f)[V]) {
-    if constexpr (V == 1) {
-        if constexpr (std::is_same<T, float>::value) f[0] = *p;
-        else if constexpr (std::is_same<T, bf16_t>::value) f[0] = bf16_to_f32(*p);
-        else f[0] = f16_to_f32(*p);
-    } else {
-        const uint4 v = *(const uint4 *)p;
-        if constexpr (sizeof(T) == 4) {
-            f[0] = __uint_as_float(v.x); f[1] = __uint_as_float(v.y); f[2] = __uint_as_float(v.z); f[3] = __uint_as_float(v.w);
-        } else {
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if constexpr (std::is_same<T, bf16_t>::value) {
-                    f[2 * i] = __uint_as_float(w[i] << 16);
-                    f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-                } else {
-                    f[2 * i] = f16_to_f32(f16_t{(uint16_t)(w[i] & 0xffff)});
-                    f[2 * i + 1] = f16_to_f32(f16_t{(uint16_t)(w[i] >> 16)});
-                }
-            }
-        }
-    }
+    if constexpr (V == 1) f[0] = load_f32(p);
+    else unpack16<T>(*(const uint4 *)p, f);
 }
-// f32 -> f16 of a value the compiler cannot see through: left to itself it folds the last multiply into the conversion
+// one rounding per element, to nearest even in both paths; the hardware bf16 converter (pack16, store_hw) keeps a NaN a NaN.
+// f32 -> f16 of values the compiler cannot see through: left to itself it folds the last multiply into the conversion
 // (v_fma_mixlo_f16: the exact product rounded once to f16) in the element path only, and the two paths then differ in the last bit
-__device__ __forceinline__ f16_t glu_f16(float f) {
-    asm("" : "+v"(f));
-    return f32_to_f16(f);
-}
-// one rounding per element, to nearest even in both paths; the hardware bf16 converter keeps a NaN a NaN
 template <typename T, int V>
 __device__ __forceinline__ void glu_store(T *p, const float (&f)[V]) {
-    if constexpr (V == 1) {
-        if constexpr (std::is_same<T, float>::value) *p = f[0];
-        else if constexpr (std::is_same<T, bf16_t>::value) p->x = (uint16_t)f32x2_to_bf16x2_hw(f[0], 0.f);
-        else *p = glu_f16(f[0]);
-    } else {
-        uint4 v;
-        if constexpr (sizeof(T) == 4) {
-            v.x = __float_as_uint(f[0]); v.y = __float_as_uint(f[1]); v.z = __float_as_uint(f[2]); v.w = __float_as_uint(f[3]);
-        } else {
-            uint32_t w[4];
+    float r[V];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if constexpr (std::is_same<T, bf16_t>::value) w[i] = f32x2_to_bf16x2_hw(f[2 * i], f[2 * i + 1]);
-                else w[i] = (uint32_t)glu_f16(f[2 * i]).x | ((uint32_t)glu_f16(f[2 * i + 1]).x << 16);
-            }
-            v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-        }
-        *(uint4 *)p = v;
+    for (int i = 0; i < V; ++i) {
+        r[i] = f[i];
+        if constexpr (std::is_same<T, f16_t>::value) asm("" : "+v"(r[i]));
     }
+    if constexpr (V == 1) store_hw(p, r[0]);
+    else *(uint4 *)p = pack16<T>(r);
 }
 
 // sigma(x) and the pieces of its derivative from t = |x| log2 e >= 0: s = sigma(x), q = 1 - sigma(x), sq = sigma (1 - sigma).
@@ -193,28 +159,6 @@ __global__ __launch_bounds__(kGluBlock) void glu_bwd_kernel(const GluArgs a) {
 }
 #undef KF_GLU_WALK
 
-template <bool BWD, typename T, int V, int ACT>
-void glu_launch_gated(bool gated, unsigned grid, hipStream_t st, const GluArgs &a) {
-    if constexpr (BWD) {
-        if (gated) glu_bwd_kernel<T, V, ACT, true><<<grid, kGluBlock, 0, st>>>(a);
-        else glu_bwd_kernel<T, V, ACT, false><<<grid, kGluBlock, 0, st>>>(a);
-    } else {
-        if (gated) glu_fwd_kernel<T, V, ACT, true><<<grid, kGluBlock, 0, st>>>(a);
-        else glu_fwd_kernel<T, V, ACT, false><<<grid, kGluBlock, 0, st>>>(a);
-    }
-}
-template <bool BWD, typename T, int V>
-void glu_launch_act(int act, bool gated, unsigned grid, hipStream_t st, const GluArgs &a) {
-    if (act == KF_ACT_SILU) glu_launch_gated<BWD, T, V, KF_ACT_SILU>(gated, grid, st, a);
-    else if (act == KF_ACT_GELU_TANH) glu_launch_gated<BWD, T, V, KF_ACT_GELU_TANH>(gated, grid, st, a);
-    else glu_launch_gated<BWD, T, V, KF_ACT_GELU_ERF>(gated, grid, st, a);
-}
-template <bool BWD, typename T>
-void glu_launch_vec(bool vec, int act, bool gated, unsigned grid, hipStream_t st, const GluArgs &a) {
-    if (vec) glu_launch_act<BWD, T, 16 / sizeof(T)>(act, gated, grid, st, a);
-    else glu_launch_act<BWD, T, 1>(act, gated, grid, st, a);
-}
-
 // the checks both entries share; ptrs / lds: every operand that is present, outputs included
 int glu_check(const char *who, int act, int dtype, int64_t rows, int64_t F, const void *const *ptrs, const int64_t *lds, const char *const *names, int n) {
     KF_REQUIRE(act == KF_ACT_SILU || act == KF_ACT_GELU_TANH || act == KF_ACT_GELU_ERF, KF_ERR_INVALID,
@@ -251,11 +195,19 @@ int glu_run(const char *const *prof, int act, int dtype, int64_t rows, int64_t F
     a.step_cols = stride % a.P;
     hipStream_t st = as_stream(stream);
     KF_PROF(prof[vec ? 0 : 1], st);
-    if (dtype == KF_F32) glu_launch_vec<BWD, float>(vec, act, a.up != nullptr, grid, st, a);
-    else if (dtype == KF_BF16) glu_launch_vec<BWD, bf16_t>(vec, act, a.up != nullptr, grid, st, a);
-    else glu_launch_vec<BWD, f16_t>(vec, act, a.up != nullptr, grid, st, a);
-    KF_LAUNCH_CHECK();
-    return KF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_flags([&](auto VEC, auto GATED) {
+            constexpr int V = VEC ? kPack16<T> : 1;
+            auto go = [&](auto ACT) {
+                if constexpr (BWD) return launch(glu_bwd_kernel<T, V, ACT, GATED>, grid, kGluBlock, 0, st, a);
+                else return launch(glu_fwd_kernel<T, V, ACT, GATED>, grid, kGluBlock, 0, st, a);
+            };
+            return act == KF_ACT_SILU        ? go(std::integral_constant<int, KF_ACT_SILU>{})
+                   : act == KF_ACT_GELU_TANH ? go(std::integral_constant<int, KF_ACT_GELU_TANH>{})
+                                             : go(std::integral_constant<int, KF_ACT_GELU_ERF>{});
+        }, vec, a.up != nullptr);
+    });
 }
 
 } // namespace

@@ -5,7 +5,7 @@
 // offset into `self`, and move the value's bits. HBM-bound byte work: no arithmetic on values, so
 // the result is bit-exact for every dtype. Duplicated targets: last writer wins in unspecified
 // order, as in the reference (no atomics, tensor_index.h:56-75).
-#include "common.h"
+#include "float_pack.h"
 #include "offset_calc.h"
 
 namespace kf {
@@ -62,13 +62,6 @@ __global__ __launch_bounds__(256) void index_get_kernel(const char *table, int64
 // The indices are wrapped, then stably sorted (kf_sort, int64 keys + positions); then
 // dst[r, :] = sum over the run of equal sorted indices r of src[pos[j], :], added in run order (the stable sort's order =
 // input order): one wave per run START (the other waves leave at once), f32 accumulation, no atomics - bitwise reproducible.
-template <typename T> __device__ __forceinline__ float ia_ld(const T *p) { return (float)*p; }
-template <> __device__ __forceinline__ float ia_ld<bf16_t>(const bf16_t *p) { return bf16_to_f32(*p); }
-template <> __device__ __forceinline__ float ia_ld<f16_t>(const f16_t *p) { return f16_to_f32(*p); }
-template <typename T> __device__ __forceinline__ void ia_st(T *p, float v) { *p = (T)v; }
-template <> __device__ __forceinline__ void ia_st<bf16_t>(bf16_t *p, float v) { *p = f32_to_bf16(v); }
-template <> __device__ __forceinline__ void ia_st<f16_t>(f16_t *p, float v) { *p = f32_to_f16(v); }
-
 template <typename K>
 __global__ __launch_bounds__(256) void index_wrap_kernel(const int64_t *idx, int64_t n, int64_t nrows, K *out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -123,7 +116,7 @@ __global__ __launch_bounds__(256) void index_add_sorted_vec_kernel(const K *key,
                     T t[V];
                     __builtin_memcpy(t, &raw[q], 16);
 #pragma unroll
-                    for (int e = 0; e < V; ++e) acc[q][e] += ia_ld(&t[e]);
+                    for (int e = 0; e < V; ++e) acc[q][e] += load_f32(&t[e]);
                 }
             }
             if (cnt < 64) break;
@@ -134,7 +127,7 @@ __global__ __launch_bounds__(256) void index_add_sorted_vec_kernel(const K *key,
             if (c < npk) {
                 T t[V];
 #pragma unroll
-                for (int e = 0; e < V; ++e) ia_st(&t[e], acc[q][e]);
+                for (int e = 0; e < V; ++e) store_canonical(&t[e], acc[q][e]);
                 uint4 o;
                 __builtin_memcpy(&o, t, 16);
                 ((uint4 *)(dst + (int64_t)k * cols))[c] = o;
@@ -160,13 +153,13 @@ __global__ __launch_bounds__(256) void index_add_sorted_kernel(const K *key, con
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int64_t c = c0 + (int64_t)i * 64 + lane;
-                if (c < cols) acc[i] += ia_ld(row + c);
+                if (c < cols) acc[i] += load_f32(row + c);
             }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int64_t c = c0 + (int64_t)i * 64 + lane;
-            if (c < cols) ia_st(dst + r * cols + c, acc[i]);
+            if (c < cols) store_canonical(dst + r * cols + c, acc[i]);
         }
     }
 }
@@ -189,15 +182,8 @@ extern "C" int kf_index_get(const void *table, int64_t nrows, int64_t row_bytes,
     KF_PROF("index_get", st);
     const char *t = (const char *)table;
     char *o = (char *)out;
-    switch (us) {
-    case 16: index_get_kernel<uint4><<<grid, 256, 0, st>>>(t, nrows, row_bytes, idx, units, (uint32_t)upr, o); break;
-    case 8: index_get_kernel<uint64_t><<<grid, 256, 0, st>>>(t, nrows, row_bytes, idx, units, (uint32_t)upr, o); break;
-    case 4: index_get_kernel<uint32_t><<<grid, 256, 0, st>>>(t, nrows, row_bytes, idx, units, (uint32_t)upr, o); break;
-    case 2: index_get_kernel<uint16_t><<<grid, 256, 0, st>>>(t, nrows, row_bytes, idx, units, (uint32_t)upr, o); break;
-    default: index_get_kernel<uint8_t><<<grid, 256, 0, st>>>(t, nrows, row_bytes, idx, units, (uint32_t)upr, o); break;
-    }
-    KF_LAUNCH_CHECK();
-    return KF_OK;
+    auto go = [&](auto u) { return launch(index_get_kernel<decltype(u)>, grid, 256, 0, st, t, nrows, row_bytes, idx, units, (uint32_t)upr, o); };
+    return us == 16 ? go(uint4{}) : us == 8 ? go(uint64_t{}) : us == 4 ? go(uint32_t{}) : us == 2 ? go(uint16_t{}) : go(uint8_t{});
 }
 
 static inline size_t ia_align(size_t v) { return (v + 255) / 256 * 256; }
@@ -226,9 +212,10 @@ extern "C" int kf_index_add(int dtype, const int64_t *idx, int64_t n, const void
     const bool k32 = nrows < 0x7fffffffLL;   // (the key nrows itself must fit: it marks out-of-range indices)
     {
         KF_PROF("index_wrap", st);
-        if (k32) index_wrap_kernel<int32_t><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(idx, n, nrows, (int32_t *)wrapped);
-        else index_wrap_kernel<int64_t><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(idx, n, nrows, (int64_t *)wrapped);
-        KF_LAUNCH_CHECK();
+        const unsigned gw = (unsigned)((n + 255) / 256);
+        const int rw = k32 ? launch(index_wrap_kernel<int32_t>, gw, 256, 0, st, idx, n, nrows, (int32_t *)wrapped)
+                           : launch(index_wrap_kernel<int64_t>, gw, 256, 0, st, idx, n, nrows, (int64_t *)wrapped);
+        if (rw != KF_OK) return rw;
     }
     const int kcode = k32 ? KF_I32 : KF_I64;
     const size_t sws = kf_sort_workspace_bytes(kcode, 1, n);
@@ -241,21 +228,18 @@ extern "C" int kf_index_add(int dtype, const int64_t *idx, int64_t n, const void
     const int es = dtype == KF_F32 ? 4 : 2;
     const bool vec = (cols * es) % 16 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
     const int64_t npk = cols * es / 16;
-#define KF_IA(T_, K_)                                                                                                                              \
-    {                                                                                                                                              \
-        if (!vec) index_add_sorted_kernel<T_, K_><<<grid, 256, 0, st>>>((const K_ *)sorted, pos, n, (const T_ *)src, cols, nrows, (T_ *)dst);        \
-        else if (npk <= 64) index_add_sorted_vec_kernel<T_, K_, 1><<<grid, 256, 0, st>>>((const K_ *)sorted, pos, n, (const T_ *)src, cols, nrows, (T_ *)dst); \
-        else if (npk <= 128) index_add_sorted_vec_kernel<T_, K_, 2><<<grid, 256, 0, st>>>((const K_ *)sorted, pos, n, (const T_ *)src, cols, nrows, (T_ *)dst); \
-        else if (npk <= 256) index_add_sorted_vec_kernel<T_, K_, 4><<<grid, 256, 0, st>>>((const K_ *)sorted, pos, n, (const T_ *)src, cols, nrows, (T_ *)dst); \
-        else index_add_sorted_vec_kernel<T_, K_, 8><<<grid, 256, 0, st>>>((const K_ *)sorted, pos, n, (const T_ *)src, cols, nrows, (T_ *)dst);             \
-    }
-#define KF_IA_K(T_) \
-    if (k32) KF_IA(T_, int32_t) else KF_IA(T_, int64_t)
-    if (dtype == KF_F32) { KF_IA_K(float) } else if (dtype == KF_BF16) { KF_IA_K(bf16_t) } else { KF_IA_K(f16_t) }
-#undef KF_IA_K
-#undef KF_IA
-    KF_LAUNCH_CHECK();
-    return KF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_flags([&](auto K32) {
+            using K = std::conditional_t<K32, int32_t, int64_t>;
+            auto run = [&](auto kernel) { return launch(kernel, grid, 256, 0, st, (const K *)sorted, pos, n, (const T *)src, cols, nrows, (T *)dst); };
+            return !vec         ? run(index_add_sorted_kernel<T, K>)
+                   : npk <= 64  ? run(index_add_sorted_vec_kernel<T, K, 1>)
+                   : npk <= 128 ? run(index_add_sorted_vec_kernel<T, K, 2>)
+                   : npk <= 256 ? run(index_add_sorted_vec_kernel<T, K, 4>)
+                                : run(index_add_sorted_vec_kernel<T, K, 8>);
+        }, k32);
+    });
 }
 
 extern "C" int kf_index_put(const kf_iter_desc *d, int nidx, const int64_t *sizes, const int64_t *strides_bytes,
@@ -290,12 +274,11 @@ extern "C" int kf_index_put(const kf_iter_desc *d, int nidx, const int64_t *size
     hipStream_t st = as_stream(stream);
     KF_PROF("index_put", st);
     switch (dtype_size(d->dtype[0])) {
-    case 1: index_put_kernel<uint8_t><<<(unsigned)blocks, kIB, 0, st>>>(a); break;
-    case 2: index_put_kernel<uint16_t><<<(unsigned)blocks, kIB, 0, st>>>(a); break;
-    case 4: index_put_kernel<uint32_t><<<(unsigned)blocks, kIB, 0, st>>>(a); break;
-    case 8: index_put_kernel<uint64_t><<<(unsigned)blocks, kIB, 0, st>>>(a); break;
+    case 1: return launch(index_put_kernel<uint8_t>, (unsigned)blocks, kIB, 0, st, a);
+    case 2: return launch(index_put_kernel<uint16_t>, (unsigned)blocks, kIB, 0, st, a);
+    case 4: return launch(index_put_kernel<uint32_t>, (unsigned)blocks, kIB, 0, st, a);
+    case 8: return launch(index_put_kernel<uint64_t>, (unsigned)blocks, kIB, 0, st, a);
     default: KF_REQUIRE(false, KF_ERR_INVALID, "kf_index_put: bad dtype");
     }
-    KF_LAUNCH_CHECK();
     return KF_OK;
 }

@@ -16,7 +16,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "float_pack.h"
 
 namespace kf {
 
@@ -29,50 +29,6 @@ struct NormArgs {
     float eps;
     int rms;
 };
-
-template <typename T> struct NPack;
-template <> struct NPack<float> { static constexpr int V = 4; };
-template <> struct NPack<bf16_t> { static constexpr int V = 8; };
-template <> struct NPack<f16_t> { static constexpr int V = 8; };
-
-template <typename T, int V>
-__device__ __forceinline__ void n_unpack(const uint4 &p, float (&f)[V]) {
-    if constexpr (sizeof(T) == 4) {
-        f[0] = __uint_as_float(p.x); f[1] = __uint_as_float(p.y); f[2] = __uint_as_float(p.z); f[3] = __uint_as_float(p.w);
-    } else {
-        const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                f[2 * i] = __uint_as_float(w[i] << 16);
-                f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-            } else {
-                f[2 * i] = f16_to_f32(f16_t{(uint16_t)(w[i] & 0xffff)});
-                f[2 * i + 1] = f16_to_f32(f16_t{(uint16_t)(w[i] >> 16)});
-            }
-        }
-    }
-}
-template <typename T, int V>
-__device__ __forceinline__ uint4 n_pack(const float (&f)[V]) {
-    uint4 p;
-    if constexpr (sizeof(T) == 4) {
-        p.x = __float_as_uint(f[0]); p.y = __float_as_uint(f[1]); p.z = __float_as_uint(f[2]); p.w = __float_as_uint(f[3]);
-    } else {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                w[i] = f32x2_to_bf16x2_hw(f[2 * i], f[2 * i + 1]);
-            } else {
-                const uint32_t lo = f32_to_f16(f[2 * i]).x, hi = f32_to_f16(f[2 * i + 1]).x;
-                w[i] = lo | (hi << 16);
-            }
-        }
-        p.x = w[0]; p.y = w[1]; p.z = w[2]; p.w = w[3];
-    }
-    return p;
-}
 
 // sum over the TPR lanes that share a row (TPR = 64: one wave; 256 / 512 / 1024: the whole block, through LDS). Every lane gets the total.
 template <int TPR>
@@ -102,7 +58,7 @@ __device__ __forceinline__ float n_row_sum(float v, float *red) {
 // ---- forward: a row in registers ---------------------------------------------------------------------------------
 template <typename T, int TPR, int PACKS>
 __global__ __launch_bounds__(256) void norm_fwd_kernel(const NormArgs a) {
-    constexpr int V = NPack<T>::V, RPB = 256 / TPR;
+    constexpr int V = kPack16<T>, RPB = 256 / TPR;
     __shared__ float red[4];
     const int tr = threadIdx.x % TPR;
     const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / TPR;
@@ -121,7 +77,7 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const NormArgs a) {
         }
 #pragma unroll
         for (int p = 0; p < PACKS; ++p) {
-            n_unpack<T, V>(raw[p], xv[p]);
+            unpack16<T>(raw[p], xv[p]);
 #pragma unroll
             for (int i = 0; i < V; ++i) s += a.rms ? xv[p][i] * xv[p][i] : xv[p][i];
         }
@@ -168,8 +124,8 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const NormArgs a) {
             const int p = p0 + g;
             const int64_t c = ((int64_t)p * TPR + tr) * V;
             float wv[V], bv[V], o[V];
-            n_unpack<T, V>(wr[g], wv);
-            n_unpack<T, V>(br[g], bv);
+            unpack16<T>(wr[g], wv);
+            unpack16<T>(br[g], bv);
 #pragma unroll
             for (int i = 0; i < V; ++i) {
                 float t = (xv[p][i] - mean) * rstd;
@@ -177,7 +133,7 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const NormArgs a) {
                 if (a.b) t += bv[i];
                 o[i] = t;
             }
-            if (c < a.cols) *(uint4 *)(y + c) = n_pack<T, V>(o);
+            if (c < a.cols) *(uint4 *)(y + c) = pack16<T>(o);
         }
     }
 }
@@ -214,7 +170,7 @@ __device__ __forceinline__ void n_row_sum2(float &s1, float &s2, float (*red)[2]
 template <typename T, int TPR, int PACKS, bool RMS, int PF>
 __global__ __launch_bounds__(TPR < 256 ? 256 : TPR) void norm_bwd_kernel(const NormArgs a) {
     constexpr int NT = TPR < 256 ? 256 : TPR; // threads per block: four wave-rows, or ONE row across 4 / 8 / 16 waves
-    constexpr int V = NPack<T>::V, RPB = NT / TPR;
+    constexpr int V = kPack16<T>, RPB = NT / TPR;
     __shared__ float red[2][2][16];
     const int tr = threadIdx.x % TPR, sub = threadIdx.x / TPR;
     // Registers hold the row as it was LOADED (16-byte packs of x and dy: half the registers of their f32 images for 16-bit rows);
@@ -266,9 +222,9 @@ __global__ __launch_bounds__(TPR < 256 ? 256 : TPR) void norm_bwd_kernel(const N
 #pragma unroll
         for (int p = 0; p < PACKS; ++p) {
             float xv[V], dv[V], wv[V];
-            n_unpack<T, V>(xq[0][p], xv);
-            n_unpack<T, V>(dq[0][p], dv);
-            n_unpack<T, V>(wr[p], wv);
+            unpack16<T>(xq[0][p], xv);
+            unpack16<T>(dq[0][p], dv);
+            unpack16<T>(wr[p], wv);
 #pragma unroll
             for (int i = 0; i < V; ++i) {
                 const float xh = RMS ? xv[i] * rstd : (xv[i] - mean) * rstd;
@@ -295,16 +251,16 @@ __global__ __launch_bounds__(TPR < 256 ? 256 : TPR) void norm_bwd_kernel(const N
                 const int64_t c = ((int64_t)p * TPR + tr) * V;
                 if (okc[p]) {
                     float xv[V], dv[V], wv[V], o[V];
-                    n_unpack<T, V>(xq[0][p], xv);
-                    n_unpack<T, V>(dq[0][p], dv);
-                    n_unpack<T, V>(wr[p], wv);
+                    unpack16<T>(xq[0][p], xv);
+                    unpack16<T>(dq[0][p], dv);
+                    unpack16<T>(wr[p], wv);
 #pragma unroll
                     for (int i = 0; i < V; ++i) {
                         const float xh = RMS ? xv[i] * rstd : (xv[i] - mean) * rstd;
                         const float g = dv[i] * wv[i];
                         o[i] = RMS ? rstd * (g - xh * s2) : rstd * (g - s1 - xh * s2);
                     }
-                    *(uint4 *)(dx + c) = n_pack<T, V>(o);
+                    *(uint4 *)(dx + c) = pack16<T>(o);
                 }
             }
         }
@@ -384,7 +340,7 @@ __global__ __launch_bounds__(256) void norm_fold_kernel(const float *part, int n
     if (kl != 0 || c >= cols) return;
     const float tw = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
     const float tb = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
-    auto st = [](void *p, int64_t i, float v) {
+    auto st = [](void *p, int64_t i, float v) { // (the canonical store, written out: through store_canonical the address is formed first and the instructions change order)
         if constexpr (sizeof(T) == 4) ((float *)p)[i] = v;
         else if constexpr (std::is_same<T, bf16_t>::value) ((bf16_t *)p)[i] = f32_to_bf16(v);
         else ((f16_t *)p)[i] = f32_to_f16(v);
@@ -394,13 +350,7 @@ __global__ __launch_bounds__(256) void norm_fold_kernel(const float *part, int n
 }
 
 // ---- generic rows (any length, any alignment): one block per row, strided loops, x re-read from L2 -------------------
-template <typename T> __device__ __forceinline__ float n_ld(const T *p) { return (float)*p; }
-template <> __device__ __forceinline__ float n_ld<bf16_t>(const bf16_t *p) { return bf16_to_f32(*p); }
-template <> __device__ __forceinline__ float n_ld<f16_t>(const f16_t *p) { return f16_to_f32(*p); }
-template <typename T> __device__ __forceinline__ void n_st(T *p, float v) { *p = (T)v; }
-template <> __device__ __forceinline__ void n_st<bf16_t>(bf16_t *p, float v) { *p = f32_to_bf16(v); }
-template <> __device__ __forceinline__ void n_st<f16_t>(f16_t *p, float v) { *p = f32_to_f16(v); }
-
+// (single elements are stored with store_canonical: a NaN leaves here as 0x7FC0, from the packed kernels above with its payload)
 template <typename T>
 __global__ __launch_bounds__(256) void norm_fwd_generic_kernel(const NormArgs a) {
     __shared__ float red[4];
@@ -408,14 +358,14 @@ __global__ __launch_bounds__(256) void norm_fwd_generic_kernel(const NormArgs a)
     const T *x = (const T *)a.x + row * a.ldx;
     const float inv_n = 1.0f / (float)a.cols;
     float s = 0.f;
-    for (int64_t c = threadIdx.x; c < a.cols; c += 256) { const float v = n_ld(x + c); s += a.rms ? v * v : v; }
+    for (int64_t c = threadIdx.x; c < a.cols; c += 256) { const float v = load_f32(x + c); s += a.rms ? v * v : v; }
     s = n_row_sum<256>(s, red);
     float mean = 0.f, var;
     if (a.rms) var = s * inv_n;
     else {
         mean = s * inv_n;
         float q = 0.f;
-        for (int64_t c = threadIdx.x; c < a.cols; c += 256) { const float d = n_ld(x + c) - mean; q += d * d; }
+        for (int64_t c = threadIdx.x; c < a.cols; c += 256) { const float d = load_f32(x + c) - mean; q += d * d; }
         var = n_row_sum<256>(q, red) * inv_n;
     }
     const float rstd = 1.0f / sqrtf(var + a.eps);
@@ -425,10 +375,10 @@ __global__ __launch_bounds__(256) void norm_fwd_generic_kernel(const NormArgs a)
     }
     T *y = (T *)a.y + row * a.ldx;
     for (int64_t c = threadIdx.x; c < a.cols; c += 256) {
-        float t = (n_ld(x + c) - mean) * rstd;
-        if (a.w) t *= n_ld((const T *)a.w + c);
-        if (a.b) t += n_ld((const T *)a.b + c);
-        n_st(y + c, t);
+        float t = (load_f32(x + c) - mean) * rstd;
+        if (a.w) t *= load_f32((const T *)a.w + c);
+        if (a.b) t += load_f32((const T *)a.b + c);
+        store_canonical(y + c, t);
     }
 }
 
@@ -441,7 +391,7 @@ __global__ __launch_bounds__(256) void norm_bwd_generic_kernel(const NormArgs a)
     const float rstd = a.rstd[row], mean = a.rms ? 0.f : a.mean[row], inv_n = 1.0f / (float)a.cols;
     float s1 = 0.f, s2 = 0.f;
     for (int64_t c = threadIdx.x; c < a.cols; c += 256) {
-        const float g = n_ld(dy + c) * (a.w ? n_ld((const T *)a.w + c) : 1.f), xh = (n_ld(x + c) - mean) * rstd;
+        const float g = load_f32(dy + c) * (a.w ? load_f32((const T *)a.w + c) : 1.f), xh = (load_f32(x + c) - mean) * rstd;
         s1 += g;
         s2 += g * xh;
     }
@@ -449,8 +399,8 @@ __global__ __launch_bounds__(256) void norm_bwd_generic_kernel(const NormArgs a)
     s1 = a.rms ? 0.f : n_row_sum<256>(s1, red) * inv_n;
     T *dx = (T *)a.dx + row * a.ldx;
     for (int64_t c = threadIdx.x; c < a.cols; c += 256) {
-        const float g = n_ld(dy + c) * (a.w ? n_ld((const T *)a.w + c) : 1.f), xh = (n_ld(x + c) - mean) * rstd;
-        n_st(dx + c, rstd * (g - s1 - xh * s2));
+        const float g = load_f32(dy + c) * (a.w ? load_f32((const T *)a.w + c) : 1.f), xh = (load_f32(x + c) - mean) * rstd;
+        store_canonical(dx + c, rstd * (g - s1 - xh * s2));
     }
 }
 template <typename T>
@@ -459,13 +409,13 @@ __global__ __launch_bounds__(256) void norm_colsum_generic_kernel(const NormArgs
     if (c >= a.cols) return;
     float sw = 0.f, sb = 0.f;
     for (int64_t r = 0; r < a.rows; ++r) {
-        const float d = n_ld((const T *)a.dy + r * a.ldx + c);
-        const float xh = (n_ld((const T *)a.x + r * a.ldx + c) - (a.rms ? 0.f : a.mean[r])) * a.rstd[r];
+        const float d = load_f32((const T *)a.dy + r * a.ldx + c);
+        const float xh = (load_f32((const T *)a.x + r * a.ldx + c) - (a.rms ? 0.f : a.mean[r])) * a.rstd[r];
         sw += d * xh;
         sb += d;
     }
-    if (dw) n_st((T *)dw + c, sw);
-    if (db) n_st((T *)db + c, sb);
+    if (dw) store_canonical((T *)dw + c, sw);
+    if (db) store_canonical((T *)db + c, sb);
 }
 
 // the register-tile plan of a row: threads per row and packs per thread (0: generic kernel)
@@ -524,8 +474,41 @@ static int norm_bwd_launch(NormArgs &a, hipStream_t st, int &nblk) {
     constexpr int NT = TPR < 256 ? 256 : TPR, RPB = NT / TPR;
     const int64_t nrb = (a.rows + RPB - 1) / RPB;
     nblk = (int)std::min<int64_t>(nrb, resident);
-    norm_bwd_kernel<T, TPR, PACKS, RMS, PF><<<(unsigned)nblk, NT, 0, st>>>(a);
-    return KF_OK;
+    return launch(norm_bwd_kernel<T, TPR, PACKS, RMS, PF>, (unsigned)nblk, NT, 0, st, a);
+}
+
+// the plan as template arguments: f(NormTile<TPR, PACKS>{}) for the plan's (threads per row, packs per thread); one switch for the forward's
+// plans and one for the backward's, as norm_plan hands them out
+template <int TPR_, int PACKS_> struct NormTile { static constexpr int TPR = TPR_, PACKS = PACKS_; };
+template <typename F> static int norm_with_fwd_tile(const NormPlan &pl, F &&f) {
+    switch (pl.tpr * 100 + pl.packs) {
+    case 801: return f(NormTile<8, 1>{});
+    case 1601: return f(NormTile<16, 1>{});
+    case 3201: return f(NormTile<32, 1>{});
+    case 6401: return f(NormTile<64, 1>{});
+    case 6402: return f(NormTile<64, 2>{});
+    case 6404: return f(NormTile<64, 4>{});
+    case 25602: return f(NormTile<256, 2>{});
+    case 25604: return f(NormTile<256, 4>{});
+    case 25608: return f(NormTile<256, 8>{});
+    default: return f(NormTile<256, 16>{});
+    }
+}
+template <typename F> static int norm_with_bwd_tile(const NormPlan &pl, F &&f) {
+    switch (pl.tpr * 100 + pl.packs) {
+    case 801: return f(NormTile<8, 1>{});
+    case 1601: return f(NormTile<16, 1>{});
+    case 3201: return f(NormTile<32, 1>{});
+    case 6401: return f(NormTile<64, 1>{});
+    case 6402: return f(NormTile<64, 2>{});
+    case 6404: return f(NormTile<64, 4>{});
+    case 25601: return f(NormTile<256, 1>{});
+    case 25602: return f(NormTile<256, 2>{});
+    case 51201: return f(NormTile<512, 1>{});
+    case 51202: return f(NormTile<512, 2>{});
+    case 102401: return f(NormTile<1024, 1>{});
+    default: return f(NormTile<1024, 2>{});
+    }
 }
 
 } // namespace kf
@@ -540,35 +523,6 @@ static int norm_check(const char *who, int kind, int dtype, int64_t rows, int64_
     return KF_OK;
 }
 
-#define KF_NORM_DISPATCH(KERNEL, T, PL, ...)                                                     \
-    switch ((PL).tpr * 100 + (PL).packs) {                                                       \
-    case 801: KERNEL<T, 8, 1> __VA_ARGS__; break;                                                \
-    case 1601: KERNEL<T, 16, 1> __VA_ARGS__; break;                                              \
-    case 3201: KERNEL<T, 32, 1> __VA_ARGS__; break;                                              \
-    case 6401: KERNEL<T, 64, 1> __VA_ARGS__; break;                                              \
-    case 6402: KERNEL<T, 64, 2> __VA_ARGS__; break;                                              \
-    case 6404: KERNEL<T, 64, 4> __VA_ARGS__; break;                                              \
-    case 25602: KERNEL<T, 256, 2> __VA_ARGS__; break;                                            \
-    case 25604: KERNEL<T, 256, 4> __VA_ARGS__; break;                                            \
-    case 25608: KERNEL<T, 256, 8> __VA_ARGS__; break;                                            \
-    default: KERNEL<T, 256, 16> __VA_ARGS__; break;                                              \
-    }
-#define KF_NORM_DISPATCH_BWD(KERNEL, T, PL, RMS_, ...)                                           \
-    switch ((PL).tpr * 100 + (PL).packs) {                                                       \
-    case 801: KERNEL<T, 8, 1, RMS_> __VA_ARGS__; break;                                          \
-    case 1601: KERNEL<T, 16, 1, RMS_> __VA_ARGS__; break;                                        \
-    case 3201: KERNEL<T, 32, 1, RMS_> __VA_ARGS__; break;                                        \
-    case 6401: KERNEL<T, 64, 1, RMS_> __VA_ARGS__; break;                                        \
-    case 6402: KERNEL<T, 64, 2, RMS_> __VA_ARGS__; break;                                        \
-    case 6404: KERNEL<T, 64, 4, RMS_> __VA_ARGS__; break;                                        \
-    case 25601: KERNEL<T, 256, 1, RMS_> __VA_ARGS__; break;                                      \
-    case 25602: KERNEL<T, 256, 2, RMS_> __VA_ARGS__; break;                                      \
-    case 51201: KERNEL<T, 512, 1, RMS_> __VA_ARGS__; break;                                      \
-    case 51202: KERNEL<T, 512, 2, RMS_> __VA_ARGS__; break;                                      \
-    case 102401: KERNEL<T, 1024, 1, RMS_> __VA_ARGS__; break;                                    \
-    default: KERNEL<T, 1024, 2, RMS_> __VA_ARGS__; break;                                        \
-    }
-
 extern "C" int kf_norm_fwd(int kind, int dtype, int64_t rows, int64_t cols, int64_t ld, const void *x, const void *weight, const void *bias,
                            double eps, void *y, float *mean, float *rstd, void *stream) {
     int rc = norm_check("kf_norm_fwd", kind, dtype, rows, cols, ld);
@@ -582,19 +536,13 @@ extern "C" int kf_norm_fwd(int kind, int dtype, int64_t rows, int64_t cols, int6
     const NormPlan pl = norm_plan(dtype, cols, ld, ptrs, 4, false);
     if (pl.tpr == 0) {
         KF_PROF("norm_fwd_generic", st);
-        if (dtype == KF_F32) norm_fwd_generic_kernel<float><<<(unsigned)rows, 256, 0, st>>>(a);
-        else if (dtype == KF_BF16) norm_fwd_generic_kernel<bf16_t><<<(unsigned)rows, 256, 0, st>>>(a);
-        else norm_fwd_generic_kernel<f16_t><<<(unsigned)rows, 256, 0, st>>>(a);
-        KF_LAUNCH_CHECK();
-        return KF_OK;
+        return with_dtype(dtype, [&](auto t) { return launch(norm_fwd_generic_kernel<decltype(t)>, (unsigned)rows, 256, 0, st, a); });
     }
     const unsigned grid = (unsigned)((rows + (256 / pl.tpr) - 1) / (256 / pl.tpr));
     KF_PROF("norm_fwd", st);
-    if (dtype == KF_F32) { KF_NORM_DISPATCH(norm_fwd_kernel, float, pl, <<<grid, 256, 0, st>>>(a)) }
-    else if (dtype == KF_BF16) { KF_NORM_DISPATCH(norm_fwd_kernel, bf16_t, pl, <<<grid, 256, 0, st>>>(a)) }
-    else { KF_NORM_DISPATCH(norm_fwd_kernel, f16_t, pl, <<<grid, 256, 0, st>>>(a)) }
-    KF_LAUNCH_CHECK();
-    return KF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        return norm_with_fwd_tile(pl, [&](auto tile) { return launch(norm_fwd_kernel<decltype(t), tile.TPR, tile.PACKS>, grid, 256, 0, st, a); });
+    });
 }
 
 extern "C" int kf_norm_bwd_workspace_bytes(int kind, int dtype, int64_t rows, int64_t cols, int64_t ld, size_t *bytes) {
@@ -624,14 +572,11 @@ extern "C" int kf_norm_bwd(int kind, int dtype, int64_t rows, int64_t cols, int6
     const unsigned gc = (unsigned)((cols + 255) / 256);
     if (pl.tpr == 0) {
         KF_PROF("norm_bwd_generic", st);
-#define KF_NORM_GEN(T)                                                                    \
-    norm_bwd_generic_kernel<T><<<(unsigned)rows, 256, 0, st>>>(a);                        \
-    KF_LAUNCH_CHECK();                                                                    \
-    if (sums) norm_colsum_generic_kernel<T><<<gc, 256, 0, st>>>(a, dweight, dbias);
-        if (dtype == KF_F32) { KF_NORM_GEN(float) } else if (dtype == KF_BF16) { KF_NORM_GEN(bf16_t) } else { KF_NORM_GEN(f16_t) }
-#undef KF_NORM_GEN
-        KF_LAUNCH_CHECK();
-        return KF_OK;
+        return with_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            const int rg = launch(norm_bwd_generic_kernel<T>, (unsigned)rows, 256, 0, st, a);
+            return rg != KF_OK || !sums ? rg : launch(norm_colsum_generic_kernel<T>, gc, 256, 0, st, a, dweight, dbias);
+        });
     }
     int nblk = norm_bwd_blocks(pl, rows);
     if (sums) {
@@ -639,22 +584,17 @@ extern "C" int kf_norm_bwd(int kind, int dtype, int64_t rows, int64_t cols, int6
         KF_REQUIRE(workspace && workspace_bytes >= need, KF_ERR_WORKSPACE, "kf_norm_bwd: workspace of %zu bytes required, got %zu", need, workspace_bytes);
         a.part = (float *)workspace;
     }
-    {
-        KF_PROF("norm_bwd", st);
-#define KF_NB(T_)                                                                          \
-    if (a.rms) { KF_NORM_DISPATCH_BWD(norm_bwd_launch, T_, pl, true, (a, st, nblk)) }      \
-    else { KF_NORM_DISPATCH_BWD(norm_bwd_launch, T_, pl, false, (a, st, nblk)) }
-        if (dtype == KF_F32) { KF_NB(float) } else if (dtype == KF_BF16) { KF_NB(bf16_t) } else { KF_NB(f16_t) }
-#undef KF_NB
-        KF_LAUNCH_CHECK();
-    }
-    if (sums) {
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        {
+            KF_PROF("norm_bwd", st);
+            const int rb = with_flags([&](auto RMS) {
+                return norm_with_bwd_tile(pl, [&](auto tile) { return norm_bwd_launch<T, tile.TPR, tile.PACKS, RMS>(a, st, nblk); });
+            }, a.rms != 0);
+            if (rb != KF_OK) return rb;
+        }
+        if (!sums) return (int)KF_OK;
         KF_PROF("norm_bwd_fold", st);
-        const unsigned gf = (unsigned)((cols + 63) / 64);
-        if (dtype == KF_F32) norm_fold_kernel<float><<<gf, 256, 0, st>>>(a.part, nblk, cols, dweight, dbias);
-        else if (dtype == KF_BF16) norm_fold_kernel<bf16_t><<<gf, 256, 0, st>>>(a.part, nblk, cols, dweight, dbias);
-        else norm_fold_kernel<f16_t><<<gf, 256, 0, st>>>(a.part, nblk, cols, dweight, dbias);
-        KF_LAUNCH_CHECK();
-    }
-    return KF_OK;
+        return launch(norm_fold_kernel<T>, (unsigned)((cols + 63) / 64), 256, 0, st, a.part, nblk, cols, dweight, dbias);
+    });
 }

@@ -24,7 +24,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "float_pack.h"
 
 namespace kf {
 
@@ -60,53 +60,29 @@ struct AdamwArgs {
 };
 static_assert(sizeof(AdamwArgs) <= 4096, "kernel arguments above 4 KiB");
 
-template <typename T> __device__ __forceinline__ float ad_ld(const T *p) { return *p; }
-template <> __device__ __forceinline__ float ad_ld<bf16_t>(const bf16_t *p) { return bf16_to_f32(*p); }
-template <> __device__ __forceinline__ float ad_ld<f16_t>(const f16_t *p) { return f16_to_f32(*p); }
-template <typename T> __device__ __forceinline__ void ad_st(T *p, float v) { *p = v; }
-template <> __device__ __forceinline__ void ad_st<bf16_t>(bf16_t *p, float v) { p->x = (uint16_t)(f32x2_to_bf16x2_hw(v, 0.f) & 0xffffu); }
-template <> __device__ __forceinline__ void ad_st<f16_t>(f16_t *p, float v) { *p = f32_to_f16(v); }
-
-// pack k (8 elements) of a 16-byte-aligned stream
+// pack k (8 elements) of a 16-byte-aligned stream: one 16-byte pack of a 16-bit stream, two of an f32 one
 template <typename T>
 __device__ __forceinline__ void ad_ldv(const T *base, int64_t k, float (&f)[kAdamPack]) {
     const uint4 *q = (const uint4 *)base;
     if constexpr (sizeof(T) == 4) {
-        const uint4 a = q[2 * k], b = q[2 * k + 1];
-        f[0] = __uint_as_float(a.x); f[1] = __uint_as_float(a.y); f[2] = __uint_as_float(a.z); f[3] = __uint_as_float(a.w);
-        f[4] = __uint_as_float(b.x); f[5] = __uint_as_float(b.y); f[6] = __uint_as_float(b.z); f[7] = __uint_as_float(b.w);
-    } else {
-        const uint4 a = q[k];
-        const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+        float lo[4], hi[4];
+        unpack16<T>(q[2 * k], lo);
+        unpack16<T>(q[2 * k + 1], hi);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                f[2 * i] = __uint_as_float(w[i] << 16);
-                f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-            } else {
-                f[2 * i] = f16_to_f32(f16_t{(uint16_t)(w[i] & 0xffff)});
-                f[2 * i + 1] = f16_to_f32(f16_t{(uint16_t)(w[i] >> 16)});
-            }
-        }
+        for (int i = 0; i < 4; ++i) { f[i] = lo[i]; f[4 + i] = hi[i]; }
+    } else {
+        unpack16<T>(q[k], f);
     }
 }
 template <typename T>
 __device__ __forceinline__ void ad_stv(T *base, int64_t k, const float (&f)[kAdamPack]) {
     uint4 *q = (uint4 *)base;
     if constexpr (sizeof(T) == 4) {
-        q[2 * k] = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
-        q[2 * k + 1] = make_uint4(__float_as_uint(f[4]), __float_as_uint(f[5]), __float_as_uint(f[6]), __float_as_uint(f[7]));
+        const float lo[4] = {f[0], f[1], f[2], f[3]}, hi[4] = {f[4], f[5], f[6], f[7]};
+        q[2 * k] = pack16<T>(lo);
+        q[2 * k + 1] = pack16<T>(hi);
     } else {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                w[i] = f32x2_to_bf16x2_hw(f[2 * i], f[2 * i + 1]);
-            } else {
-                w[i] = (uint32_t)f32_to_f16(f[2 * i]).x | ((uint32_t)f32_to_f16(f[2 * i + 1]).x << 16);
-            }
-        }
-        q[k] = make_uint4(w[0], w[1], w[2], w[3]);
+        q[k] = pack16<T>(f);
     }
 }
 
@@ -159,13 +135,13 @@ __device__ __forceinline__ void ad_update_chunk(const AdamwArgs &a, int t, int64
     AdCoef c = ad_coef(a, t);
     const int tid = threadIdx.x;
     auto one = [&](int64_t i) __attribute__((always_inline)) {
-        const float gi = ad_ld(g + i) * c.gmul * clip;
+        const float gi = load_f32(g + i) * c.gmul * clip;
         float mi = m[i], vi = v[i];
-        const float pi = ad_elem(MASTER ? ms[i] : ad_ld(p + i), gi, mi, vi, c);
+        const float pi = ad_elem(MASTER ? ms[i] : load_f32(p + i), gi, mi, vi, c);
         m[i] = mi;
         v[i] = vi;
         if constexpr (MASTER) ms[i] = pi;
-        ad_st(p + i, pi);
+        store_hw(p + i, pi);
     };
     uint32_t r2 = 0, r4 = 0;
     bool have2 = false, have4 = false, ok = true;
@@ -254,8 +230,8 @@ __device__ __forceinline__ float ad_norm_chunk(const AdamwArgs &a, int t, int64_
     const int64_t head = std::min<int64_t>(n, (int64_t)(((16u - ((uint32_t)(uintptr_t)g & 15u)) & 15u) / (uint32_t)sizeof(G)));
     const int64_t nb = (n - head) / kAdamPack, t0 = head + nb * kAdamPack;
     if (ch == 0) {
-        if (tid < head) { const float x = ad_ld(g + tid) * gs; s += x * x; }
-        if (t0 + tid < n) { const float x = ad_ld(g + t0 + tid) * gs; s += x * x; }
+        if (tid < head) { const float x = load_f32(g + tid) * gs; s += x * x; }
+        if (t0 + tid < n) { const float x = load_f32(g + t0 + tid) * gs; s += x * x; }
     }
     constexpr int64_t CP = kAdamChunk / kAdamPack;
     constexpr int U = (int)(CP / kAdamBlock);
@@ -423,23 +399,20 @@ extern "C" int kf_adamw_step(const kf_adamw_tensor *tensors, int64_t n, double b
             KF_PROF("adamw_norm", st);
             for (int64_t gi = 0; gi < ng; ++gi) {
                 group(gi, a);
-                adamw_norm<<<kAdamNormGrid, kAdamBlock, 0, st>>>(a);
-                KF_LAUNCH_CHECK();
+                const int rc = launch(adamw_norm, kAdamNormGrid, kAdamBlock, 0, st, a);
+                if (rc != KF_OK) return rc;
             }
         }
         KF_PROF("adamw_fold", st);
-        adamw_fold<<<1, kAdamFoldThreads, 0, st>>>(partial, ng * kAdamNormGrid, max_grad_norm, coef, grad_norm);
-        KF_LAUNCH_CHECK();
+        const int rc = launch(adamw_fold, 1, kAdamFoldThreads, 0, st, partial, ng * kAdamNormGrid, max_grad_norm, coef, grad_norm);
+        if (rc != KF_OK) return rc;
     }
     KF_PROF("adamw_update", st);
     for (int64_t gi = 0; gi < ng; ++gi) {
         const int32_t chunks = group(gi, a);
-        if (!clip) {
-            adamw_advance<<<1, 64, 0, st>>>(a);
-            KF_LAUNCH_CHECK();
-        }
-        adamw_update<<<(unsigned)std::max<int32_t>(1, chunks), kAdamBlock, 0, st>>>(a);
-        KF_LAUNCH_CHECK();
+        int rc = clip ? KF_OK : launch(adamw_advance, 1, 64, 0, st, a);
+        if (rc == KF_OK) rc = launch(adamw_update, (unsigned)std::max<int32_t>(1, chunks), kAdamBlock, 0, st, a);
+        if (rc != KF_OK) return rc;
     }
     return KF_OK;
 }

@@ -22,7 +22,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "float_pack.h"
 
 // rope_rot's FMAs are written out, and nothing else may be fused: the packed and the element path must round alike, bit for bit
 #pragma clang fp contract(off)
@@ -35,52 +35,7 @@ constexpr int kRopeBlock = 256;   // four waves = four tokens in flight per bloc
 constexpr int kRopeU = 4;         // heads (rotation) / packs (copy) per lane with loads in flight before the first use
 constexpr int64_t kRopeMaxGrid = 1 << 20;
 
-template <typename T> struct RopePack { static constexpr int V = 16 / sizeof(T); };
-
-template <typename T>
-__device__ __forceinline__ void rope_unpack(const uint4 &p, float (&f)[RopePack<T>::V]) {
-    if constexpr (sizeof(T) == 4) {
-        f[0] = __uint_as_float(p.x); f[1] = __uint_as_float(p.y); f[2] = __uint_as_float(p.z); f[3] = __uint_as_float(p.w);
-    } else {
-        const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                f[2 * i] = __uint_as_float(w[i] << 16);
-                f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-            } else {
-                f[2 * i] = f16_to_f32(f16_t{(uint16_t)(w[i] & 0xffff)});
-                f[2 * i + 1] = f16_to_f32(f16_t{(uint16_t)(w[i] >> 16)});
-            }
-        }
-    }
-}
-// one rounding per element; the hardware bf16 converter keeps a NaN a NaN (a bad position must show)
-template <typename T>
-__device__ __forceinline__ uint4 rope_pack(const float (&f)[RopePack<T>::V]) {
-    uint4 p;
-    if constexpr (sizeof(T) == 4) {
-        p.x = __float_as_uint(f[0]); p.y = __float_as_uint(f[1]); p.z = __float_as_uint(f[2]); p.w = __float_as_uint(f[3]);
-    } else {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                w[i] = f32x2_to_bf16x2_hw(f[2 * i], f[2 * i + 1]);
-            } else {
-                w[i] = (uint32_t)f32_to_f16(f[2 * i]).x | ((uint32_t)f32_to_f16(f[2 * i + 1]).x << 16);
-            }
-        }
-        p.x = w[0]; p.y = w[1]; p.z = w[2]; p.w = w[3];
-    }
-    return p;
-}
-template <typename T> __device__ __forceinline__ float rope_ld(const T *p) { return (float)*p; }
-template <> __device__ __forceinline__ float rope_ld<bf16_t>(const bf16_t *p) { return bf16_to_f32(*p); }
-template <> __device__ __forceinline__ float rope_ld<f16_t>(const f16_t *p) { return f16_to_f32(*p); }
-template <typename T> __device__ __forceinline__ void rope_st(T *p, float v) { *p = (T)v; }
-template <> __device__ __forceinline__ void rope_st<bf16_t>(bf16_t *p, float v) { p->x = (uint16_t)f32x2_to_bf16x2_hw(v, 0.f); }
-template <> __device__ __forceinline__ void rope_st<f16_t>(f16_t *p, float v) { *p = f32_to_f16(v); }
+// stores: pack16 and store_hw, one rounding per element; the hardware bf16 converter keeps a NaN a NaN (a bad position must show)
 
 // y_a = x_a c - x_b s, y_b = x_b c + x_a s: the same expression in both paths, so the element path and the packed path agree bitwise
 __device__ __forceinline__ void rope_rot(float xa, float xb, float c, float s, float &ya, float &yb) {
@@ -112,7 +67,7 @@ __device__ __forceinline__ int64_t rope_token(const RopeArgs &a, int64_t tok, in
 // the packed path: 16-byte packs (see the file comment for the lane map)
 template <typename T, bool INTERLEAVED>
 __global__ __launch_bounds__(kRopeBlock) void rope_packed(const RopeArgs a) {
-    constexpr int V = RopePack<T>::V;
+    constexpr int V = kPack16<T>;
     const T *x = (const T *)a.x;
     T *y = (T *)a.y;
     const int lane = threadIdx.x & 63;
@@ -161,8 +116,8 @@ __global__ __launch_bounds__(kRopeBlock) void rope_packed(const RopeArgs a) {
                     const int64_t h = h0 + (int64_t)u * HP;
                     if (h < a.h_rot) {
                         float fa[V], fb[V], ga[V], gb[V];
-                        rope_unpack<T>(ra[u], fa);
-                        rope_unpack<T>(rb[u], fb);
+                        unpack16<T>(ra[u], fa);
+                        unpack16<T>(rb[u], fb);
                         if constexpr (INTERLEAVED) {
                             // pairs (2i, 2i + 1): pack a holds pairs 0 .. V/2 - 1 of the slot, pack b the rest
 #pragma unroll
@@ -175,8 +130,8 @@ __global__ __launch_bounds__(kRopeBlock) void rope_packed(const RopeArgs a) {
                             for (int k = 0; k < V; ++k) rope_rot(fa[k], fb[k], c[k], s[k], ga[k], gb[k]);
                         }
                         T *yh = y + yo + h * a.yh;
-                        *(uint4 *)(yh + ea) = rope_pack<T>(ga);
-                        *(uint4 *)(yh + eb) = rope_pack<T>(gb);
+                        *(uint4 *)(yh + ea) = pack16<T>(ga);
+                        *(uint4 *)(yh + eb) = pack16<T>(gb);
                     }
                 }
             }
@@ -229,10 +184,10 @@ __global__ __launch_bounds__(kRopeBlock) void rope_elem(const RopeArgs a) {
             const float c = ok ? a.cos[p * half + i] : __builtin_nanf(""), s = ok ? a.sin[p * half + i] * a.sign : __builtin_nanf("");
             const T *xh = x + xo + h * a.xh;
             float ya, yb;
-            rope_rot(rope_ld(xh + ia), rope_ld(xh + ib), c, s, ya, yb);
+            rope_rot(load_f32(xh + ia), load_f32(xh + ib), c, s, ya, yb);
             T *yh = y + yo + h * a.yh;
-            rope_st(yh + ia, ya);
-            rope_st(yh + ib, yb);
+            store_hw(yh + ia, ya);
+            store_hw(yh + ib, yb);
         }
         for (int64_t k = lane; k < ncopy; k += 64) {
             int64_t h, e;
@@ -290,23 +245,17 @@ extern "C" int kf_rope(int dtype, int64_t B, int64_t H, int64_t S, int64_t D, in
                         rope_aligned16(sin) && lx->batch % b16 == 0 && lx->head % b16 == 0 && lx->row % b16 == 0 && ly->batch % b16 == 0 &&
                         ly->head % b16 == 0 && ly->row % b16 == 0;
     const unsigned grid = (unsigned)std::min<int64_t>((tokens + kRopeBlock / 64 - 1) / (kRopeBlock / 64), kRopeMaxGrid);
-#define KF_ROPE_LAUNCH(KERNEL)                                                                                              \
-    do {                                                                                                                    \
-        if (dtype == KF_F32) { if (interleaved) KERNEL<float, true><<<grid, kRopeBlock, 0, st>>>(a); else KERNEL<float, false><<<grid, kRopeBlock, 0, st>>>(a); } \
-        else if (dtype == KF_BF16) { if (interleaved) KERNEL<bf16_t, true><<<grid, kRopeBlock, 0, st>>>(a); else KERNEL<bf16_t, false><<<grid, kRopeBlock, 0, st>>>(a); } \
-        else { if (interleaved) KERNEL<f16_t, true><<<grid, kRopeBlock, 0, st>>>(a); else KERNEL<f16_t, false><<<grid, kRopeBlock, 0, st>>>(a); } \
-    } while (0)
-    if (packed) {
-        KF_PROF("rope_packed", st);
-        KF_ROPE_LAUNCH(rope_packed);
-        KF_LAUNCH_CHECK();
-    } else {
-        KF_PROF("rope_elem", st);
-        KF_ROPE_LAUNCH(rope_elem);
-        KF_LAUNCH_CHECK();
-    }
-#undef KF_ROPE_LAUNCH
-    return KF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_flags([&](auto IL) {
+            if (packed) {
+                KF_PROF("rope_packed", st);
+                return launch(rope_packed<T, IL>, grid, kRopeBlock, 0, st, a);
+            }
+            KF_PROF("rope_elem", st);
+            return launch(rope_elem<T, IL>, grid, kRopeBlock, 0, st, a);
+        }, interleaved != 0);
+    });
 }
 
 extern "C" int kf_rope_table(double base, int64_t rotary_dim, int64_t rows, float *cos, float *sin, void *stream) {
@@ -318,7 +267,5 @@ extern "C" int kf_rope_table(double base, int64_t rotary_dim, int64_t rows, floa
     const int64_t n = rows * (rotary_dim / 2);
     const unsigned grid = (unsigned)std::min<int64_t>((n + kRopeBlock - 1) / kRopeBlock, kRopeMaxGrid);
     KF_PROF("rope_table", st);
-    rope_table_kernel<<<grid, kRopeBlock, 0, st>>>(base, rotary_dim, rows, cos, sin);
-    KF_LAUNCH_CHECK();
-    return KF_OK;
+    return launch(rope_table_kernel, grid, kRopeBlock, 0, st, base, rotary_dim, rows, cos, sin);
 }

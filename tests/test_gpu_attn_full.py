@@ -271,6 +271,16 @@ def test_generic_bf16_head_80(kv_len):
     assert "attn_full_fwd_generic" in labels and "attn_full_bwd_dkv_generic" in labels and not any("mfma" in n for n in labels)
 
 
+@pytest.mark.parametrize("kv_len", [None, [70, 5]])
+def test_generic_f16_head_40(kv_len):
+    """f16 at a head size the matrix-core kernels do not take: the generic kernels' third element type, held to the same 16-bit bounds"""
+    rng = np.random.default_rng(40)
+    q, k, v, go = inputs(rng, H.F16, 2, 2, 1, 33, 70, 40)
+    got, labels = profiled(lambda: run(H.F16, q, k, v, go, kv_len))
+    check16(H.F16, q, k, v, go, got, kv_len, "f16 D40")
+    assert {"attn_full_fwd_generic", "attn_full_bwd_dq_generic", "attn_full_bwd_dkv_generic"} <= labels and not any("mfma" in n for n in labels)
+
+
 # ---- determinism, graph capture ----
 def test_reproducible_and_capturable():
     rng = np.random.default_rng(513)

@@ -543,6 +543,7 @@ def test_dropping_a_bucket_frees_it_without_detach():
     w.set_requires_grad(True)
     x = kfunca.from_numpy(rng.uniform(-1, 1, (256, 256)).astype(np.float32), 0).bfloat16()
     g = kfunca.from_numpy(rng.uniform(-1, 1, (256, 256)).astype(np.float32), 0).bfloat16()
+    gc.collect()  # cyclic garbage of earlier tests must not be freed between the two counts (the collect below would take it along)
     before = kfunca.memstat_dict(0)["active_blocks"]
     bucket = kfunca.GradBucket([w], 64.0)
     bucket.attach()

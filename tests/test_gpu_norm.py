@@ -57,7 +57,8 @@ def test_golden_f32_forward_backward():
 
 @pytest.mark.parametrize("code,eps", [(H.BF16, 2.0 ** -7), (H.F16, 2.0 ** -10), (H.F32, 1e-5)])
 @pytest.mark.parametrize("rows,cols", [(3, 8), (70, 512), (33, 2048), (17, 4096), (9, 8192), (5, 16384), (2, 32768), (11, 1000), (6, 12288),
-                                       (1030, 16), (50, 32), (1000, 64), (333, 128), (77, 256), (41, 1536)])  # (8 / 16 / 32 lanes per row: several rows per wave)
+                                       (1030, 16), (50, 32), (1000, 64), (333, 128), (77, 256), (41, 1536),  # (8 / 16 / 32 lanes per row: several rows per wave)
+                                       (3, 33)])  # no whole number of packs in any dtype: the generic forward, backward and column sums
 def test_vs_oracle_every_plan(code, eps, rows, cols):
     """Every register-tile plan (one wave per row with 1 / 2 / 4 packs, one block per row with 2..16 packs), the generic kernels
     (row length not a multiple of the pack; rows beyond the backward's tile) and no-weight / no-bias forms, vs the oracle."""
@@ -132,7 +133,8 @@ def test_index_get_bit_exact(dt, cols):
     assert np.array_equal(got, O.index_get(table, idx)) and np.array_equal(got, table[idx])
 
 
-@pytest.mark.parametrize("cols", [200, 100, 4104])  # 16-byte packs (one block of columns), element-wise rows, packs in two column blocks
+# 16-byte packs (one block of columns), element-wise rows, packs in two column blocks; 260, 520, 1032: 65 and 129 packs per row (two and four packs per lane)
+@pytest.mark.parametrize("cols", [200, 100, 4104, 260, 520, 1032])
 @pytest.mark.parametrize("code", [H.F32, H.BF16, H.F16])
 def test_index_add_is_the_gathers_backward(code, cols):
     """dTable[r] = sum of the gradient rows whose index is r, in input order, f32 accumulation; heavy duplicates, negative
@@ -191,6 +193,35 @@ def test_index_add_drops_out_of_range_indices(nrows, n, cols):
             acc = acc + src[j]
         want[r] = acc
     assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("cols", [64, 100])  # 16-byte packs, element-wise rows
+@pytest.mark.parametrize("code", [H.F32, H.BF16, H.F16])
+def test_index_add_into_2_31_rows_sorts_64_bit_keys(code, cols):
+    """nrows = 2^31: neither the row numbers nor the out-of-range key nrows fit the 32-bit sort keys, so the add sorts int64 keys. Only rows that
+    are named are written, so the destination here holds the first 16 rows (and a guard band); same sums, in input order, bit for bit."""
+    rng = np.random.default_rng(230 + code + cols)
+    nrows, n, have, guard = 1 << 31, 600, 16, 8
+    idx = rng.integers(0, have, size=(n,)).astype(np.int64)
+    idx[:100] = 3
+    idx[idx == 11] = 12  # row 11 is named by nobody
+    idx[::50] = rng.choice(np.array([nrows, nrows + 5, 2 ** 40, -nrows - 1], dtype=np.int64), size=idx[::50].size)  # out of range: dropped
+    src = O.from_float(rng.uniform(-1, 1, (n, cols)).astype(np.float32), code)
+    bi, bs = H.DevBuf.from_numpy(idx), H.DevBuf.from_numpy(src)
+    dst = H.DevBuf.from_numpy(O.from_float(np.full((have + guard, cols), 5.0, dtype=np.float32), code))
+    ws = H.index_add(code, bi.ptr, n, bs.ptr, cols, nrows, dst.ptr)
+    H.device_sync()
+    del ws
+    got = O.to_float(dst.to_numpy((have + guard, cols), src.dtype), code)
+    want = np.full((have + guard, cols), 5.0, dtype=np.float32)
+    srcf = O.to_float(src, code)
+    for r in np.unique(idx[(idx >= 0) & (idx < have)]):
+        acc = np.zeros(cols, dtype=np.float32)
+        for j in np.nonzero(idx == r)[0]:  # input order, f32 adds: what the kernel does
+            acc = acc + srcf[j]
+        want[r] = acc
+    assert np.array_equal(got, O.to_float(O.from_float(want, code), code))
+    assert (got[11] == 5.0).all() and (got[have:] == 5.0).all()
 
 
 def test_index_add_long_index_list_takes_the_global_sort_with_skipped_passes():
