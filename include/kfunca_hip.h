@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table, kf_attn_fwd_gqa, kf_attn_bwd_gqa_workspace_bytes, kf_attn_bwd_gqa, kf_glu_fwd, kf_glu_bwd, KF_ACT_*, kf_attn_full_fwd, kf_attn_full_bwd_workspace_bytes, kf_attn_full_bwd):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
+#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table, kf_attn_fwd_gqa, kf_attn_bwd_gqa_workspace_bytes, kf_attn_bwd_gqa, kf_glu_fwd, kf_glu_bwd, KF_ACT_*, kf_attn_full_fwd, kf_attn_full_bwd_workspace_bytes, kf_attn_full_bwd, kf_softmax_fwd, kf_softmax_bwd, KF_SOFTMAX, KF_LOG_SOFTMAX):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
 
 /* ---- status ------------------------------------------------------------------------------ */
 enum {
@@ -600,6 +600,36 @@ int kf_glu_fwd(int act, int dtype, int64_t rows, int64_t F, const void *gate, in
                void *h, int64_t ldh, void *stream);
 int kf_glu_bwd(int act, int dtype, int64_t rows, int64_t F, const void *gate, int64_t ldg, const void *up, int64_t ldu,
                const void *dh, int64_t lddh, void *dgate, int64_t lddg, void *dup, int64_t lddu, void *stream);
+
+/* ---- row softmax and log_softmax (no reference counterpart: MoE routers, sampling, distillation, contrastive heads) ---- */
+enum { KF_SOFTMAX = 0, KF_LOG_SOFTMAX = 1 };
+/*
+ * x, y, dy, dx: [rows, V] row-major with leading dimensions in elements, each >= V; one dtype in {KF_F32, KF_BF16, KF_F16} for all of
+ * them; the arithmetic is f32 with one rounding per output element. Over the last dimension, with s = scale * x (scale finite, > 0:
+ * 1 / temperature) and lse = log sum_v exp(s_v):
+ *     KF_SOFTMAX       y_v = exp(s_v - lse)        dx_v = scale * y_v * (dy_v - sum_u dy_u y_u)
+ *     KF_LOG_SOFTMAX   y_v = s_v - lse             dx_v = scale * (dy_v - exp(y_v) * sum_u dy_u)
+ * The backward works from the forward's OUTPUT y: a caller keeps y, not x.
+ * Special values, as torch: a -inf element gives 0 (softmax) or -inf (log_softmax), and the formulas above for its gradient (0 for
+ * softmax, scale * dy_v for log_softmax); a row that holds a NaN or +inf, or only -inf, is NaN throughout; no other row is affected.
+ * Large logits (|s| ~ 1e4) keep f32 accuracy: the max is taken out inside one FMA and its rounding residual is folded back.
+ * Allowed aliases, bitwise equal to the out-of-place call: y == x with ldy == ldx (an in-place forward); dx == dy with lddx == lddy.
+ * Every other overlap of an output with an input is refused (column blocks of one wider buffer, whose rows interleave, do not overlap).
+ * Columns V .. ld of an output row are never written. Bases need the alignment of an element only: a row is read as a scalar head up to
+ * the first 16-byte boundary, 16-byte packs, and a scalar tail, so odd V and odd leading dimensions keep the vector access; where the
+ * rows of two operands sit differently against the 16-byte boundaries the call takes the element path, with the same bits. The order in
+ * which a row is summed depends on V and on the 16-byte phase of the row of x (y in the backward) only.
+ * Regimes, from (rows, V) alone: V <= 2048 one wave per row, 2048 < V <= 16384 one 256-thread block per row (the row - in the backward y
+ * and dy - in registers: read once, written once); longer rows one block per row in two passes (the online max and sum, or the row sum;
+ * then a re-read and the write). Row offsets are 64-bit (rows * ld may exceed 2^31); rows < 2^31. One launch, no workspace, no atomics, a
+ * fixed combination order: bitwise reproducible; no allocation, no synchronisation: calls can be captured with kf_graph_*. rows == 0 or
+ * V == 0 is KF_OK without a launch. Every argument is checked before any device call: KF_ERR_INVALID (kind, dtype, negative extents, a
+ * scale that is not finite and > 0, a null pointer, a leading dimension < V, a base not aligned to its element, an alias not listed).
+ */
+int kf_softmax_fwd(int kind, int dtype, int64_t rows, int64_t V, float scale, const void *x, int64_t ldx, void *y, int64_t ldy,
+                   void *stream);
+int kf_softmax_bwd(int kind, int dtype, int64_t rows, int64_t V, float scale, const void *y, int64_t ldy, const void *dy, int64_t lddy,
+                   void *dx, int64_t lddx, void *stream);
 
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128

@@ -14,6 +14,7 @@
 #include "comm.h"
 #include "device_api.h"
 #include "glu.h"
+#include "softmax.h"
 #include "ops.h"
 #include "optim.h"
 #include "rope.h"
@@ -423,6 +424,16 @@ PYBIND11_MODULE(_C, m) {
     m.def("silu", [](const Tensor &x) { return gpu::activation(KF_ACT_SILU, x); }, py::arg("x"));
     m.def("gelu", [gelu_kind](const Tensor &x, const std::string &approximate) { return gpu::activation(gelu_kind(approximate), x); },
           py::arg("x"), py::arg("approximate") = "none");
+    // the distribution over a dimension (an MoE router, sampling, distillation): one launch each way, the backward from the kept result
+    m.def("softmax", &gpu::softmax, py::arg("x"), py::arg("dim") = -1, py::arg("scale") = 1.0f,
+          "softmax(x, dim=-1, scale=1.0): exp(scale * x) normalised to sum 1 over dimension dim of a float, half or bfloat16 tensor, in f32 "
+          "with one rounding per element. scale (1 / temperature) must be finite and > 0. A -inf element gives 0; a row holding a NaN or "
+          "+inf, or only -inf, is NaN. The last dimension of a row-strided view is read in place; any other dim is moved last and back. "
+          "Differentiable: the backward keeps the result, not x.");
+    m.def("log_softmax", &gpu::log_softmax, py::arg("x"), py::arg("dim") = -1, py::arg("scale") = 1.0f,
+          "log_softmax(x, dim=-1, scale=1.0): scale * x - log(sum(exp(scale * x))) over dimension dim of a float, half or bfloat16 tensor, in "
+          "f32 with one rounding per element and no cancellation at large logits. scale (1 / temperature) must be finite and > 0. A -inf "
+          "element stays -inf; a row holding a NaN or +inf, or only -inf, is NaN. Differentiable: the backward keeps the result, not x.");
     // from_numpy for bfloat16: uint16 bit patterns in, a BFloat16 tensor out (the inverse of to_numpy's uint16 view)
     m.def("from_numpy_bf16", [](py::array array, int device) {
         CHECK_FAIL(array.dtype().kind() == 'u' && array.dtype().itemsize() == 2, "from_numpy_bf16 expects uint16 bit patterns");

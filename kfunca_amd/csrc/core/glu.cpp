@@ -2,6 +2,7 @@
 #include "glu.h"
 
 #include "device_api.h"
+#include "row_view.h"
 
 namespace gpu {
 
@@ -9,32 +10,6 @@ namespace {
 int code(ScalarType t) { return static_cast<int>(t); }
 bool glu_dtype_ok(ScalarType t) { return t == ScalarType::Float || t == ScalarType::Half || t == ScalarType::BFloat16; }
 
-// [rows, F] through a leading dimension: a unit stride along the last dim and one uniform row stride over the flattened leading dims
-struct RowView {
-    Tensor t;          // keeps the storage alive
-    int64_t rows, ld;
-};
-bool row_strided(const Tensor &t, int64_t F, int64_t &ld) {
-    const int n = t.dim();
-    if (n == 0 || (t.shape(n - 1) > 1 && t.stride(n - 1) != 1)) return false;
-    ld = -1;
-    int64_t inner = 1;   // rows spanned by the dims to the right of d
-    for (int d = n - 2; d >= 0; --d) {
-        if (t.shape(d) == 1) continue;
-        if (ld < 0) ld = t.stride(d);
-        else if (t.stride(d) != ld * inner) return false;
-        inner *= t.shape(d);
-    }
-    if (ld < 0) ld = F;   // one row
-    return ld >= F;
-}
-RowView rows_of(const Tensor &t) {
-    const int64_t F = t.shape(-1);
-    int64_t ld = 0;
-    if (row_strided(t, F, ld)) return {t, F ? t.numel() / F : 0, ld};
-    Tensor d = t.dense();
-    return {d, F ? d.numel() / F : 0, F};
-}
 char *at(const RowView &v, int64_t col) { return static_cast<char *>(v.t.data_ptr()) + col * v.t.element_size_in_bytes(); }
 
 // The backward of h = act(gate) * up recomputed from the kept inputs. packed: inputs = {x}, x = gate | up, one [..., 2F] gradient;

@@ -28,6 +28,7 @@ EPI_NONE, EPI_BIAS_ROW = range(2)
 NORM_RMS, NORM_LAYER = range(2)
 CE_NONE, CE_SUM, CE_MEAN = range(3)
 ACT_SILU, ACT_GELU_TANH, ACT_GELU_ERF = range(3)
+SOFTMAX, LOG_SOFTMAX = range(2)
 MAX_DIMS, MAX_TENSORS = 12, 8
 KF_OK, KF_ERR_HIP, KF_ERR_INVALID, KF_ERR_UNSUPPORTED, KF_ERR_INDEX_RANGE, KF_ERR_WORKSPACE, KF_ERR_COMM, KF_ERR_OOM = range(8)
 COMM_ID_BYTES = 128
@@ -50,6 +51,7 @@ EXPORTS = [
     "kf_adamw_workspace_bytes", "kf_adamw_step",
     "kf_rope", "kf_rope_table",
     "kf_glu_fwd", "kf_glu_bwd",
+    "kf_softmax_fwd", "kf_softmax_bwd",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
     "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa",
@@ -198,6 +200,8 @@ def lib():
         _lib.kf_rope_table.argtypes = [C.c_double, i64, i64, vp, vp, vp]
         _lib.kf_glu_fwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp]
         _lib.kf_glu_bwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+        _lib.kf_softmax_fwd.argtypes = [C.c_int, C.c_int, i64, i64, C.c_float, vp, i64, vp, i64, vp]
+        _lib.kf_softmax_bwd.argtypes = [C.c_int, C.c_int, i64, i64, C.c_float, vp, i64, vp, i64, vp, i64, vp]
         _lib.kf_comm_unique_id.argtypes = [C.c_char_p]
         _lib.kf_comm_init.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int, C.c_int]
         _lib.kf_comm_destroy.argtypes = [vp]
@@ -685,6 +689,17 @@ def glu_bwd(act, dtype, rows, F, gate, ldg, up, ldu, dh, lddh, dgate, lddg, dup=
     """Gated activation backward (kf_glu_bwd): dup = dh act(gate), dgate = dh up act'(gate), recomputed from gate and up (up = dup = None:
     dgate = dh act'(gate)). dgate may be gate and dup may be up (same leading dimension): the projection is overwritten with its gradient."""
     check(lib().kf_glu_bwd(act, dtype, rows, F, gate, ldg, up, ldu, dh, lddh, dgate, lddg, dup, lddu, stream))
+
+
+def softmax_fwd(kind, dtype, rows, V, scale, x, ldx, y, ldy, stream=None):
+    """Row softmax (kind = SOFTMAX) or log_softmax (LOG_SOFTMAX) of scale * x over the last dimension (kf_softmax_fwd) on [rows, V] operands
+    with leading dimensions in elements. y may be x (same leading dimension): in place."""
+    check(lib().kf_softmax_fwd(kind, dtype, rows, V, scale, x, ldx, y, ldy, stream))
+
+
+def softmax_bwd(kind, dtype, rows, V, scale, y, ldy, dy, lddy, dx, lddx, stream=None):
+    """The backward of softmax_fwd from its OUTPUT y and dy (kf_softmax_bwd). dx may be dy (same leading dimension)."""
+    check(lib().kf_softmax_bwd(kind, dtype, rows, V, scale, y, ldy, dy, lddy, dx, lddx, stream))
 
 
 def device_sync():
