@@ -545,6 +545,34 @@ int kf_attn_full_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, 
                      const void *d_o, const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk,
                      void *dv, const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Prefix-LM softmax attention: full attention inside a per-batch prefix, causal after it, with the optional per-batch key length of
+ * kf_attn_full_*. With prefix_len == NULL it is causal attention over a padded batch. Everything not said here - operands, grouped
+ * K/V heads, the layout rule, lse, the argument checks and their statuses (with this entry's name in kf_last_error()), zero B, Hq or
+ * Sq, capturability - is kf_attn_full_*'s contract. kv_len, prefix_len: int64 [B] on the device, or NULL.
+ *     len_b = clamp(kv_len[b], 0, Skv)       (kv_len == NULL: Skv)
+ *     pre_b = clamp(prefix_len[b], 0, Skv)   (prefix_len == NULL: 0)
+ *     query m sees key n   <=>   n < len_b  and  (n < pre_b  or  n <= m)
+ * The alignment is top-left with absolute indices, as in kf_attn_fwd; Sq and Skv may be in either size order. A batch with len_b == 0
+ * has o = 0 and lse = -inf and contributes zero to every gradient; with len_b >= 1 every query sees key 0. Rows n >= len_b of dk and
+ * dv are written as zeros, and so is a row n < len_b that no query sees (n >= pre_b and n >= Sq). K and V rows at n >= len_b are never
+ * read. No atomics: bitwise reproducible; with pre_b >= len_b for every batch the results have the bits of kf_attn_full_*'s.
+ * Kernels: the kernels of kf_attn_full_* compiled with the mask (it bounds the key tiles of a query block - min(len_b, max(pre_b,
+ * last query + 1)) -, starts the query tiles of a key block beyond the prefix at the block, skips tiles no lane of a wave sees and
+ * selects on the scores of the tiles the mask edge crosses). Profile labels attn_prefix_fwd_mfma_d64 / _d128,
+ * attn_prefix_bwd_dq_mfma_*, attn_prefix_bwd_dkv_mfma_*, attn_prefix_*_generic; the delta pre-pass is shared and keeps
+ * attn_full_bwd_delta (attn_full_bwd_delta_generic). The workspace is kf_attn_full_bwd_workspace_bytes' (delta), uninitialised.
+ */
+int kf_attn_prefix_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                       const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k,
+                       const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse,
+                       void *stream);
+int kf_attn_prefix_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                       const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k,
+                       const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo,
+                       const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk,
+                       const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- rotary position embeddings (no reference counterpart: the position signal between the QKV projection and attention) ---- */
 /*
  * x, y: [B, H, S, D] addressed by kf_attn_layout element strides of B, H, S; D is contiguous; dtype in {KF_F32, KF_BF16, KF_F16};

@@ -391,12 +391,22 @@ PYBIND11_MODULE(_C, m) {
     }, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none());
     m.def("causal_attention_gqa", &gpu::causal_attention_gqa, py::arg("q"), py::arg("k"), py::arg("v"));
     // full (non-causal) attention with an optional per-batch key length (Long [B]): encoder self-attention, cross-attention, padded batches
-    m.def("attention", [](const Tensor &q, const Tensor &k, const Tensor &v, py::object kv_len) {
-        return gpu::attention(q, k, v, kv_len.is_none() ? Tensor() : kv_len.cast<Tensor>());
-    }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kv_len") = py::none());
-    m.def("attention_qkv", [](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object kv_len) {
-        return gpu::attention_qkv(qkv, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>(), kv_len.is_none() ? Tensor() : kv_len.cast<Tensor>());
-    }, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none(), py::arg("kv_len") = py::none());
+    // causal = True: the prefix-LM mask (full inside prefix_len[b], causal after it; prefix_len = None: causal over a padded batch)
+    auto opt = [](const py::object &t) { return t.is_none() ? Tensor() : t.cast<Tensor>(); };
+    m.def("attention", [opt](const Tensor &q, const Tensor &k, const Tensor &v, py::object kv_len, bool causal, py::object prefix_len) {
+        return gpu::attention(q, k, v, opt(kv_len), causal, opt(prefix_len));
+    }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kv_len") = py::none(), py::arg("causal") = false, py::arg("prefix_len") = py::none(),
+          "Softmax attention of q [B, Hq, Sq, D] over k, v [B, Hkv, Skv, D]. kv_len: Long [B], batch b sees keys n < kv_len[b]. causal=True adds\n"
+          "the prefix-LM mask: query m sees key n iff n < kv_len[b] and (n < prefix_len[b] or n <= m), top-left aligned; prefix_len: Long [B]\n"
+          "or None (no prefix: causal attention over a padded batch), refused with causal=False. A plain causal call without lengths is\n"
+          "faster through causal_attention / causal_attention_gqa.");
+    m.def("attention_qkv", [opt](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object kv_len, bool causal,
+                                 py::object prefix_len) {
+        return gpu::attention_qkv(qkv, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>(), opt(kv_len), causal, opt(prefix_len));
+    }, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none(), py::arg("kv_len") = py::none(),
+          py::arg("causal") = false, py::arg("prefix_len") = py::none(),
+          "attention on the packed projection [B*S, (H + 2*kv_heads)*D] (columns q | k | v), read in place; the result is [B*S, H*D]. kv_len,\n"
+          "causal and prefix_len as in attention (Sq = Skv = S). A plain causal call without lengths is faster through causal_attention_qkv.");
     // rotary position embeddings: f64-accurate tables, and the rotation of q and k in place in the packed projection (one launch each way)
     m.def("rope_table", [](int64_t max_positions, int64_t rotary_dim, double base, int device) {
         auto [c, sn] = gpu::rope_table(max_positions, rotary_dim, base, device);

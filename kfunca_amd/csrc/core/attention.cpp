@@ -1,6 +1,7 @@
 // namespace gpu: the attention operators over the C ABI's attention entries - causal_attention, causal_attention_gqa and
 // causal_attention_qkv (ops.h; nn_ops.cpp:6-8 + the checks of causal_attention_kernel.cu:9-20), attention and attention_qkv (attn_full.h).
-// Three families of entries, one host path: check, plan the padding, pad, allocate, call, un-pad.
+// Four families of entries (the causal pair, full attention and its prefix-LM form), one host path: check, plan the padding, pad,
+// allocate, call, un-pad.
 #include <cmath>
 
 #include "allocator.h"
@@ -22,7 +23,11 @@ enum class Family {
     CausalMha, // kf_attn_fwd / kf_attn_bwd, their _scaled forms for padded operands, their _strided forms for the packed projection
     CausalGqa, // kf_attn_fwd_gqa / kf_attn_bwd_gqa: query head h reads K/V head h / (Hq / Hkv)
     Full,      // kf_attn_full_fwd / kf_attn_full_bwd: no mask but an optional per-batch key length
+    Prefix,    // kf_attn_prefix_fwd / kf_attn_prefix_bwd: Full's operands and checks; causal beyond an optional per-batch prefix
 };
+bool full_like(Family f) { return f == Family::Full || f == Family::Prefix; }
+// the length arrays of attention / attention_qkv: undefined tensors for the other families
+struct Lens { Tensor kv, prefix; };
 
 // One call as the C ABI takes it: the sizes handed down (padded ones where the host pads), the scale of the REAL head size, and the
 // layouts of q, k, v and their gradients (lx) and of out and its gradient (lo); NULL: contiguous [B, H, S, D].
@@ -31,7 +36,7 @@ struct Call {
     int dt, device;
     int64_t B, Hq, Hkv, Sq, Skv, D;
     float scale;
-    const int64_t *kv_len;
+    const int64_t *kv_len, *prefix_len;
     const kf_attn_layout *lx, *lo;
     bool padded;
 };
@@ -49,6 +54,9 @@ void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o
         break;
     case Family::Full:
         DEV_CALL(kf_attn_full_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        break;
+    case Family::Prefix:
+        DEV_CALL(kf_attn_prefix_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.prefix_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
         break;
     }
 }
@@ -71,6 +79,10 @@ void run_bwd(const Call &c, const void *q, const void *k, const void *v, const v
     case Family::Full:
         DEV_CALL(kf_attn_full_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq, c.lx,
                                   dk, c.lx, dv, c.lx, ws, bytes, st));
+        break;
+    case Family::Prefix:
+        DEV_CALL(kf_attn_prefix_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.prefix_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go,
+                                    c.lo, dq, c.lx, dk, c.lx, dv, c.lx, ws, bytes, st));
         break;
     }
 }
@@ -101,6 +113,7 @@ DataPtr bwd_scratch(const Call &c, size_t &bytes) {
         DEV_CALL(kf_attn_bwd_gqa_workspace_bytes(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, &need, &floor_));
         break;
     case Family::Full: // one size, no smaller form to retry with
+    case Family::Prefix:
         DEV_CALL(kf_attn_full_bwd_workspace_bytes(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, &bytes));
         return DeviceAllocator::GetInstance()->allocate(bytes > 0 ? bytes : 1, c.device);
     }
@@ -109,7 +122,7 @@ DataPtr bwd_scratch(const Call &c, size_t &bytes) {
 
 // The refusals of causal_attention_gqa and attention carry their operator's name; causal_attention's carry no text but the dtype's.
 void check_operands(Family f, const Tensor &q, const Tensor &k, const Tensor &v) {
-    const char *op = f == Family::Full ? "attention" : "causal_attention_gqa";
+    const char *op = full_like(f) ? "attention" : "causal_attention_gqa";
     auto text = [&](auto... parts) { return f == Family::CausalMha ? std::string() : utils::concat(op, parts...); };
     CHECK_FAIL(q.defined() && k.defined() && v.defined() && q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
                text(" expects q [B, Hq, Sq, D] and k, v [B, Hkv, Skv, D]"));
@@ -118,21 +131,22 @@ void check_operands(Family f, const Tensor &q, const Tensor &k, const Tensor &v)
                text(": the K/V head count ", k.shape(1), " must divide the query head count ", q.shape(1)));
     CHECK_FAIL(q.dtype() == k.dtype() && q.dtype() == v.dtype(), text(": q, k, v must share a dtype"));
     CHECK_FAIL(q.dtype() == ScalarType::Float || h16(q.dtype()),
-               f == Family::Full ? std::string("attention supports float, half and bfloat16") : utils::concat("Unsupported ScalarType ", q.dtype()));
-    if (f == Family::Full) {
+               full_like(f) ? std::string("attention supports float, half and bfloat16") : utils::concat("Unsupported ScalarType ", q.dtype()));
+    if (full_like(f)) {
         CHECK_FAIL(q.shape(3) >= 1 && q.shape(3) <= 256, "attention: head size ", q.shape(3), " outside [1, 256]");
         CHECK_FAIL(k.shape(2) >= 1, "attention: keys are empty");
     }
     CHECK_FAIL(q.is_dense() && k.is_dense() && v.is_dense(), text(" expects dense tensors"));
     CHECK_FAIL(q.device() == k.device() && q.device() == v.device(), text(": q, k, v must be on one device"));
 }
-// the kernels read kv_len as a dense int64 array
-Tensor check_len(const Tensor &kv_len, int64_t B, int device) {
+// the kernels read kv_len and prefix_len as dense int64 arrays
+Tensor check_len(const Tensor &kv_len, int64_t B, int device, const char *name = "kv_len") {
     if (!kv_len.defined()) return Tensor();
-    CHECK_FAIL(kv_len.dtype() == ScalarType::Long, "attention: kv_len must be of type Long");
-    CHECK_FAIL(kv_len.numel() == B && kv_len.device() == device, "attention: kv_len must hold B = ", B, " elements on the operands' device");
+    CHECK_FAIL(kv_len.dtype() == ScalarType::Long, "attention: ", name, " must be of type Long");
+    CHECK_FAIL(kv_len.numel() == B && kv_len.device() == device, "attention: ", name, " must hold B = ", B, " elements on the operands' device");
     return kv_len.dense();
 }
+Lens check_lens(const Lens &l, int64_t B, int device) { return {check_len(l.kv, B, device), check_len(l.prefix, B, device, "prefix_len")}; }
 const int64_t *len_ptr(const Tensor &kv_len) { return kv_len.defined() ? static_cast<const int64_t *>(kv_len.data_ptr()) : nullptr; }
 
 // The extents handed down. The MFMA kernels want D = 64 or 128 (and, f32, whole tiles of 32 rows); everything else takes the generic
@@ -145,7 +159,7 @@ struct PadPlan { int64_t Sq, Skv, D; };
 PadPlan pad_plan(Family f, const Tensor &q, const Tensor &k) {
     const int64_t Sq = q.shape(2), Skv = k.shape(2), D = q.shape(3);
     PadPlan p{Sq, Skv, D};
-    if (f == Family::Full) {
+    if (full_like(f)) {
         if (h16(q.dtype()) && D != 64 && D <= 128) p.D = D < 64 ? 64 : 128;
         return p;
     }
@@ -172,13 +186,13 @@ Tensor unpad(const Tensor &t, int64_t rows, int64_t cols) {
     return v.dense();
 }
 
-Call contiguous_call(Family f, const Tensor &q, const Tensor &k, const PadPlan &pp, const Tensor &kv_len) {
+Call contiguous_call(Family f, const Tensor &q, const Tensor &k, const PadPlan &pp, const Lens &len) {
     const bool padded = pp.Sq != q.shape(2) || pp.Skv != k.shape(2) || pp.D != q.shape(3);
     return {f, code(q.dtype()), q.device(), q.shape(0), q.shape(1), k.shape(1), pp.Sq, pp.Skv, pp.D, 1.0f / std::sqrt((float)q.shape(3)),
-            len_ptr(kv_len), nullptr, nullptr, padded};
+            len_ptr(len.kv), len_ptr(len.prefix), nullptr, nullptr, padded};
 }
 
-std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len) {
+std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len) {
     const int64_t B = q.shape(0), Hq = q.shape(1), Sq = q.shape(2), D = q.shape(3);
     if (f == Family::CausalGqa) {
         if (q.numel() == 0) return {empty_like(q), empty({B, Hq, Sq}, ScalarType::Float, q.device())};
@@ -188,14 +202,14 @@ std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Te
     Tensor qp = pad(q, pp.Sq, pp.D), kp = pad(k, pp.Skv, pp.D), vp = pad(v, pp.Skv, pp.D);
     Tensor outp = empty_like(qp);
     Tensor lsep = empty({B, Hq, pp.Sq}, ScalarType::Float, q.device());
-    run_fwd(contiguous_call(f, q, k, pp, kv_len), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), outp.data_ptr(), static_cast<float *>(lsep.data_ptr()));
+    run_fwd(contiguous_call(f, q, k, pp, len), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), outp.data_ptr(), static_cast<float *>(lsep.data_ptr()));
     return {unpad(outp, Sq, D), unpad(lsep, Sq, 0)};
 }
 
-std::tuple<Tensor, Tensor, Tensor> attention_backward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, const Tensor &out,
+std::tuple<Tensor, Tensor, Tensor> attention_backward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len, const Tensor &out,
                                                       const Tensor &lse, const Tensor &grad_out) {
     if (f == Family::CausalMha) check_operands(f, q, k, v); // causal_attention_bwd is an operator of its own (ops.h)
-    CHECK_FAIL(grad_out.sizes() == q.sizes() && grad_out.dtype() == q.dtype(), f == Family::Full ? "attention: the gradient does not match the output" : "");
+    CHECK_FAIL(grad_out.sizes() == q.sizes() && grad_out.dtype() == q.dtype(), full_like(f) ? "attention: the gradient does not match the output" : "");
     const int64_t Sq = q.shape(2), Skv = k.shape(2), D = q.shape(3);
     if (f == Family::CausalGqa && (q.numel() == 0 || k.numel() == 0)) // nothing attends: every gradient is zero
         return {zeros(q.sizes(), q.dtype(), q.device()), zeros(k.sizes(), k.dtype(), k.device()), zeros(v.sizes(), v.dtype(), v.device())};
@@ -203,9 +217,9 @@ std::tuple<Tensor, Tensor, Tensor> attention_backward(Family f, const Tensor &q,
     Tensor qp = pad(q, pp.Sq, pp.D), kp = pad(k, pp.Skv, pp.D), vp = pad(v, pp.Skv, pp.D), op = pad(out, pp.Sq, pp.D);
     Tensor lp = pad(lse, pp.Sq, 0), gp = pad(grad_out.dense(), pp.Sq, pp.D);
     Tensor dqp = empty_like(qp), dkp = empty_like(kp), dvp = empty_like(vp);
-    if (f == Family::Full && dqp.numel() == 0) // no query: dk and dv are zero
+    if (full_like(f) && dqp.numel() == 0) // no query: dk and dv are zero
         return {unpad(dqp, Sq, D), unpad(zeros(kp.sizes(), k.dtype(), k.device()), Skv, D), unpad(zeros(vp.sizes(), v.dtype(), v.device()), Skv, D)};
-    const Call c = contiguous_call(f, q, k, pp, kv_len);
+    const Call c = contiguous_call(f, q, k, pp, len);
     size_t bytes = 0;
     DataPtr scratch = bwd_scratch(c, bytes);
     run_bwd(c, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), static_cast<const float *>(lp.data_ptr()), gp.data_ptr(), dqp.data_ptr(),
@@ -215,24 +229,25 @@ std::tuple<Tensor, Tensor, Tensor> attention_backward(Family f, const Tensor &q,
 
 class AttentionGradFunction : public GradFunction {
 public:
-    AttentionGradFunction(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, const Tensor &out, const Tensor &lse)
-        : family_(f), kv_len_(kv_len), out_(out), lse_(lse) {
+    AttentionGradFunction(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len, const Tensor &out, const Tensor &lse)
+        : family_(f), len_(len), out_(out), lse_(lse) {
         inputs = {q, k, v};
     }
     std::vector<Tensor> backward(Tensor g) override {
-        auto [dq, dk, dv] = attention_backward(family_, inputs[0], inputs[1], inputs[2], kv_len_, out_, lse_, g);
+        auto [dq, dk, dv] = attention_backward(family_, inputs[0], inputs[1], inputs[2], len_, out_, lse_, g);
         return {dq, dk, dv};
     }
 
 private:
     Family family_;
-    Tensor kv_len_, out_, lse_;
+    Lens len_;
+    Tensor out_, lse_;
 };
 
-// kv_len is checked and made dense once; the backward keeps that tensor
-Tensor contiguous_attention(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len) {
+// kv_len and prefix_len are checked and made dense once; the backward keeps those tensors
+Tensor contiguous_attention(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &lens) {
     check_operands(f, q, k, v);
-    const Tensor len = check_len(kv_len, q.shape(0), q.device());
+    const Lens len = check_lens(lens, q.shape(0), q.device());
     auto [out, lse] = attention_forward(f, q, k, v, len);
     out.set_requires_grad(q.requires_grad() || k.requires_grad() || v.requires_grad());
     if (out.requires_grad()) out.set_grad_fn(new AttentionGradFunction(f, q, k, v, len, out, lse));
@@ -246,15 +261,15 @@ PackedLay packed_layouts(int64_t S, int64_t H, int64_t Hkv, int64_t D) {
     return {{S * W, D, W}, {S * d, D, d}};
 }
 // family CausalMha is Hkv = H here: K at column H D, V at 2 H D (the strided entries); otherwise K at H D, V at (H + Hkv) D
-Call packed_call(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D, const PackedLay &L, const Tensor &kv_len) {
-    return {f, code(qkv.dtype()), qkv.device(), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), len_ptr(kv_len), &L.qkv, &L.flat, false};
+Call packed_call(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D, const PackedLay &L, const Lens &len) {
+    return {f, code(qkv.dtype()), qkv.device(), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), len_ptr(len.kv), len_ptr(len.prefix), &L.qkv, &L.flat, false};
 }
 
 class PackedAttentionGradFunction : public GradFunction {
 public:
-    PackedAttentionGradFunction(Family f, const Tensor &qkv, const Tensor &kv_len, const Tensor &out, const Tensor &lse, int64_t B, int64_t S, int64_t H,
+    PackedAttentionGradFunction(Family f, const Tensor &qkv, const Lens &len, const Tensor &out, const Tensor &lse, int64_t B, int64_t S, int64_t H,
                                 int64_t Hkv)
-        : family_(f), kv_len_(kv_len), out_(out), lse_(lse), B_(B), S_(S), H_(H), Hkv_(Hkv) {
+        : family_(f), len_(len), out_(out), lse_(lse), B_(B), S_(S), H_(H), Hkv_(Hkv) {
         inputs = {qkv};
     }
     std::vector<Tensor> backward(Tensor g) override { // one packed gradient; dk, dv summed over each group
@@ -263,7 +278,7 @@ public:
         Tensor gc = g.dense();
         Tensor dqkv = empty(qkv.sizes(), qkv.dtype(), qkv.device());
         const PackedLay L = packed_layouts(S_, H_, Hkv_, D);
-        const Call c = packed_call(family_, qkv, B_, S_, H_, Hkv_, D, L, kv_len_);
+        const Call c = packed_call(family_, qkv, B_, S_, H_, Hkv_, D, L, len_);
         const char *p = static_cast<const char *>(qkv.data_ptr());
         char *gp = static_cast<char *>(dqkv.data_ptr());
         size_t bytes = 0;
@@ -275,20 +290,22 @@ public:
 
 private:
     Family family_;
-    Tensor kv_len_, out_, lse_;
+    Lens len_;
+    Tensor out_, lse_;
     int64_t B_, S_, H_, Hkv_;
 };
 
-// f: CausalMha for causal_attention_qkv(qkv, B, S, H) (Hkv = H, the [B*S, 3*H*D] texts), CausalGqa for its kv_heads form, Full for attention_qkv
-Tensor packed_attention(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, const Tensor &kv_len) {
-    const char *op = f == Family::Full ? "attention_qkv" : "causal_attention_qkv";
+// f: CausalMha for causal_attention_qkv(qkv, B, S, H) (Hkv = H, the [B*S, 3*H*D] texts), CausalGqa for its kv_heads form, Full and Prefix
+// for attention_qkv
+Tensor packed_attention(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, const Lens &lens) {
+    const char *op = full_like(f) ? "attention_qkv" : "causal_attention_qkv";
     CHECK_FAIL(qkv.defined() && qkv.dim() == 2 && qkv.is_dense(), op,
                f == Family::CausalMha ? " expects a contiguous [B*S, 3*H*D] tensor" : " expects a contiguous [B*S, (H + 2*kv_heads)*D] tensor");
     if (f == Family::CausalMha) {
         CHECK_FAIL(B > 0 && S > 0 && H > 0 && qkv.shape(0) == B * S && qkv.shape(1) % (3 * H) == 0, "causal_attention_qkv: shape does not match B, S, H");
     } else {
         CHECK_FAIL(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, op, ": kv_heads ", Hkv, " must divide H ", H);
-        CHECK_FAIL(qkv.shape(0) == B * S && (f != Family::Full || qkv.shape(1) > 0) && qkv.shape(1) % (H + 2 * Hkv) == 0, op,
+        CHECK_FAIL(qkv.shape(0) == B * S && (!full_like(f) || qkv.shape(1) > 0) && qkv.shape(1) % (H + 2 * Hkv) == 0, op,
                    ": shape does not match B, S, H, kv_heads");
     }
     const int64_t D = qkv.shape(1) / (H + 2 * Hkv), d = H * D, dkv = Hkv * D;
@@ -298,10 +315,10 @@ Tensor packed_attention(Family f, const Tensor &qkv, int64_t B, int64_t S, int64
         const int64_t nh[3] = {H, Hkv, Hkv};
         std::vector<Tensor> heads;
         for (int i = 0; i < 3; ++i) heads.push_back(parts[i].dense().view({B, S, nh[i], D}).permute({0, 2, 1, 3}).dense());
-        Tensor a = contiguous_attention(f, heads[0], heads[1], heads[2], kv_len);
+        Tensor a = contiguous_attention(f, heads[0], heads[1], heads[2], lens);
         return a.permute({0, 2, 1, 3}).dense().view({B * S, d});
     }
-    const Tensor len = check_len(kv_len, B, qkv.device());
+    const Lens len = check_lens(lens, B, qkv.device());
     const int64_t es = qkv.element_size_in_bytes();
     Tensor out = empty({B * S, d}, qkv.dtype(), qkv.device());
     Tensor lse = empty({B, H, S}, ScalarType::Float, qkv.device());
@@ -319,23 +336,30 @@ Tensor packed_attention(Family f, const Tensor &qkv, int64_t B, int64_t S, int64
 
 std::tuple<Tensor, Tensor> causal_attention_fwd(const Tensor &q, const Tensor &k, const Tensor &v) {
     check_operands(Family::CausalMha, q, k, v);
-    return attention_forward(Family::CausalMha, q, k, v, Tensor());
+    return attention_forward(Family::CausalMha, q, k, v, Lens());
 }
 std::tuple<Tensor, Tensor, Tensor> causal_attention_bwd(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &out, const Tensor &lse,
                                                         const Tensor &grad_out) {
-    return attention_backward(Family::CausalMha, q, k, v, Tensor(), out, lse, grad_out);
+    return attention_backward(Family::CausalMha, q, k, v, Lens(), out, lse, grad_out);
 }
-Tensor causal_attention(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalMha, q, k, v, Tensor()); }
-Tensor causal_attention_gqa(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalGqa, q, k, v, Tensor()); }
-Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len) { return contiguous_attention(Family::Full, q, k, v, kv_len); }
+Tensor causal_attention(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalMha, q, k, v, Lens()); }
+Tensor causal_attention_gqa(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalGqa, q, k, v, Lens()); }
+// causal = false is the full family's path, call for call; a prefix belongs to the causal mask
+static Family masked_family(const char *op, bool causal, const Tensor &prefix_len) {
+    CHECK_FAIL(causal || !prefix_len.defined(), op, ": prefix_len needs causal = true (without the causal mask every key is visible already)");
+    return causal ? Family::Prefix : Family::Full;
+}
+Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, bool causal, const Tensor &prefix_len) {
+    return contiguous_attention(masked_family("attention", causal, prefix_len), q, k, v, {kv_len, prefix_len});
+}
 
-Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H) { return packed_attention(Family::CausalMha, qkv, B, S, H, H, Tensor()); }
+Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H) { return packed_attention(Family::CausalMha, qkv, B, S, H, H, Lens()); }
 Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads) {
-    if (kv_heads >= 0 && kv_heads != H) return packed_attention(Family::CausalGqa, qkv, B, S, H, kv_heads, Tensor());
+    if (kv_heads >= 0 && kv_heads != H) return packed_attention(Family::CausalGqa, qkv, B, S, H, kv_heads, Lens());
     return causal_attention_qkv(qkv, B, S, H);
 }
-Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len) {
-    return packed_attention(Family::Full, qkv, B, S, H, kv_heads < 0 ? H : kv_heads, kv_len);
+Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len, bool causal, const Tensor &prefix_len) {
+    return packed_attention(masked_family("attention_qkv", causal, prefix_len), qkv, B, S, H, kv_heads < 0 ? H : kv_heads, {kv_len, prefix_len});
 }
 
 } // namespace gpu

@@ -23,6 +23,15 @@
 //  * generic path (f32; 16-bit with D <= 256 other than 64 and 128; bases that are not 16-byte aligned): plain vector-ALU kernels,
 //    one workgroup per output row, f32 accumulation, the same semantics. They are meant to be correct, not fast; an f32 matrix-core
 //    tier is out of scope.
+//
+// The prefix-LM variant (kf_attn_prefix_*: full inside a per-batch prefix, causal after it; no prefix: causal over a padded batch) is
+// the same kernels compiled with CAUSAL:
+//   pre_b = clamp(prefix_len[b], 0, Skv)   (prefix_len == NULL: 0);   query m sees key n  <=>  n < len_b and (n < pre_b or n <= m)
+// top-left aligned with absolute indices, Sq and Skv in either size order. The mask enters a kernel as a loop bound or tile skip
+// (key_bound, the per-wave skips, the dK/dV start tile t0), as the choice of the masked tile body, and as one compare-and-select per
+// score inside it; besides that only the assignment of blocks to workgroups differs (block_of), which no result depends on. With
+// pre_b >= len_b every choice is kf_attn_full_*'s and the results have its bits. The instantiations without CAUSAL are the code they
+// were before the variant existed.
 // No kernel uses atomics; every result is bitwise reproducible run to run.
 #include <math.h>
 
@@ -53,6 +62,7 @@ struct FullArgs {
     int G;               // query heads per K/V head
     float scale;
     Lay lq, lk, lv, lo, ldo, ldq, ldk, ldv;
+    const int64_t *prefix_len; // [B] on the device, or null (the prefix-LM variant only; last, so no other member moves)
 };
 
 __device__ __forceinline__ int64_t key_len(const FullArgs &a, int64_t b) {
@@ -60,6 +70,14 @@ __device__ __forceinline__ int64_t key_len(const FullArgs &a, int64_t b) {
     const int64_t l = a.kv_len[b];
     return l < 0 ? 0 : (l > a.Skv ? a.Skv : l);
 }
+
+// the prefix-LM variant (kf_attn_prefix_*): keys n < pre_b are visible to every query, the others to queries m >= n
+__device__ __forceinline__ int64_t prefix_of(const FullArgs &a, int64_t b) {
+    if (!a.prefix_len) return 0;
+    const int64_t l = a.prefix_len[b];
+    return l < 0 ? 0 : (l > a.Skv ? a.Skv : l);
+}
+__device__ __forceinline__ int clamp_i(int64_t v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : (int)v); }
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
@@ -232,14 +250,45 @@ __device__ __forceinline__ void t_store(const TileRegs<D> &r, char *slot) {
     }
 }
 
+// forward / dQ: keys the workgroup of query block xb walks (tiles 0 .. ceil(bound / 64) - 1, ascending). The prefix-LM variant stops
+// at the last key one of its queries can see: min(len, max(pre, min(Sq, xb 128 + 128)))
+// Which block of its (batch, head) a workgroup takes. Under the causal mask a block's work grows (forward, dQ) or shrinks (dK/dV)
+// with its index, and the hardware deals consecutive workgroup ids round-robin to XCDs and shader engines: with block = id % n the
+// heavy blocks of every head land on the same engines and the light ones on the others, and the kernel takes as long as without the
+// mask. Rotating the blocks of each (batch, head) by a hash of its index gives every engine every block size. The results do not
+// depend on which workgroup computes a block.
+template <bool CAUSAL>
+__device__ __forceinline__ int64_t block_of(int64_t pos, int64_t group, int64_t n) {
+    if constexpr (!CAUSAL) return pos;
+    return (pos + (int64_t)(((uint32_t)group * 2654435761u) >> 16)) % n;
+}
+
+// rows of the tile at kv0 that the query of lane xl of the wave at qw sees: min(len, max(pre, qw + xl + 1)) - kv0, clamped to the tile.
+// Everything but the last step is wave-uniform (scalar); the clamp of qw + 1 - kv0 keeps it in 32 bits without changing the result.
+__device__ __forceinline__ int tile_lim(int64_t len, int64_t pre, int64_t qw, int64_t kv0, int xl) {
+    const int nl = clamp_i(len - kv0, 0, TK), np = clamp_i(pre - kv0, 0, TK), dq1 = clamp_i(qw + 1 - kv0, -32, TK);
+    const int dm1 = dq1 + xl;
+    return min(nl, max(np, dm1));
+}
+
+template <bool CAUSAL>
+__device__ __forceinline__ int64_t key_bound(const FullArgs &a, int64_t len, int64_t pre, int64_t xb) {
+    if constexpr (!CAUSAL) return len;
+    const int64_t qe = a.Sq < xb * TQ + TQ ? a.Sq : xb * TQ + TQ, vis = pre > qe ? pre : qe;
+    return len < vis ? len : vis;
+}
+
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
-// S^T = K Q^T (A = K rows from LDS, B = Q fragments in registers), online softmax with a deferred running maximum. MASK: the last
-// tile of a batch whose key count is no multiple of 64 - keys at kv0 + row >= len get -inf (their K rows are zeros in LDS)
-template <bool BF, bool MASK, int D>
+// S^T = K Q^T (A = K rows from LDS, B = Q fragments in registers), online softmax with a deferred running maximum. MASK 1: the last
+// tile of a batch whose key count is no multiple of 64 - keys at kv0 + row >= len get -inf (their K rows are zeros in LDS). MASK 2
+// (prefix-LM variant): the keys a query sees are a leading interval, n < min(len, max(pre, m + 1)), so tile row r is visible to this
+// lane's query iff r < lim, that bound relative to the tile (tile_lim)
+template <bool BF, int MASK, int D>
 __device__ __forceinline__ void f_qk_sm(const char *buf, const typename AFrag<BF>::type (&qf)[D / 16], const int (&ko)[D / 16], f32x16 (&o)[D / 32],
-                                        typename AFrag<BF>::type (&pf)[4], float &m_i, float &l_i, float c, int64_t kv0, int64_t len, int hl) {
+                                        typename AFrag<BF>::type (&pf)[4], float &m_i, float &l_i, float c, int64_t kv0, int64_t len, int hl,
+                                        int lim = 0) {
     using frag_t = typename AFrag<BF>::type;
     f32x16 s[2];
 #pragma unroll
@@ -259,10 +308,17 @@ __device__ __forceinline__ void f_qk_sm(const char *buf, const typename AFrag<BF
     for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            if (MASK && kv0 + sub * 32 + a_row(e, hl) >= len) s[sub][e] = -INFINITY;
+            if constexpr (MASK == 1) {
+                if (kv0 + sub * 32 + a_row(e, hl) >= len) s[sub][e] = -INFINITY;
+            } else if constexpr (MASK == 2) {
+                if (sub * 32 + a_row(e, hl) >= lim) s[sub][e] = -INFINITY;
+            }
             mx = fmaxf(mx, s[sub][e]);
         }
-    mx = a_half_max(mx); // finite: key kv0 of every visited tile is visible
+    // Without the causal mask mx is finite: key kv0 of every visited tile is visible. With it a row may see no key of this tile
+    // (mx = -inf), but never in tile 0, which is visited first and holds key 0, visible to every row (rows m >= Sq included): m_i is
+    // finite from there on, so m_i - fmaxf(m_i, -inf) = 0 and exp2(-inf - m_i c) = 0 - no (-inf) - (-inf) arises.
+    mx = a_half_max(mx);
     // deferred running maximum (attention.hip: s_qk_sm): a larger one is adopted, and O and l rescaled, only when some query of the
     // wave exceeds the maximum in use by more than kDeferMax exponent units
     if (__builtin_amdgcn_ballot_w64((mx - m_i) * c > kDeferMax) != 0) {
@@ -319,16 +375,19 @@ __device__ __forceinline__ void f_pv(const char *vt, const int (&vo)[DB][2], con
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <bool BF, int D>
-__global__ __launch_bounds__(NT) void attn_full_fwd_kernel(const FullArgs a) {
+// CAUSAL (the prefix-LM variant) enters in three places only: the tile bound / per-wave tile skip, the choice of the masked body,
+// and the select on the scores inside it.
+template <bool BF, int D, bool CAUSAL>
+__global__ __launch_bounds__(NT, CAUSAL && D == 64 ? 2 : 1) void attn_full_fwd_kernel(const FullArgs a) {
     using frag_t = typename AFrag<BF>::type;
     constexpr int KS = D / 16, DB = D / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
     const int64_t nxb = (a.Sq + TQ - 1) / TQ;
-    const int64_t xb = blockIdx.x % nxb, bh = blockIdx.x / nxb, b = bh / a.H, h = bh % a.H, g = h / a.G;
+    const int64_t bh = blockIdx.x / nxb, xb = block_of<CAUSAL>(blockIdx.x % nxb, bh, nxb), b = bh / a.H, h = bh % a.H, g = h / a.G;
     const int64_t len = key_len(a, b);
-    const int nt = (int)((len + TK - 1) / TK);
+    const int64_t pre = CAUSAL ? prefix_of(a, b) : 0;
+    const int nt = (int)((key_bound<CAUSAL>(a, len, pre, xb) + TK - 1) / TK);
     const char *Kg = a.k + b * a.lk.sb + g * a.lk.sh;
     const char *Vg = a.v + b * a.lv.sb + g * a.lv.sh;
     int ko[KS], vo[DB][2];
@@ -371,9 +430,18 @@ __global__ __launch_bounds__(NT) void attn_full_fwd_kernel(const FullArgs a) {
         if (t + 1 < nt) t_load<D>(tr, Kg + (kv0 + TK) * a.lk.sr, Vg + (kv0 + TK) * a.lv.sr, a.lk.sr, a.lv.sr, len - kv0 - TK);
         __syncthreads(); // tile t is in its slot; slot (t + 1) & 1 is no longer read
         const char *cur = smem + (t & 1) * SLOT;
-        if (active) {
-            if (kv0 + TK > len) f_qk_sm<BF, true, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
-            else f_qk_sm<BF, false, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
+        if constexpr (CAUSAL) {
+            // (wave-uniform) no query of the wave sees a key of a tile at or beyond both the prefix and the wave's last query; tile 0 is
+            // never skipped (qw + 32 > 0). A skipping wave still stages and synchronises.
+            if (active && kv0 < (pre > qw + 32 ? pre : qw + 32)) {
+                if (kv0 + TK > len || (kv0 + TK - 1 > qw && kv0 + TK - 1 >= pre)) {
+                    f_qk_sm<BF, 2, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl, tile_lim(len, pre, qw, kv0, xl));
+                } else f_qk_sm<BF, 0, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
+                f_pv<BF, DB>(cur + TILE, vo, pf, o);
+            }
+        } else if (active) {
+            if (kv0 + TK > len) f_qk_sm<BF, 1, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
+            else f_qk_sm<BF, 0, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
             f_pv<BF, DB>(cur + TILE, vo, pf, o);
         }
         if (t + 1 < nt) t_store<D>(tr, smem + ((t + 1) & 1) * SLOT);
@@ -422,9 +490,10 @@ __global__ __launch_bounds__(NT) void attn_full_delta_kernel(const char *o, cons
 // ------------------------------------------------------------------------------------------
 // backward: dQ. Per 32-key sub-tile: S^T = K Q^T, dP^T = V dO^T, dS^T = P^T o (dP^T - delta), dQ^T += K^T dS^T
 // ------------------------------------------------------------------------------------------
-template <bool BF, bool MASK, int D>
+template <bool BF, int MASK, int D>
 __device__ __forceinline__ void q_tile(const char *buf, const char *doslab, const typename AFrag<BF>::type (&qf)[D / 16], const int (&ko)[D / 16],
-                                       const int (&vo)[D / 32][2], f32x16 (&dq)[D / 32], float c, float lse2, float dlt, int64_t kv0, int64_t len, int hl) {
+                                       const int (&vo)[D / 32][2], f32x16 (&dq)[D / 32], float c, float lse2, float dlt, int64_t kv0, int64_t len, int hl,
+                                       int lim = 0) {
     using frag_t = typename AFrag<BF>::type;
     constexpr int DB = D / 32;
     const char *vt = buf + TILE;
@@ -449,7 +518,11 @@ __device__ __forceinline__ void q_tile(const char *buf, const char *doslab, cons
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], c, -lse2));
-            if (MASK && kv0 + sub * 32 + a_row(e, hl) >= len) p = 0.f;
+            if constexpr (MASK == 1) {
+                if (kv0 + sub * 32 + a_row(e, hl) >= len) p = 0.f;
+            } else if constexpr (MASK == 2) { // f_qk_sm's predicate
+                if (sub * 32 + a_row(e, hl) >= lim) p = 0.f;
+            }
             s[e] = p * (dp[e] - dlt);
         }
         TrN<DB> ta;
@@ -471,16 +544,17 @@ __device__ __forceinline__ void q_tile(const char *buf, const char *doslab, cons
 constexpr int QSLAB = 32 * AROW;              // one wave's dO rows (8 KiB)
 constexpr int DQ_LDS = 2 * SLOT + 4 * QSLAB;  // two K | V slots + four dO slabs = 96 KiB
 
-template <bool BF, int D>
+template <bool BF, int D, bool CAUSAL>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) {
     using frag_t = typename AFrag<BF>::type;
     constexpr int KS = D / 16, DB = D / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
     const int64_t nxb = (a.Sq + TQ - 1) / TQ;
-    const int64_t xb = blockIdx.x % nxb, bh = blockIdx.x / nxb, b = bh / a.H, h = bh % a.H, g = h / a.G;
+    const int64_t bh = blockIdx.x / nxb, xb = block_of<CAUSAL>(blockIdx.x % nxb, bh, nxb), b = bh / a.H, h = bh % a.H, g = h / a.G;
     const int64_t len = key_len(a, b);
-    const int nt = (int)((len + TK - 1) / TK);
+    const int64_t pre = CAUSAL ? prefix_of(a, b) : 0;
+    const int nt = (int)((key_bound<CAUSAL>(a, len, pre, xb) + TK - 1) / TK);
     const char *Kg = a.k + b * a.lk.sb + g * a.lk.sh;
     const char *Vg = a.v + b * a.lv.sb + g * a.lv.sh;
     char *doslab = smem + 2 * SLOT + wid * QSLAB; // this wave's dO rows, same swizzled image as a K tile (B operand of dP^T)
@@ -535,9 +609,15 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) 
         if (t + 1 < nt) t_load<D>(tr, Kg + (kv0 + TK) * a.lk.sr, Vg + (kv0 + TK) * a.lv.sr, a.lk.sr, a.lv.sr, len - kv0 - TK);
         __syncthreads();
         const char *cur = smem + (t & 1) * SLOT;
-        if (active) {
-            if (kv0 + TK > len) q_tile<BF, true, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
-            else q_tile<BF, false, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
+        if constexpr (CAUSAL) { // the forward's skip and body choice
+            if (active && kv0 < (pre > qw + 32 ? pre : qw + 32)) {
+                if (kv0 + TK > len || (kv0 + TK - 1 > qw && kv0 + TK - 1 >= pre)) {
+                    q_tile<BF, 2, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl, tile_lim(len, pre, qw, kv0, xl));
+                } else q_tile<BF, 0, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
+            }
+        } else if (active) {
+            if (kv0 + TK > len) q_tile<BF, 1, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
+            else q_tile<BF, 0, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
         }
         if (t + 1 < nt) t_store<D>(tr, smem + ((t + 1) & 1) * SLOT);
     }
@@ -559,10 +639,12 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) 
 constexpr int KV_SLOT = SLOT + 512;       // Q | dO | lse log2(e) [64] | delta [64]
 constexpr int KV_LDS = 2 * KV_SLOT;
 
-template <bool BF, bool MASK, int D>
+// MASK 2 (prefix-LM variant): P = 0 for the tile's queries r < cut - every one (64) when the lane's key is dead, those before the key
+// when it lies beyond the prefix, none otherwise.
+template <bool BF, int MASK, int D>
 __device__ __forceinline__ void kv_tile(const char *buf, const typename AFrag<BF>::type (&kf)[D / 16], const typename AFrag<BF>::type (&vf)[D / 16],
                                         const int (&ko)[D / 16], const int (&vo)[D / 32][2], f32x16 (&dk)[D / 32], f32x16 (&dv)[D / 32], float c, bool dead,
-                                        int hl) {
+                                        int hl, int cut = 0) {
     using frag_t = typename AFrag<BF>::type;
     constexpr int DB = D / 32;
     const char *dot = buf + TILE;
@@ -595,7 +677,11 @@ __device__ __forceinline__ void kv_tile(const char *buf, const typename AFrag<BF
                 const int e = 4 * j + i;
                 // f16: P travels as P 2^14 into the dV product (small weights would be subnormal f16 values), dS at its own scale
                 float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], c, (BF ? 0.f : kPShiftLog2) - lv[i]));
-                if (MASK && dead) p = 0.f;
+                if constexpr (MASK == 1) {
+                    if (dead) p = 0.f;
+                } else if constexpr (MASK == 2) {
+                    if (sub * 32 + 8 * j + 4 * hl + i < cut) p = 0.f;
+                }
                 s[e] = p;
                 dp[e] = BF ? p * (dp[e] - dl[i]) : p * ((dp[e] - dl[i]) * (1.f / kPShiftF16));
             }
@@ -609,19 +695,25 @@ __device__ __forceinline__ void kv_tile(const char *buf, const typename AFrag<BF
     f_pv<BF, DB>(buf, vo, df, dk);
 }
 
-template <bool BF, int D>
+template <bool BF, int D, bool CAUSAL>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a) {
     using frag_t = typename AFrag<BF>::type;
     constexpr int KS = D / 16, DB = D / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
     const int64_t nkb = (a.Skv + TQ - 1) / TQ;
-    const int64_t kb = blockIdx.x % nkb, bg = blockIdx.x / nkb, b = bg / a.Hkv, g = bg % a.Hkv;
+    const int64_t bg = blockIdx.x / nkb, kb = block_of<CAUSAL>(blockIdx.x % nkb, bg, nkb), b = bg / a.Hkv, g = bg % a.Hkv;
     const int64_t len = key_len(a, b);
     const int64_t k0 = kb * TQ, kw = k0 + wid * 32, n = kw + xl;
     char *dKg = a.dk + b * a.ldk.sb + g * a.ldk.sh;
     char *dVg = a.dv + b * a.ldv.sb + g * a.ldv.sh;
-    if (k0 >= len) { // (workgroup-uniform) a key block beyond the batch's length: its dK and dV rows are zeros
+    // prefix-LM variant: a key block beyond the prefix is seen by queries m >= k0 only, so its query tiles start at t0 = k0 / 64; with
+    // no tile left (the block lies beyond Sq too) no query sees it
+    const int nqt = (int)((a.Sq + TK - 1) / TK);
+    const int64_t pre = CAUSAL ? prefix_of(a, b) : 0;
+    const int64_t t0 = CAUSAL && k0 >= pre ? k0 / TK : 0;
+    const int64_t nq = nqt - t0; // query tiles per head
+    if (k0 >= len || (CAUSAL && nq <= 0)) { // (workgroup-uniform) a key block beyond the batch's length, or unseen: its dK and dV rows are zeros
         const int64_t rows = a.Skv - k0 < TQ ? a.Skv - k0 : TQ;
         for (int id = threadIdx.x; id < rows * (D / 8); id += NT) {
             const int row = id / (D / 8), ch = id % (D / 8);
@@ -663,12 +755,13 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a)
 #pragma unroll
         for (int e = 0; e < 16; ++e) { dk[d][e] = 0.f; dv[d][e] = 0.f; }
 
-    const int nqt = (int)((a.Sq + TK - 1) / TK);
-    const int64_t nit = (int64_t)a.G * nqt; // query heads g G .. g G + G - 1 in ascending order, each over all its query tiles
+    const int64_t nit = (int64_t)a.G * nq; // query heads g G .. g G + G - 1 in ascending order, each over its query tiles t0 .. nqt - 1
     TileRegs<D> tr;
     float rcv = 0.f;
+    int64_t q0n = 0, q0 = t0 * TK; // first query of the tile just loaded / of the tile in LDS (read by the prefix-LM variant only)
     auto load = [&](int64_t it) {
-        const int64_t hh = g * a.G + it / nqt, q0 = (it % nqt) * TK, bh = b * a.H + hh;
+        const int64_t hh = g * a.G + it / nq, q0 = (t0 + it % nq) * TK, bh = b * a.H + hh;
+        q0n = q0;
         t_load<D>(tr, a.q + b * a.lq.sb + hh * a.lq.sh + q0 * a.lq.sr, a.d_o + b * a.ldo.sb + hh * a.ldo.sh + q0 * a.ldo.sr, a.lq.sr, a.ldo.sr, a.Sq - q0);
         if (threadIdx.x < 128) {
             const int64_t mq = q0 + (threadIdx.x & 63);
@@ -686,11 +779,18 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a)
         if (it + 1 < nit) load(it + 1);
         __syncthreads();
         const char *cur = smem + (it & 1) * KV_SLOT;
-        if (work) {
-            if (ragged) kv_tile<BF, true, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
-            else kv_tile<BF, false, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
+        if constexpr (CAUSAL) {
+            if (work && !(kw >= pre && q0 + TK - 1 < kw)) { // (wave-uniform) skip: every key of the wave is causal and after the tile's last query
+                if (ragged || (kw + 31 >= pre && kw + 31 > q0))
+                    kv_tile<BF, 2, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl, dead ? TK : (n >= pre ? clamp_i(n - q0, 0, TK) : 0));
+                else kv_tile<BF, 0, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
+            }
+        } else if (work) {
+            if (ragged) kv_tile<BF, 1, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
+            else kv_tile<BF, 0, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
         }
         if (it + 1 < nit) store(smem + ((it + 1) & 1) * KV_SLOT);
+        q0 = q0n;
     }
     __syncthreads();
     if (kw < a.Skv) { // a wave without a visible key stores its zeros: rows n >= len of dK and dV are zeros
@@ -716,12 +816,22 @@ __device__ __forceinline__ float g_block_reduce(float v, float *red) { // every 
     return MAX ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-template <typename T>
+// CAUSAL (prefix-LM variant): query m sees the keys n < min(len, max(pre, m + 1)) - a plain bound in the forward and dQ, a predicate
+// on the query in dK/dV
+template <bool CAUSAL>
+__device__ __forceinline__ int64_t g_key_bound(const FullArgs &a, int64_t b, int64_t m) {
+    const int64_t len = key_len(a, b);
+    if constexpr (!CAUSAL) return len;
+    const int64_t pre = prefix_of(a, b), vis = pre > m + 1 ? pre : m + 1;
+    return len < vis ? len : vis;
+}
+
+template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(NT) void attn_full_fwd_generic_kernel(const FullArgs a) {
     __shared__ float qs[256], ps[256], red[4];
     const int tid = threadIdx.x, D = (int)a.D;
     const int64_t bh = blockIdx.x / a.Sq, m = blockIdx.x % a.Sq, b = bh / a.H, h = bh % a.H, g = h / a.G;
-    const int64_t len = key_len(a, b);
+    const int64_t len = g_key_bound<CAUSAL>(a, b, m);
     const T *Q = (const T *)a.q + (bh * a.Sq + m) * D;
     const T *K = (const T *)a.k + (b * a.Hkv + g) * a.Skv * D;
     const T *V = (const T *)a.v + (b * a.Hkv + g) * a.Skv * D;
@@ -762,12 +872,12 @@ __global__ __launch_bounds__(NT) void attn_full_delta_generic_kernel(const T *o,
     delta[row] = acc;
 }
 
-template <typename T>
+template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const FullArgs a) {
     __shared__ float qs[256], dos[256], dss[256];
     const int tid = threadIdx.x, D = (int)a.D;
     const int64_t bh = blockIdx.x / a.Sq, m = blockIdx.x % a.Sq, b = bh / a.H, h = bh % a.H, g = h / a.G;
-    const int64_t len = key_len(a, b);
+    const int64_t len = g_key_bound<CAUSAL>(a, b, m);
     const T *K = (const T *)a.k + (b * a.Hkv + g) * a.Skv * D;
     const T *V = (const T *)a.v + (b * a.Hkv + g) * a.Skv * D;
     if (tid < D) {
@@ -799,7 +909,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const Full
     if (tid < D) store_canonical((T *)a.dq + (bh * a.Sq + m) * D + tid, acc * a.scale);
 }
 
-template <typename T>
+template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const FullArgs a) {
     __shared__ float ks[256], vs[256], ps[256], dss[256];
     const int tid = threadIdx.x, D = (int)a.D;
@@ -815,6 +925,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
         vs[tid] = load_f32((const T *)a.v + (bg * a.Skv + n) * D + tid);
     }
     __syncthreads();
+    const bool in_prefix = !CAUSAL || n < prefix_of(a, b); // else only queries m >= n see this key
     float ak = 0.f, av = 0.f;
     for (int hh = 0; hh < a.G; ++hh) {
         const int64_t bh = b * a.H + g * a.G + hh;
@@ -822,7 +933,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
         for (int64_t c0 = 0; c0 < a.Sq; c0 += NT) {
             const int64_t m = c0 + tid;
             float p = 0.f, ds = 0.f;
-            if (m < a.Sq) {
+            if (m < a.Sq && (in_prefix || m >= n)) {
                 float dot = 0.f, dp = 0.f;
                 for (int d = 0; d < D; ++d) {
                     dot += ks[d] * load_f32(Q + m * D + d);
@@ -917,25 +1028,94 @@ static int full_check(const char *who, int dtype, int64_t B, int64_t Hq, int64_t
 using namespace kf;
 using namespace kf::full;
 
-extern "C" int kf_attn_full_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
-                                const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
-                                void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+// The two families share their host path. `causal` selects the prefix-LM instantiations and labels (kf_attn_prefix_*); without it
+// prefix_len is not read and the launches are kf_attn_full_*'s own.
+static int full_fwd(const char *who, bool causal, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                    const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
+                    const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
     const void *ops[4] = {q, k, v, o};
     const kf_attn_layout *lay[4] = {lq, lk, lv, lo};
     FullArgs a;
     Plan plan;
-    int rc = full_check("kf_attn_full_fwd", dtype, B, Hq, Hkv, Sq, Skv, D, scale, ops, lay, 4, a, plan);
+    int rc = full_check(who, dtype, B, Hq, Hkv, Sq, Skv, D, scale, ops, lay, 4, a, plan);
     if (rc != KF_OK || plan == PLAN_NONE) return rc;
     a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.out = (char *)o; a.lse = lse; a.kv_len = kv_len;
+    a.prefix_len = causal ? prefix_len : nullptr;
     hipStream_t st = as_stream(stream);
     const bool bf = dtype == KF_BF16, d64 = D == 64;
     if (plan == PLAN_MFMA) {
         const unsigned grid = (unsigned)(B * Hq * ((Sq + TQ - 1) / TQ));
-        KF_PROF(d64 ? "attn_full_fwd_mfma_d64" : "attn_full_fwd_mfma_d128", st);
-        return with_flags([&](auto BF, auto D64) { return launch(attn_full_fwd_kernel<BF, D64 ? 64 : 128>, grid, NT, 2 * SLOT, st, a); }, bf, d64);
+        KF_PROF(causal ? (d64 ? "attn_prefix_fwd_mfma_d64" : "attn_prefix_fwd_mfma_d128") : (d64 ? "attn_full_fwd_mfma_d64" : "attn_full_fwd_mfma_d128"), st);
+        return with_flags([&](auto BF, auto D64, auto C) { return launch(attn_full_fwd_kernel<BF, D64 ? 64 : 128, C>, grid, NT, 2 * SLOT, st, a); }, bf, d64,
+                          causal);
     }
-    KF_PROF("attn_full_fwd_generic", st);
-    return with_dtype(dtype, [&](auto t) { return launch(attn_full_fwd_generic_kernel<decltype(t)>, (unsigned)(B * Hq * Sq), NT, 0, st, a); });
+    KF_PROF(causal ? "attn_prefix_fwd_generic" : "attn_full_fwd_generic", st);
+    return with_dtype(dtype, [&](auto t) {
+        return with_flags([&](auto C) { return launch(attn_full_fwd_generic_kernel<decltype(t), C>, (unsigned)(B * Hq * Sq), NT, 0, st, a); }, causal);
+    });
+}
+
+static int full_bwd(const char *who, bool causal, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                    const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
+                    const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
+                    const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
+                    const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream) {
+    const void *ops[8] = {q, k, v, o, d_o, dq, dk, dv};
+    const kf_attn_layout *lay[8] = {lq, lk, lv, lo, ldo, ldq, ldk, ldv};
+    FullArgs a;
+    Plan plan;
+    int rc = full_check(who, dtype, B, Hq, Hkv, Sq, Skv, D, scale, ops, lay, 8, a, plan);
+    if (rc != KF_OK || plan == PLAN_NONE) return rc;
+    KF_REQUIRE(lse, KF_ERR_INVALID, "%s: null operand", who);
+    const size_t need = ws_bytes(B, Hq, Sq);
+    KF_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % sizeof(float) == 0, KF_ERR_INVALID,
+               "%s: workspace of at least %zu bytes required (kf_attn_full_bwd_workspace_bytes), got %zu", who, need, workspace_bytes);
+    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.o = (const char *)o; a.d_o = (const char *)d_o;
+    a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv;
+    a.lse_r = lse; a.delta = (float *)workspace; a.kv_len = kv_len;
+    a.prefix_len = causal ? prefix_len : nullptr;
+    hipStream_t st = as_stream(stream);
+    const bool bf = dtype == KF_BF16, d64 = D == 64;
+    const int64_t nrows = B * Hq * Sq;
+    if (plan == PLAN_MFMA) {
+        { // the delta pre-pass knows no mask: one kernel and one label for both families
+            KF_PROF("attn_full_bwd_delta", st);
+            rc = with_flags([&](auto BF) { return launch(attn_full_delta_kernel<BF>, (unsigned)((nrows + 15) / 16), NT, 0, st, a.o, a.d_o, a.delta, nrows, a.lo, a.ldo, Sq, Hq, (int)(D / 8)); }, bf);
+            if (rc != KF_OK) return rc;
+        }
+        {
+            KF_PROF(causal ? (d64 ? "attn_prefix_bwd_dq_mfma_d64" : "attn_prefix_bwd_dq_mfma_d128") : (d64 ? "attn_full_bwd_dq_mfma_d64" : "attn_full_bwd_dq_mfma_d128"), st);
+            const unsigned grid = (unsigned)(B * Hq * ((Sq + TQ - 1) / TQ));
+            rc = with_flags([&](auto BF, auto D64, auto C) { return launch(attn_full_bwd_dq_kernel<BF, D64 ? 64 : 128, C>, grid, NT, DQ_LDS, st, a); }, bf, d64,
+                            causal);
+            if (rc != KF_OK) return rc;
+        }
+        KF_PROF(causal ? (d64 ? "attn_prefix_bwd_dkv_mfma_d64" : "attn_prefix_bwd_dkv_mfma_d128") : (d64 ? "attn_full_bwd_dkv_mfma_d64" : "attn_full_bwd_dkv_mfma_d128"), st);
+        const unsigned grid = (unsigned)(B * Hkv * ((Skv + TQ - 1) / TQ));
+        return with_flags([&](auto BF, auto D64, auto C) { return launch(attn_full_bwd_dkv_kernel<BF, D64 ? 64 : 128, C>, grid, NT, KV_LDS, st, a); }, bf, d64,
+                          causal);
+    }
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        {
+            KF_PROF("attn_full_bwd_delta_generic", st);
+            rc = launch(attn_full_delta_generic_kernel<T>, (unsigned)((nrows + NT - 1) / NT), NT, 0, st, (const T *)o, (const T *)d_o, a.delta, nrows, (int)D);
+            if (rc != KF_OK) return rc;
+        }
+        {
+            KF_PROF(causal ? "attn_prefix_bwd_dq_generic" : "attn_full_bwd_dq_generic", st);
+            rc = with_flags([&](auto C) { return launch(attn_full_bwd_dq_generic_kernel<T, C>, (unsigned)nrows, NT, 0, st, a); }, causal);
+            if (rc != KF_OK) return rc;
+        }
+        KF_PROF(causal ? "attn_prefix_bwd_dkv_generic" : "attn_full_bwd_dkv_generic", st);
+        return with_flags([&](auto C) { return launch(attn_full_bwd_dkv_generic_kernel<T, C>, (unsigned)(B * Hkv * Skv), NT, 0, st, a); }, causal);
+    });
+}
+
+extern "C" int kf_attn_full_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
+                                const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
+                                void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+    return full_fwd("kf_attn_full_fwd", false, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, stream);
 }
 
 extern "C" int kf_attn_full_bwd_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, size_t *bytes) {
@@ -953,51 +1133,21 @@ extern "C" int kf_attn_full_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, i
                                 const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
                                 const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv, void *workspace,
                                 size_t workspace_bytes, void *stream) {
-    const void *ops[8] = {q, k, v, o, d_o, dq, dk, dv};
-    const kf_attn_layout *lay[8] = {lq, lk, lv, lo, ldo, ldq, ldk, ldv};
-    FullArgs a;
-    Plan plan;
-    int rc = full_check("kf_attn_full_bwd", dtype, B, Hq, Hkv, Sq, Skv, D, scale, ops, lay, 8, a, plan);
-    if (rc != KF_OK || plan == PLAN_NONE) return rc;
-    KF_REQUIRE(lse, KF_ERR_INVALID, "kf_attn_full_bwd: null operand");
-    const size_t need = ws_bytes(B, Hq, Sq);
-    KF_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % sizeof(float) == 0, KF_ERR_INVALID,
-               "kf_attn_full_bwd: workspace of at least %zu bytes required (kf_attn_full_bwd_workspace_bytes), got %zu", need, workspace_bytes);
-    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.o = (const char *)o; a.d_o = (const char *)d_o;
-    a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv;
-    a.lse_r = lse; a.delta = (float *)workspace; a.kv_len = kv_len;
-    hipStream_t st = as_stream(stream);
-    const bool bf = dtype == KF_BF16, d64 = D == 64;
-    const int64_t nrows = B * Hq * Sq;
-    if (plan == PLAN_MFMA) {
-        {
-            KF_PROF("attn_full_bwd_delta", st);
-            rc = with_flags([&](auto BF) { return launch(attn_full_delta_kernel<BF>, (unsigned)((nrows + 15) / 16), NT, 0, st, a.o, a.d_o, a.delta, nrows, a.lo, a.ldo, Sq, Hq, (int)(D / 8)); }, bf);
-            if (rc != KF_OK) return rc;
-        }
-        {
-            KF_PROF(d64 ? "attn_full_bwd_dq_mfma_d64" : "attn_full_bwd_dq_mfma_d128", st);
-            const unsigned grid = (unsigned)(B * Hq * ((Sq + TQ - 1) / TQ));
-            rc = with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dq_kernel<BF, D64 ? 64 : 128>, grid, NT, DQ_LDS, st, a); }, bf, d64);
-            if (rc != KF_OK) return rc;
-        }
-        KF_PROF(d64 ? "attn_full_bwd_dkv_mfma_d64" : "attn_full_bwd_dkv_mfma_d128", st);
-        const unsigned grid = (unsigned)(B * Hkv * ((Skv + TQ - 1) / TQ));
-        return with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dkv_kernel<BF, D64 ? 64 : 128>, grid, NT, KV_LDS, st, a); }, bf, d64);
-    }
-    return with_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        {
-            KF_PROF("attn_full_bwd_delta_generic", st);
-            rc = launch(attn_full_delta_generic_kernel<T>, (unsigned)((nrows + NT - 1) / NT), NT, 0, st, (const T *)o, (const T *)d_o, a.delta, nrows, (int)D);
-            if (rc != KF_OK) return rc;
-        }
-        {
-            KF_PROF("attn_full_bwd_dq_generic", st);
-            rc = launch(attn_full_bwd_dq_generic_kernel<T>, (unsigned)nrows, NT, 0, st, a);
-            if (rc != KF_OK) return rc;
-        }
-        KF_PROF("attn_full_bwd_dkv_generic", st);
-        return launch(attn_full_bwd_dkv_generic_kernel<T>, (unsigned)(B * Hkv * Skv), NT, 0, st, a);
-    });
+    return full_bwd("kf_attn_full_bwd", false, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq, dk,
+                    ldk, dv, ldv, workspace, workspace_bytes, stream);
+}
+
+extern "C" int kf_attn_prefix_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
+                                  const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v,
+                                  const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+    return full_fwd("kf_attn_prefix_fwd", true, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, prefix_len, q, lq, k, lk, v, lv, o, lo, lse, stream);
+}
+
+extern "C" int kf_attn_prefix_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
+                                  const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v,
+                                  const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
+                                  const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
+                                  const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream) {
+    return full_bwd("kf_attn_prefix_bwd", true, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, prefix_len, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq,
+                    dk, ldk, dv, ldv, workspace, workspace_bytes, stream);
 }
