@@ -573,6 +573,39 @@ int kf_attn_prefix_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq
                        const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk,
                        const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Sliding-window softmax attention: a band of keys around each query, either side optionally unbounded, with the optional per-batch
+ * key length of kf_attn_full_*. Everything not said here - operands, grouped K/V heads, the layout rule, lse, the argument checks and
+ * their statuses (with this entry's name in kf_last_error()), zero B, Hq or Sq, capturability - is kf_attn_full_*'s contract.
+ * kv_len: int64 [B] on the device, or NULL. window_left, window_right: host scalars, a key count >= 0 or -1 for "unbounded on that
+ * side"; anything below -1 is KF_ERR_INVALID (checked first, before any pointer is looked at).
+ *     len_b = clamp(kv_len[b], 0, Skv)   (kv_len == NULL: Skv)
+ *     query m sees key n   <=>   n < len_b  and  (wl < 0 or n >= m - wl)  and  (wr < 0 or n <= m + wr)
+ * The alignment is top-left with absolute indices, as in kf_attn_fwd; Sq and Skv may be in either size order. (wl, 0) is a causal
+ * sliding window (the query's own key and wl earlier ones), (w, w) a symmetric local window, (-1, 0) padded-causal attention and
+ * (-1, -1) full attention; the last two are served by the kernels of kf_attn_prefix_* (prefix_len NULL) and kf_attn_full_*, have their
+ * bits and their profile labels.
+ * A query row that sees no key - possible inside a live batch: m - wl >= len_b - has o = 0 (zero bits), lse = -inf and dq = 0 and adds
+ * nothing to dk or dv. Rows n >= len_b of dk and dv are written as zeros, and so is a row n < len_b that no query sees (n > Sq - 1 + wr,
+ * the last key of the last query).
+ * K and V rows at n >= len_b are never read. No atomics: bitwise reproducible.
+ * Kernels: the kernels of kf_attn_full_* compiled with the window (a query block walks the key tiles max(0, q0 - wl) / 64 ..
+ * ceil(min(len_b, qe + wr) / 64) - 1 only, a key block the query tiles max(0, k0 - wr) / 64 .. min(Sq - 1, k0 + 127 + wl) / 64; a wave
+ * skips tiles outside the band of its 32 rows; the tiles an edge crosses select on their scores). Profile labels
+ * attn_window_fwd_mfma_d64 / _d128, attn_window_bwd_dq_mfma_*, attn_window_bwd_dkv_mfma_*, attn_window_*_generic; the delta pre-pass
+ * keeps attn_full_bwd_delta (attn_full_bwd_delta_generic). The workspace is kf_attn_full_bwd_workspace_bytes' (delta), uninitialised.
+ */
+int kf_attn_window_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                       const int64_t *kv_len, int64_t window_left, int64_t window_right, const void *q, const kf_attn_layout *lq,
+                       const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, void *o,
+                       const kf_attn_layout *lo, float *lse, void *stream);
+int kf_attn_window_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                       const int64_t *kv_len, int64_t window_left, int64_t window_right, const void *q, const kf_attn_layout *lq,
+                       const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, const void *o,
+                       const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
+                       const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- rotary position embeddings (no reference counterpart: the position signal between the QKV projection and attention) ---- */
 /*
  * x, y: [B, H, S, D] addressed by kf_attn_layout element strides of B, H, S; D is contiguous; dtype in {KF_F32, KF_BF16, KF_F16};

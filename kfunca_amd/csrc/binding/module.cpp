@@ -392,21 +392,46 @@ PYBIND11_MODULE(_C, m) {
     m.def("causal_attention_gqa", &gpu::causal_attention_gqa, py::arg("q"), py::arg("k"), py::arg("v"));
     // full (non-causal) attention with an optional per-batch key length (Long [B]): encoder self-attention, cross-attention, padded batches
     // causal = True: the prefix-LM mask (full inside prefix_len[b], causal after it; prefix_len = None: causal over a padded batch)
+    // window = (left, right): the sliding-window mask, keys m - left .. m + right of query m; None in a place: unbounded on that side
     auto opt = [](const py::object &t) { return t.is_none() ? Tensor() : t.cast<Tensor>(); };
-    m.def("attention", [opt](const Tensor &q, const Tensor &k, const Tensor &v, py::object kv_len, bool causal, py::object prefix_len) {
-        return gpu::attention(q, k, v, opt(kv_len), causal, opt(prefix_len));
+    auto win = [](const char *op, const py::object &w, gpu::AttentionWindow &out) -> const gpu::AttentionWindow * {
+        if (w.is_none()) return nullptr;
+        const std::string text = std::string(op) + ": window is a pair (left, right) of non-negative ints, or None for unbounded on that side";
+        if (!py::isinstance<py::sequence>(w) || py::len(w) != 2) throw py::value_error(text);
+        const py::sequence s = w.cast<py::sequence>();
+        int64_t v[2];
+        for (int i = 0; i < 2; ++i) {
+            const py::object e = s[i];
+            if (e.is_none()) { v[i] = -1; continue; }
+            if (!py::isinstance<py::int_>(e) || e.cast<int64_t>() < 0) throw py::value_error(text);
+            v[i] = e.cast<int64_t>();
+        }
+        out = {v[0], v[1]};
+        return &out;
+    };
+    m.def("attention", [opt, win](const Tensor &q, const Tensor &k, const Tensor &v, py::object kv_len, bool causal, py::object prefix_len, py::object window) {
+        gpu::AttentionWindow w;
+        return gpu::attention(q, k, v, opt(kv_len), causal, opt(prefix_len), win("attention", window, w));
     }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kv_len") = py::none(), py::arg("causal") = false, py::arg("prefix_len") = py::none(),
+          py::arg("window") = py::none(),
           "Softmax attention of q [B, Hq, Sq, D] over k, v [B, Hkv, Skv, D]. kv_len: Long [B], batch b sees keys n < kv_len[b]. causal=True adds\n"
           "the prefix-LM mask: query m sees key n iff n < kv_len[b] and (n < prefix_len[b] or n <= m), top-left aligned; prefix_len: Long [B]\n"
           "or None (no prefix: causal attention over a padded batch), refused with causal=False. A plain causal call without lengths is\n"
-          "faster through causal_attention / causal_attention_gqa.");
-    m.def("attention_qkv", [opt](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object kv_len, bool causal,
-                                 py::object prefix_len) {
-        return gpu::attention_qkv(qkv, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>(), opt(kv_len), causal, opt(prefix_len));
+          "faster through causal_attention / causal_attention_gqa.\n"
+          "window: None, or a pair (left, right) for sliding-window attention: query m sees key n iff n < kv_len[b] and m - left <= n <= m + right,\n"
+          "top-left aligned. Each side is a non-negative int or None (unbounded on that side); negative values are refused. causal=True with a\n"
+          "window means right = 0 (a right side other than 0 or None is refused); window together with prefix_len is refused. A query that\n"
+          "sees no key gives a zero row.");
+    m.def("attention_qkv", [opt, win](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object kv_len, bool causal,
+                                      py::object prefix_len, py::object window) {
+        gpu::AttentionWindow w;
+        return gpu::attention_qkv(qkv, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>(), opt(kv_len), causal, opt(prefix_len),
+                                  win("attention_qkv", window, w));
     }, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none(), py::arg("kv_len") = py::none(),
-          py::arg("causal") = false, py::arg("prefix_len") = py::none(),
+          py::arg("causal") = false, py::arg("prefix_len") = py::none(), py::arg("window") = py::none(),
           "attention on the packed projection [B*S, (H + 2*kv_heads)*D] (columns q | k | v), read in place; the result is [B*S, H*D]. kv_len,\n"
-          "causal and prefix_len as in attention (Sq = Skv = S). A plain causal call without lengths is faster through causal_attention_qkv.");
+          "causal and prefix_len as in attention (Sq = Skv = S). A plain causal call without lengths is faster through causal_attention_qkv.\n"
+          "window: as in attention.");
     // rotary position embeddings: f64-accurate tables, and the rotation of q and k in place in the packed projection (one launch each way)
     m.def("rope_table", [](int64_t max_positions, int64_t rotary_dim, double base, int device) {
         auto [c, sn] = gpu::rope_table(max_positions, rotary_dim, base, device);

@@ -1,6 +1,6 @@
 // namespace gpu: the attention operators over the C ABI's attention entries - causal_attention, causal_attention_gqa and
 // causal_attention_qkv (ops.h; nn_ops.cpp:6-8 + the checks of causal_attention_kernel.cu:9-20), attention and attention_qkv (attn_full.h).
-// Four families of entries (the causal pair, full attention and its prefix-LM form), one host path: check, plan the padding, pad,
+// Five families of entries (the causal pair, full attention and its prefix-LM and sliding-window forms), one host path: check, plan the padding, pad,
 // allocate, call, un-pad.
 #include <cmath>
 
@@ -24,10 +24,15 @@ enum class Family {
     CausalGqa, // kf_attn_fwd_gqa / kf_attn_bwd_gqa: query head h reads K/V head h / (Hq / Hkv)
     Full,      // kf_attn_full_fwd / kf_attn_full_bwd: no mask but an optional per-batch key length
     Prefix,    // kf_attn_prefix_fwd / kf_attn_prefix_bwd: Full's operands and checks; causal beyond an optional per-batch prefix
+    Window,    // kf_attn_window_fwd / kf_attn_window_bwd: Full's operands and checks; keys m - left .. m + right of query m
 };
-bool full_like(Family f) { return f == Family::Full || f == Family::Prefix; }
-// the length arrays of attention / attention_qkv: undefined tensors for the other families
-struct Lens { Tensor kv, prefix; };
+bool full_like(Family f) { return f == Family::Full || f == Family::Prefix || f == Family::Window; }
+// the length arrays of attention / attention_qkv: undefined tensors for the other families; with them the window of Family::Window
+// (-1: unbounded on that side), which the backward keeps beside the lengths
+struct Lens {
+    Tensor kv, prefix;
+    int64_t wl = -1, wr = -1;
+};
 
 // One call as the C ABI takes it: the sizes handed down (padded ones where the host pads), the scale of the REAL head size, and the
 // layouts of q, k, v and their gradients (lx) and of out and its gradient (lo); NULL: contiguous [B, H, S, D].
@@ -39,6 +44,7 @@ struct Call {
     const int64_t *kv_len, *prefix_len;
     const kf_attn_layout *lx, *lo;
     bool padded;
+    int64_t wl, wr;
 };
 
 void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o, float *lse) {
@@ -57,6 +63,9 @@ void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o
         break;
     case Family::Prefix:
         DEV_CALL(kf_attn_prefix_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.prefix_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        break;
+    case Family::Window:
+        DEV_CALL(kf_attn_window_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.wl, c.wr, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
         break;
     }
 }
@@ -83,6 +92,10 @@ void run_bwd(const Call &c, const void *q, const void *k, const void *v, const v
     case Family::Prefix:
         DEV_CALL(kf_attn_prefix_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.prefix_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go,
                                     c.lo, dq, c.lx, dk, c.lx, dv, c.lx, ws, bytes, st));
+        break;
+    case Family::Window:
+        DEV_CALL(kf_attn_window_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.wl, c.wr, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo,
+                                    dq, c.lx, dk, c.lx, dv, c.lx, ws, bytes, st));
         break;
     }
 }
@@ -114,6 +127,7 @@ DataPtr bwd_scratch(const Call &c, size_t &bytes) {
         break;
     case Family::Full: // one size, no smaller form to retry with
     case Family::Prefix:
+    case Family::Window:
         DEV_CALL(kf_attn_full_bwd_workspace_bytes(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, &bytes));
         return DeviceAllocator::GetInstance()->allocate(bytes > 0 ? bytes : 1, c.device);
     }
@@ -146,7 +160,7 @@ Tensor check_len(const Tensor &kv_len, int64_t B, int device, const char *name =
     CHECK_FAIL(kv_len.numel() == B && kv_len.device() == device, "attention: ", name, " must hold B = ", B, " elements on the operands' device");
     return kv_len.dense();
 }
-Lens check_lens(const Lens &l, int64_t B, int device) { return {check_len(l.kv, B, device), check_len(l.prefix, B, device, "prefix_len")}; }
+Lens check_lens(const Lens &l, int64_t B, int device) { return {check_len(l.kv, B, device), check_len(l.prefix, B, device, "prefix_len"), l.wl, l.wr}; }
 const int64_t *len_ptr(const Tensor &kv_len) { return kv_len.defined() ? static_cast<const int64_t *>(kv_len.data_ptr()) : nullptr; }
 
 // The extents handed down. The MFMA kernels want D = 64 or 128 (and, f32, whole tiles of 32 rows); everything else takes the generic
@@ -189,7 +203,7 @@ Tensor unpad(const Tensor &t, int64_t rows, int64_t cols) {
 Call contiguous_call(Family f, const Tensor &q, const Tensor &k, const PadPlan &pp, const Lens &len) {
     const bool padded = pp.Sq != q.shape(2) || pp.Skv != k.shape(2) || pp.D != q.shape(3);
     return {f, code(q.dtype()), q.device(), q.shape(0), q.shape(1), k.shape(1), pp.Sq, pp.Skv, pp.D, 1.0f / std::sqrt((float)q.shape(3)),
-            len_ptr(len.kv), len_ptr(len.prefix), nullptr, nullptr, padded};
+            len_ptr(len.kv), len_ptr(len.prefix), nullptr, nullptr, padded, len.wl, len.wr};
 }
 
 std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len) {
@@ -262,7 +276,8 @@ PackedLay packed_layouts(int64_t S, int64_t H, int64_t Hkv, int64_t D) {
 }
 // family CausalMha is Hkv = H here: K at column H D, V at 2 H D (the strided entries); otherwise K at H D, V at (H + Hkv) D
 Call packed_call(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D, const PackedLay &L, const Lens &len) {
-    return {f, code(qkv.dtype()), qkv.device(), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), len_ptr(len.kv), len_ptr(len.prefix), &L.qkv, &L.flat, false};
+    return {f, code(qkv.dtype()), qkv.device(), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), len_ptr(len.kv), len_ptr(len.prefix), &L.qkv, &L.flat, false,
+            len.wl, len.wr};
 }
 
 class PackedAttentionGradFunction : public GradFunction {
@@ -295,8 +310,8 @@ private:
     int64_t B_, S_, H_, Hkv_;
 };
 
-// f: CausalMha for causal_attention_qkv(qkv, B, S, H) (Hkv = H, the [B*S, 3*H*D] texts), CausalGqa for its kv_heads form, Full and Prefix
-// for attention_qkv
+// f: CausalMha for causal_attention_qkv(qkv, B, S, H) (Hkv = H, the [B*S, 3*H*D] texts), CausalGqa for its kv_heads form, Full, Prefix
+// and Window for attention_qkv
 Tensor packed_attention(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, const Lens &lens) {
     const char *op = full_like(f) ? "attention_qkv" : "causal_attention_qkv";
     CHECK_FAIL(qkv.defined() && qkv.dim() == 2 && qkv.is_dense(), op,
@@ -344,13 +359,26 @@ std::tuple<Tensor, Tensor, Tensor> causal_attention_bwd(const Tensor &q, const T
 }
 Tensor causal_attention(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalMha, q, k, v, Lens()); }
 Tensor causal_attention_gqa(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalGqa, q, k, v, Lens()); }
-// causal = false is the full family's path, call for call; a prefix belongs to the causal mask
-static Family masked_family(const char *op, bool causal, const Tensor &prefix_len) {
+// causal = false is the full family's path, call for call; a prefix belongs to the causal mask. Without a window the calls are those
+// made before windows existed. With one: causal closes its right side (right = 0), so another right side contradicts it, and a window
+// beside a prefix is no mask this package has.
+static Family masked_family(const char *op, bool causal, const Tensor &prefix_len, const AttentionWindow *window, Lens &lens) {
+    if (window) {
+        CHECK_FAIL(!prefix_len.defined(), op, ": window and prefix_len cannot be combined (a window inside a prefix-LM mask is not supported)");
+        CHECK_FAIL(window->left >= -1 && window->right >= -1, op, ": window sizes must be non-negative (-1 / None: unbounded on that side)");
+        CHECK_FAIL(!causal || window->right <= 0, op, ": causal = true means window right = 0, got right = ", window->right);
+        lens.wl = window->left;
+        lens.wr = causal ? 0 : window->right;
+        return Family::Window;
+    }
     CHECK_FAIL(causal || !prefix_len.defined(), op, ": prefix_len needs causal = true (without the causal mask every key is visible already)");
     return causal ? Family::Prefix : Family::Full;
 }
-Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, bool causal, const Tensor &prefix_len) {
-    return contiguous_attention(masked_family("attention", causal, prefix_len), q, k, v, {kv_len, prefix_len});
+Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, bool causal, const Tensor &prefix_len,
+                 const AttentionWindow *window) {
+    Lens lens{kv_len, prefix_len};
+    const Family f = masked_family("attention", causal, prefix_len, window, lens);
+    return contiguous_attention(f, q, k, v, lens);
 }
 
 Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H) { return packed_attention(Family::CausalMha, qkv, B, S, H, H, Lens()); }
@@ -358,8 +386,11 @@ Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, 
     if (kv_heads >= 0 && kv_heads != H) return packed_attention(Family::CausalGqa, qkv, B, S, H, kv_heads, Lens());
     return causal_attention_qkv(qkv, B, S, H);
 }
-Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len, bool causal, const Tensor &prefix_len) {
-    return packed_attention(masked_family("attention_qkv", causal, prefix_len), qkv, B, S, H, kv_heads < 0 ? H : kv_heads, {kv_len, prefix_len});
+Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len, bool causal, const Tensor &prefix_len,
+                     const AttentionWindow *window) {
+    Lens lens{kv_len, prefix_len};
+    const Family f = masked_family("attention_qkv", causal, prefix_len, window, lens);
+    return packed_attention(f, qkv, B, S, H, kv_heads < 0 ? H : kv_heads, lens);
 }
 
 } // namespace gpu

@@ -1,5 +1,5 @@
 // namespace gpu: full (non-causal) softmax attention with an optional per-batch key length (kf_attn_full_fwd, kf_attn_full_bwd) and its
-// prefix-LM / padded-causal form (kf_attn_prefix_fwd, kf_attn_prefix_bwd), with autograd. No reference counterpart: the self-attention of a vision / audio encoder (every token sees every token), cross-attention
+// prefix-LM / padded-causal form (kf_attn_prefix_fwd, kf_attn_prefix_bwd) and its sliding-window form (kf_attn_window_fwd, kf_attn_window_bwd), with autograd. No reference counterpart: the self-attention of a vision / audio encoder (every token sees every token), cross-attention
 // (Sq text queries over Skv image keys, in either size order) and padded batches (keys beyond a sample's own length are invisible).
 #pragma once
 
@@ -20,11 +20,17 @@ namespace gpu {
 // clamped to [0, Skv]; given with causal = false it is refused. A key row no query sees (n >= prefix_len[b] and n >= Sq) has zero
 // gradients. A plain causal call without lengths is faster through causal_attention / causal_attention_gqa (the generated kernels);
 // this operator does not route there, the results would not have the same bits.
-Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, bool causal = false, const Tensor &prefix_len = Tensor());
+// window (kf_attn_window_fwd, kf_attn_window_bwd): null (the calls above, unchanged) or the sliding window {left, right}: query m sees
+// key n iff n < kv_len[b], n >= m - left and n <= m + right, top-left aligned; -1 is "unbounded on that side", anything below is
+// refused. causal = true with a window means right = 0 (a right side above 0 is refused); a window beside prefix_len is refused.
+// A query that sees no key (m - left >= kv_len[b]) gives a zero row and zero gradients; a key no query sees has zero gradients.
+struct AttentionWindow { int64_t left, right; };
+Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, bool causal = false, const Tensor &prefix_len = Tensor(),
+                 const AttentionWindow *window = nullptr);
 // attention_qkv(qkv, B, S, H, kv_heads, kv_len): the packed projection [B*S, (H + 2*Hkv)*D] (columns q | k | v; kv_heads < 0: Hkv = H)
 // is read in place, the result is [B*S, H*D] and the backward writes one packed gradient - the layouts causal_attention_qkv builds.
-// causal, prefix_len: as in attention (Sq = Skv = S).
+// causal, prefix_len, window: as in attention (Sq = Skv = S).
 Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len, bool causal = false,
-                     const Tensor &prefix_len = Tensor());
+                     const Tensor &prefix_len = Tensor(), const AttentionWindow *window = nullptr);
 
 } // namespace gpu

@@ -32,6 +32,16 @@
 // score inside it; besides that only the assignment of blocks to workgroups differs (block_of), which no result depends on. With
 // pre_b >= len_b every choice is kf_attn_full_*'s and the results have its bits. The instantiations without CAUSAL are the code they
 // were before the variant existed.
+//
+// The window variant (kf_attn_window_*: a band around the diagonal, either side optionally unbounded) is a third compile-time MODE of
+// the same kernels:
+//   query m sees key n  <=>  n < len_b and (wl < 0 or n >= m - wl) and (wr < 0 or n <= m + wr)
+// top-left aligned with absolute indices. The keys a query sees are an interval that need not start at key 0, so the mask enters in
+// the same three places with a lower edge as well: the key tiles of a query block are first .. last (first_tile, key_bound), not 0 .. last, and
+// the query tiles of a key block likewise; a wave skips a tile outside the band of its 32 rows; the masked body selects on
+// lo <= r < hi per lane (win_lim). A row may see no key of the first tile its block visits, or no key at all: the masked forward body
+// carries such a row with a stand-in for its maximum (f_qk_sm), and the backward bodies select its p to 0 before anything is
+// multiplied by it (its lse is -inf). (-1, -1) and (-1, 0) are dispatched to the two older families on the host.
 // No kernel uses atomics; every result is bitwise reproducible run to run.
 #include <math.h>
 
@@ -63,7 +73,11 @@ struct FullArgs {
     float scale;
     Lay lq, lk, lv, lo, ldo, ldq, ldk, ldv;
     const int64_t *prefix_len; // [B] on the device, or null (the prefix-LM variant only; last, so no other member moves)
+    int64_t wl, wr;            // the window variant only: keys m - wl .. m + wr; an unbounded side is kNoEdge
 };
+
+enum Mode { M_FULL = 0, M_PREFIX = 1, M_WINDOW = 2 }; // the mask a kernel is compiled with
+constexpr int64_t kNoEdge = (int64_t)1 << 40;         // a window side no index reaches (extents are at most 2^31): m - wl < 0, m + wr >= Skv
 
 __device__ __forceinline__ int64_t key_len(const FullArgs &a, int64_t b) {
     if (!a.kv_len) return a.Skv;
@@ -257,9 +271,13 @@ __device__ __forceinline__ void t_store(const TileRegs<D> &r, char *slot) {
 // heavy blocks of every head land on the same engines and the light ones on the others, and the kernel takes as long as without the
 // mask. Rotating the blocks of each (batch, head) by a hash of its index gives every engine every block size. The results do not
 // depend on which workgroup computes a block.
-template <bool CAUSAL>
+// Under a window the work of a block does not depend on its index while every key exists, but a key length makes it so again: the
+// blocks beyond len_b + wl walk no tile at all, and with block = id % n those of every head of the batch share their engines. Measured
+// both ways: the rotation costs nothing where the work is uniform and takes a padded batch from 1.6 - 1.9 to
+// 1.2 - 1.4 times the time its tiles account for, so the window variant rotates as the causal one does.
+template <int MODE>
 __device__ __forceinline__ int64_t block_of(int64_t pos, int64_t group, int64_t n) {
-    if constexpr (!CAUSAL) return pos;
+    if constexpr (MODE == M_FULL) return pos;
     return (pos + (int64_t)(((uint32_t)group * 2654435761u) >> 16)) % n;
 }
 
@@ -271,11 +289,32 @@ __device__ __forceinline__ int tile_lim(int64_t len, int64_t pre, int64_t qw, in
     return min(nl, max(np, dm1));
 }
 
-template <bool CAUSAL>
+// lo <= r < lo + n as one compare (n >= 0: win_lim and the dK/dV kernel hand over the interval as first row and row count)
+__device__ __forceinline__ bool win_in(int r, int lo, int n) { return (unsigned)(r - lo) < (unsigned)n; }
+
+template <int MODE>
 __device__ __forceinline__ int64_t key_bound(const FullArgs &a, int64_t len, int64_t pre, int64_t xb) {
-    if constexpr (!CAUSAL) return len;
-    const int64_t qe = a.Sq < xb * TQ + TQ ? a.Sq : xb * TQ + TQ, vis = pre > qe ? pre : qe;
+    if constexpr (MODE == M_FULL) return len;
+    const int64_t qe = a.Sq < xb * TQ + TQ ? a.Sq : xb * TQ + TQ;
+    if constexpr (MODE == M_WINDOW) return len < qe + a.wr ? len : qe + a.wr; // the last query qe - 1 sees up to key qe - 1 + wr
+    const int64_t vis = pre > qe ? pre : qe;
     return len < vis ? len : vis;
+}
+// window variant: the first key tile of query block xb - the one that holds key max(0, xb 128 - wl), the first its first query sees
+template <int MODE>
+__device__ __forceinline__ int first_tile(const FullArgs &a, int64_t xb) {
+    if constexpr (MODE != M_WINDOW) return 0;
+    const int64_t lo = xb * TQ - a.wl;
+    return lo > 0 ? (int)(lo / TK) : 0;
+}
+// window variant: the rows lo <= r < hi of the tile at kv0 that the query of lane xl of the wave at qw sees, i.e. the keys
+// max(0, m - wl) <= n < min(len, m + wr + 1) relative to kv0. As in tile_lim everything but the last addition is wave-uniform, and the
+// clamps keep it in 32 bits without changing which rows 0 .. 63 pass: below -32 every lane's bound is negative, above 64 none's is.
+// Handed over as the first row and the row count (0 when the interval is empty), for win_in.
+__device__ __forceinline__ void win_lim(const FullArgs &a, int64_t len, int64_t qw, int64_t kv0, int xl, int &lo, int &cnt) {
+    const int nl = clamp_i(len - kv0, 0, TK);
+    lo = clamp_i(qw - a.wl - kv0, -32, TK) + xl;
+    cnt = max(min(nl, clamp_i(qw + a.wr + 1 - kv0, -32, TK) + xl) - lo, 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -284,11 +323,12 @@ __device__ __forceinline__ int64_t key_bound(const FullArgs &a, int64_t len, int
 // S^T = K Q^T (A = K rows from LDS, B = Q fragments in registers), online softmax with a deferred running maximum. MASK 1: the last
 // tile of a batch whose key count is no multiple of 64 - keys at kv0 + row >= len get -inf (their K rows are zeros in LDS). MASK 2
 // (prefix-LM variant): the keys a query sees are a leading interval, n < min(len, max(pre, m + 1)), so tile row r is visible to this
-// lane's query iff r < lim, that bound relative to the tile (tile_lim)
+// lane's query iff r < lim, that bound relative to the tile (tile_lim). MASK 3 (window variant): the keys a query sees are an interval
+// that starts anywhere: tile row r is visible iff lo <= r < lo + lim (win_lim: first row and row count)
 template <bool BF, int MASK, int D>
 __device__ __forceinline__ void f_qk_sm(const char *buf, const typename AFrag<BF>::type (&qf)[D / 16], const int (&ko)[D / 16], f32x16 (&o)[D / 32],
                                         typename AFrag<BF>::type (&pf)[4], float &m_i, float &l_i, float c, int64_t kv0, int64_t len, int hl,
-                                        int lim = 0) {
+                                        int lim = 0, int lo = 0) {
     using frag_t = typename AFrag<BF>::type;
     f32x16 s[2];
 #pragma unroll
@@ -312,18 +352,29 @@ __device__ __forceinline__ void f_qk_sm(const char *buf, const typename AFrag<BF
                 if (kv0 + sub * 32 + a_row(e, hl) >= len) s[sub][e] = -INFINITY;
             } else if constexpr (MASK == 2) {
                 if (sub * 32 + a_row(e, hl) >= lim) s[sub][e] = -INFINITY;
+            } else if constexpr (MASK == 3) {
+                if (!win_in(sub * 32 + a_row(e, hl), lo, lim)) s[sub][e] = -INFINITY;
             }
             mx = fmaxf(mx, s[sub][e]);
         }
     // Without the causal mask mx is finite: key kv0 of every visited tile is visible. With it a row may see no key of this tile
     // (mx = -inf), but never in tile 0, which is visited first and holds key 0, visible to every row (rows m >= Sq included): m_i is
     // finite from there on, so m_i - fmaxf(m_i, -inf) = 0 and exp2(-inf - m_i c) = 0 - no (-inf) - (-inf) arises.
+    // Under a window (MASK 3) that argument is gone: the first tile a block visits is seen by its earliest queries only, and a row
+    // beyond the keys' end sees none at all, so a row can be EMPTY so far: m_i = -inf, l_i = 0, o = 0. m_i stays -inf as the row's
+    // state - the first finite mx then exceeds it by +inf and is adopted with alpha = exp2(-inf) = 0 on l_i = 0 and o = 0, exactly as in
+    // tile 0 of the other variants - and only the two places where (-inf) - (-inf) would arise use a finite stand-in, 0, for it:
+    //   mx = -inf too, adoption forced by another row of the wave: (mx - m_i) c is NaN and compares false, so this row never asks; there
+    //     m_new = -inf and alpha is set to 1 (l_i and o are zeros; nothing to rescale);
+    //   the exponent: mc = 0 in place of -inf c, so p = exp2(fma(-inf, c, -0)) = 0 for each of its scores, all of which are -inf.
+    // A row that is not empty has a finite m_i and takes neither select. The unmasked body needs nothing: its mx is finite.
     mx = a_half_max(mx);
     // deferred running maximum (attention.hip: s_qk_sm): a larger one is adopted, and O and l rescaled, only when some query of the
     // wave exceeds the maximum in use by more than kDeferMax exponent units
     if (__builtin_amdgcn_ballot_w64((mx - m_i) * c > kDeferMax) != 0) {
         const float m_new = fmaxf(m_i, mx);
-        const float alpha = __builtin_amdgcn_exp2f((m_i - m_new) * c);
+        float alpha = __builtin_amdgcn_exp2f((m_i - m_new) * c);
+        if constexpr (MASK == 3) alpha = m_new == -INFINITY ? 1.f : alpha;
         l_i *= alpha;
 #pragma unroll
         for (int d = 0; d < D / 32; ++d)
@@ -331,7 +382,7 @@ __device__ __forceinline__ void f_qk_sm(const char *buf, const typename AFrag<BF
             for (int e = 0; e < 16; ++e) o[d][e] *= alpha;
         m_i = m_new;
     }
-    const float mc = m_i * c;
+    const float mc = MASK == 3 && m_i == -INFINITY ? 0.f : m_i * c;
     float rs = 0.f;
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub)
@@ -376,18 +427,20 @@ __device__ __forceinline__ void f_pv(const char *vt, const int (&vo)[DB][2], con
 }
 
 // CAUSAL (the prefix-LM variant) enters in three places only: the tile bound / per-wave tile skip, the choice of the masked body,
-// and the select on the scores inside it.
-template <bool BF, int D, bool CAUSAL>
-__global__ __launch_bounds__(NT, CAUSAL && D == 64 ? 2 : 1) void attn_full_fwd_kernel(const FullArgs a) {
+// and the select on the scores inside it. WIN (the window variant) enters in the same three, with a first tile besides the bound.
+template <bool BF, int D, int MODE>
+__global__ __launch_bounds__(NT, MODE != M_FULL && D == 64 ? 2 : 1) void attn_full_fwd_kernel(const FullArgs a) {
     using frag_t = typename AFrag<BF>::type;
+    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW;
     constexpr int KS = D / 16, DB = D / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
     const int64_t nxb = (a.Sq + TQ - 1) / TQ;
-    const int64_t bh = blockIdx.x / nxb, xb = block_of<CAUSAL>(blockIdx.x % nxb, bh, nxb), b = bh / a.H, h = bh % a.H, g = h / a.G;
+    const int64_t bh = blockIdx.x / nxb, xb = block_of<MODE>(blockIdx.x % nxb, bh, nxb), b = bh / a.H, h = bh % a.H, g = h / a.G;
     const int64_t len = key_len(a, b);
     const int64_t pre = CAUSAL ? prefix_of(a, b) : 0;
-    const int nt = (int)((key_bound<CAUSAL>(a, len, pre, xb) + TK - 1) / TK);
+    const int nt = (int)((key_bound<MODE>(a, len, pre, xb) + TK - 1) / TK);
+    const int tf = first_tile<MODE>(a, xb); // 0 but under a window; there nt <= tf when no query of the block sees a key
     const char *Kg = a.k + b * a.lk.sb + g * a.lk.sh;
     const char *Vg = a.v + b * a.lv.sb + g * a.lv.sh;
     int ko[KS], vo[DB][2];
@@ -421,15 +474,15 @@ __global__ __launch_bounds__(NT, CAUSAL && D == 64 ? 2 : 1) void attn_full_fwd_k
     frag_t pf[4];
 
     TileRegs<D> tr;
-    if (nt > 0) {
-        t_load<D>(tr, Kg, Vg, a.lk.sr, a.lv.sr, len);
+    if (nt > tf) {
+        t_load<D>(tr, Kg + (int64_t)tf * TK * a.lk.sr, Vg + (int64_t)tf * TK * a.lv.sr, a.lk.sr, a.lv.sr, len - (int64_t)tf * TK);
         t_store<D>(tr, smem);
     }
-    for (int t = 0; t < nt; ++t) {
+    for (int t = tf; t < nt; ++t) {
         const int64_t kv0 = (int64_t)t * TK;
         if (t + 1 < nt) t_load<D>(tr, Kg + (kv0 + TK) * a.lk.sr, Vg + (kv0 + TK) * a.lv.sr, a.lk.sr, a.lv.sr, len - kv0 - TK);
         __syncthreads(); // tile t is in its slot; slot (t + 1) & 1 is no longer read
-        const char *cur = smem + (t & 1) * SLOT;
+        const char *cur = smem + ((t - tf) & 1) * SLOT;
         if constexpr (CAUSAL) {
             // (wave-uniform) no query of the wave sees a key of a tile at or beyond both the prefix and the wave's last query; tile 0 is
             // never skipped (qw + 32 > 0). A skipping wave still stages and synchronises.
@@ -439,12 +492,23 @@ __global__ __launch_bounds__(NT, CAUSAL && D == 64 ? 2 : 1) void attn_full_fwd_k
                 } else f_qk_sm<BF, 0, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
                 f_pv<BF, DB>(cur + TILE, vo, pf, o);
             }
+        } else if constexpr (WIN) {
+            // (wave-uniform) skip a tile that lies wholly outside the keys qw - wl .. qw + 31 + wr of the wave's 32 rows; the masked body
+            // where the length, the lower edge (of the wave's last row) or the upper edge (of its first) cuts the tile
+            if (active && kv0 + TK > qw - a.wl && kv0 <= qw + 31 + a.wr) {
+                if (kv0 + TK > len || qw + 31 - a.wl > kv0 || qw + a.wr < kv0 + TK - 1) {
+                    int lo, cnt;
+                    win_lim(a, len, qw, kv0, xl, lo, cnt);
+                    f_qk_sm<BF, 3, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl, cnt, lo);
+                } else f_qk_sm<BF, 0, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
+                f_pv<BF, DB>(cur + TILE, vo, pf, o);
+            }
         } else if (active) {
             if (kv0 + TK > len) f_qk_sm<BF, 1, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
             else f_qk_sm<BF, 0, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
             f_pv<BF, DB>(cur + TILE, vo, pf, o);
         }
-        if (t + 1 < nt) t_store<D>(tr, smem + ((t + 1) & 1) * SLOT);
+        if (t + 1 < nt) t_store<D>(tr, smem + ((t + 1 - tf) & 1) * SLOT);
     }
     __syncthreads();
     if (active) {
@@ -493,7 +557,7 @@ __global__ __launch_bounds__(NT) void attn_full_delta_kernel(const char *o, cons
 template <bool BF, int MASK, int D>
 __device__ __forceinline__ void q_tile(const char *buf, const char *doslab, const typename AFrag<BF>::type (&qf)[D / 16], const int (&ko)[D / 16],
                                        const int (&vo)[D / 32][2], f32x16 (&dq)[D / 32], float c, float lse2, float dlt, int64_t kv0, int64_t len, int hl,
-                                       int lim = 0) {
+                                       int lim = 0, int lo = 0) {
     using frag_t = typename AFrag<BF>::type;
     constexpr int DB = D / 32;
     const char *vt = buf + TILE;
@@ -522,6 +586,8 @@ __device__ __forceinline__ void q_tile(const char *buf, const char *doslab, cons
                 if (kv0 + sub * 32 + a_row(e, hl) >= len) p = 0.f;
             } else if constexpr (MASK == 2) { // f_qk_sm's predicate
                 if (sub * 32 + a_row(e, hl) >= lim) p = 0.f;
+            } else if constexpr (MASK == 3) { // a row that sees no key has lse = -inf and p = +inf here: the select, before the product
+                if (!win_in(sub * 32 + a_row(e, hl), lo, lim)) p = 0.f;
             }
             s[e] = p * (dp[e] - dlt);
         }
@@ -544,17 +610,19 @@ __device__ __forceinline__ void q_tile(const char *buf, const char *doslab, cons
 constexpr int QSLAB = 32 * AROW;              // one wave's dO rows (8 KiB)
 constexpr int DQ_LDS = 2 * SLOT + 4 * QSLAB;  // two K | V slots + four dO slabs = 96 KiB
 
-template <bool BF, int D, bool CAUSAL>
+template <bool BF, int D, int MODE>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) {
     using frag_t = typename AFrag<BF>::type;
+    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW;
     constexpr int KS = D / 16, DB = D / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
     const int64_t nxb = (a.Sq + TQ - 1) / TQ;
-    const int64_t bh = blockIdx.x / nxb, xb = block_of<CAUSAL>(blockIdx.x % nxb, bh, nxb), b = bh / a.H, h = bh % a.H, g = h / a.G;
+    const int64_t bh = blockIdx.x / nxb, xb = block_of<MODE>(blockIdx.x % nxb, bh, nxb), b = bh / a.H, h = bh % a.H, g = h / a.G;
     const int64_t len = key_len(a, b);
     const int64_t pre = CAUSAL ? prefix_of(a, b) : 0;
-    const int nt = (int)((key_bound<CAUSAL>(a, len, pre, xb) + TK - 1) / TK);
+    const int nt = (int)((key_bound<MODE>(a, len, pre, xb) + TK - 1) / TK);
+    const int tf = first_tile<MODE>(a, xb); // 0 but under a window; there nt <= tf when no query of the block sees a key
     const char *Kg = a.k + b * a.lk.sb + g * a.lk.sh;
     const char *Vg = a.v + b * a.lv.sb + g * a.lv.sh;
     char *doslab = smem + 2 * SLOT + wid * QSLAB; // this wave's dO rows, same swizzled image as a K tile (B operand of dP^T)
@@ -600,26 +668,35 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) 
         for (int e = 0; e < 16; ++e) dq[d][e] = 0.f;
 
     TileRegs<D> tr;
-    if (nt > 0) {
-        t_load<D>(tr, Kg, Vg, a.lk.sr, a.lv.sr, len);
+    if (nt > tf) {
+        t_load<D>(tr, Kg + (int64_t)tf * TK * a.lk.sr, Vg + (int64_t)tf * TK * a.lv.sr, a.lk.sr, a.lv.sr, len - (int64_t)tf * TK);
         t_store<D>(tr, smem);
     }
-    for (int t = 0; t < nt; ++t) {
+    for (int t = tf; t < nt; ++t) {
         const int64_t kv0 = (int64_t)t * TK;
         if (t + 1 < nt) t_load<D>(tr, Kg + (kv0 + TK) * a.lk.sr, Vg + (kv0 + TK) * a.lv.sr, a.lk.sr, a.lv.sr, len - kv0 - TK);
         __syncthreads();
-        const char *cur = smem + (t & 1) * SLOT;
+        const char *cur = smem + ((t - tf) & 1) * SLOT;
         if constexpr (CAUSAL) { // the forward's skip and body choice
             if (active && kv0 < (pre > qw + 32 ? pre : qw + 32)) {
                 if (kv0 + TK > len || (kv0 + TK - 1 > qw && kv0 + TK - 1 >= pre)) {
                     q_tile<BF, 2, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl, tile_lim(len, pre, qw, kv0, xl));
                 } else q_tile<BF, 0, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
             }
+        } else if constexpr (WIN) { // the forward's skip and body choice; the unmasked body runs where every row sees all 64 keys, so
+                                    // a row with lse = -inf never meets it
+            if (active && kv0 + TK > qw - a.wl && kv0 <= qw + 31 + a.wr) {
+                if (kv0 + TK > len || qw + 31 - a.wl > kv0 || qw + a.wr < kv0 + TK - 1) {
+                    int lo, cnt;
+                    win_lim(a, len, qw, kv0, xl, lo, cnt);
+                    q_tile<BF, 3, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl, cnt, lo);
+                } else q_tile<BF, 0, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
+            }
         } else if (active) {
             if (kv0 + TK > len) q_tile<BF, 1, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
             else q_tile<BF, 0, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
         }
-        if (t + 1 < nt) t_store<D>(tr, smem + ((t + 1) & 1) * SLOT);
+        if (t + 1 < nt) t_store<D>(tr, smem + ((t + 1 - tf) & 1) * SLOT);
     }
     __syncthreads();
     if (active) {
@@ -640,11 +717,13 @@ constexpr int KV_SLOT = SLOT + 512;       // Q | dO | lse log2(e) [64] | delta [
 constexpr int KV_LDS = 2 * KV_SLOT;
 
 // MASK 2 (prefix-LM variant): P = 0 for the tile's queries r < cut - every one (64) when the lane's key is dead, those before the key
-// when it lies beyond the prefix, none otherwise.
+// when it lies beyond the prefix, none otherwise. MASK 3 (window variant): P = 0 for the tile's queries outside cut <= r < cut + hi, the
+// queries n - wr .. n + wl that see the lane's key (none, hi = 0, when it is dead); a query that sees no key (lse = -inf, P = +inf) is
+// outside it.
 template <bool BF, int MASK, int D>
 __device__ __forceinline__ void kv_tile(const char *buf, const typename AFrag<BF>::type (&kf)[D / 16], const typename AFrag<BF>::type (&vf)[D / 16],
                                         const int (&ko)[D / 16], const int (&vo)[D / 32][2], f32x16 (&dk)[D / 32], f32x16 (&dv)[D / 32], float c, bool dead,
-                                        int hl, int cut = 0) {
+                                        int hl, int cut = 0, int hi = 0) {
     using frag_t = typename AFrag<BF>::type;
     constexpr int DB = D / 32;
     const char *dot = buf + TILE;
@@ -681,6 +760,8 @@ __device__ __forceinline__ void kv_tile(const char *buf, const typename AFrag<BF
                     if (dead) p = 0.f;
                 } else if constexpr (MASK == 2) {
                     if (sub * 32 + 8 * j + 4 * hl + i < cut) p = 0.f;
+                } else if constexpr (MASK == 3) {
+                    if (!win_in(sub * 32 + 8 * j + 4 * hl + i, cut, hi)) p = 0.f;
                 }
                 s[e] = p;
                 dp[e] = BF ? p * (dp[e] - dl[i]) : p * ((dp[e] - dl[i]) * (1.f / kPShiftF16));
@@ -695,14 +776,15 @@ __device__ __forceinline__ void kv_tile(const char *buf, const typename AFrag<BF
     f_pv<BF, DB>(buf, vo, df, dk);
 }
 
-template <bool BF, int D, bool CAUSAL>
+template <bool BF, int D, int MODE>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a) {
     using frag_t = typename AFrag<BF>::type;
+    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW;
     constexpr int KS = D / 16, DB = D / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
     const int64_t nkb = (a.Skv + TQ - 1) / TQ;
-    const int64_t bg = blockIdx.x / nkb, kb = block_of<CAUSAL>(blockIdx.x % nkb, bg, nkb), b = bg / a.Hkv, g = bg % a.Hkv;
+    const int64_t bg = blockIdx.x / nkb, kb = block_of<MODE>(blockIdx.x % nkb, bg, nkb), b = bg / a.Hkv, g = bg % a.Hkv;
     const int64_t len = key_len(a, b);
     const int64_t k0 = kb * TQ, kw = k0 + wid * 32, n = kw + xl;
     char *dKg = a.dk + b * a.ldk.sb + g * a.ldk.sh;
@@ -711,9 +793,12 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a)
     // no tile left (the block lies beyond Sq too) no query sees it
     const int nqt = (int)((a.Sq + TK - 1) / TK);
     const int64_t pre = CAUSAL ? prefix_of(a, b) : 0;
-    const int64_t t0 = CAUSAL && k0 >= pre ? k0 / TK : 0;
-    const int64_t nq = nqt - t0; // query tiles per head
-    if (k0 >= len || (CAUSAL && nq <= 0)) { // (workgroup-uniform) a key block beyond the batch's length, or unseen: its dK and dV rows are zeros
+    // window variant: the keys k0 .. k0 + 127 are seen by the queries k0 - wr .. k0 + 127 + wl: query tiles t0 .. tl, none when tl < t0
+    const int64_t wlo = k0 - a.wr, whi = k0 + TQ - 1 + a.wl; // (read under WIN only)
+    const int64_t tl = (whi < a.Sq - 1 ? whi : a.Sq - 1) / TK;
+    const int64_t t0 = WIN ? (wlo > 0 ? wlo / TK : 0) : (CAUSAL && k0 >= pre ? k0 / TK : 0);
+    const int64_t nq = WIN ? tl - t0 + 1 : nqt - t0; // query tiles per head
+    if (k0 >= len || ((CAUSAL || WIN) && nq <= 0)) { // (workgroup-uniform) a key block beyond the batch's length, or unseen: its dK and dV rows are zeros
         const int64_t rows = a.Skv - k0 < TQ ? a.Skv - k0 : TQ;
         for (int id = threadIdx.x; id < rows * (D / 8); id += NT) {
             const int row = id / (D / 8), ch = id % (D / 8);
@@ -758,7 +843,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a)
     const int64_t nit = (int64_t)a.G * nq; // query heads g G .. g G + G - 1 in ascending order, each over its query tiles t0 .. nqt - 1
     TileRegs<D> tr;
     float rcv = 0.f;
-    int64_t q0n = 0, q0 = t0 * TK; // first query of the tile just loaded / of the tile in LDS (read by the prefix-LM variant only)
+    int64_t q0n = 0, q0 = t0 * TK; // first query of the tile just loaded / of the tile in LDS (read by the masked variants only)
     auto load = [&](int64_t it) {
         const int64_t hh = g * a.G + it / nq, q0 = (t0 + it % nq) * TK, bh = b * a.H + hh;
         q0n = q0;
@@ -784,6 +869,15 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a)
                 if (ragged || (kw + 31 >= pre && kw + 31 > q0))
                     kv_tile<BF, 2, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl, dead ? TK : (n >= pre ? clamp_i(n - q0, 0, TK) : 0));
                 else kv_tile<BF, 0, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
+            }
+        } else if constexpr (WIN) {
+            // (wave-uniform) skip a tile none of the wave's keys kw .. kw + 31 is seen from; the masked body where a key is dead or the
+            // tile is cut by the first query of the wave's last key (n - wr) or by the last query of its first key (n + wl)
+            if (work && q0 + TK > kw - a.wr && q0 <= kw + 31 + a.wl) {
+                if (ragged || kw + 31 - a.wr > q0 || kw + a.wl < q0 + TK - 1) {
+                    const int lo = clamp_i(n - a.wr - q0, 0, TK), hi = clamp_i(n + a.wl + 1 - q0, 0, TK);
+                    kv_tile<BF, 3, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl, lo, dead ? 0 : max(hi - lo, 0));
+                } else kv_tile<BF, 0, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
             }
         } else if (work) {
             if (ragged) kv_tile<BF, 1, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
@@ -818,27 +912,35 @@ __device__ __forceinline__ float g_block_reduce(float v, float *red) { // every 
 
 // CAUSAL (prefix-LM variant): query m sees the keys n < min(len, max(pre, m + 1)) - a plain bound in the forward and dQ, a predicate
 // on the query in dK/dV
-template <bool CAUSAL>
+// WIN (window variant): the keys max(0, m - wl) <= n < min(len, m + wr + 1) - a first key besides the bound in the forward and dQ (an
+// empty interval leaves o = 0, lse = -inf and dq = 0), the predicate n - wr <= m <= n + wl in dK/dV
+template <int MODE>
 __device__ __forceinline__ int64_t g_key_bound(const FullArgs &a, int64_t b, int64_t m) {
     const int64_t len = key_len(a, b);
-    if constexpr (!CAUSAL) return len;
+    if constexpr (MODE == M_FULL) return len;
+    if constexpr (MODE == M_WINDOW) return len < m + a.wr + 1 ? len : m + a.wr + 1;
     const int64_t pre = prefix_of(a, b), vis = pre > m + 1 ? pre : m + 1;
     return len < vis ? len : vis;
 }
+template <int MODE>
+__device__ __forceinline__ int64_t g_key_first(const FullArgs &a, int64_t m) {
+    if constexpr (MODE != M_WINDOW) return 0;
+    return m > a.wl ? m - a.wl : 0;
+}
 
-template <typename T, bool CAUSAL>
+template <typename T, int MODE>
 __global__ __launch_bounds__(NT) void attn_full_fwd_generic_kernel(const FullArgs a) {
     __shared__ float qs[256], ps[256], red[4];
     const int tid = threadIdx.x, D = (int)a.D;
     const int64_t bh = blockIdx.x / a.Sq, m = blockIdx.x % a.Sq, b = bh / a.H, h = bh % a.H, g = h / a.G;
-    const int64_t len = g_key_bound<CAUSAL>(a, b, m);
+    const int64_t len = g_key_bound<MODE>(a, b, m);
     const T *Q = (const T *)a.q + (bh * a.Sq + m) * D;
     const T *K = (const T *)a.k + (b * a.Hkv + g) * a.Skv * D;
     const T *V = (const T *)a.v + (b * a.Hkv + g) * a.Skv * D;
     if (tid < D) qs[tid] = load_f32(Q + tid);
     __syncthreads();
     float acc = 0.f, mrun = -INFINITY, lrun = 0.f;
-    for (int64_t c0 = 0; c0 < len; c0 += NT) {
+    for (int64_t c0 = g_key_first<MODE>(a, m); c0 < len; c0 += NT) {
         const int64_t n = c0 + tid;
         float s = -INFINITY;
         if (n < len) {
@@ -872,12 +974,12 @@ __global__ __launch_bounds__(NT) void attn_full_delta_generic_kernel(const T *o,
     delta[row] = acc;
 }
 
-template <typename T, bool CAUSAL>
+template <typename T, int MODE>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const FullArgs a) {
     __shared__ float qs[256], dos[256], dss[256];
     const int tid = threadIdx.x, D = (int)a.D;
     const int64_t bh = blockIdx.x / a.Sq, m = blockIdx.x % a.Sq, b = bh / a.H, h = bh % a.H, g = h / a.G;
-    const int64_t len = g_key_bound<CAUSAL>(a, b, m);
+    const int64_t len = g_key_bound<MODE>(a, b, m);
     const T *K = (const T *)a.k + (b * a.Hkv + g) * a.Skv * D;
     const T *V = (const T *)a.v + (b * a.Hkv + g) * a.Skv * D;
     if (tid < D) {
@@ -887,7 +989,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const Full
     const float lse = a.lse_r[bh * a.Sq + m], dlt = a.delta[bh * a.Sq + m];
     __syncthreads();
     float acc = 0.f;
-    for (int64_t c0 = 0; c0 < len; c0 += NT) {
+    for (int64_t c0 = g_key_first<MODE>(a, m); c0 < len; c0 += NT) {
         const int64_t n = c0 + tid;
         float ds = 0.f;
         if (n < len) {
@@ -909,7 +1011,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const Full
     if (tid < D) store_canonical((T *)a.dq + (bh * a.Sq + m) * D + tid, acc * a.scale);
 }
 
-template <typename T, bool CAUSAL>
+template <typename T, int MODE>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const FullArgs a) {
     __shared__ float ks[256], vs[256], ps[256], dss[256];
     const int tid = threadIdx.x, D = (int)a.D;
@@ -925,6 +1027,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
         vs[tid] = load_f32((const T *)a.v + (bg * a.Skv + n) * D + tid);
     }
     __syncthreads();
+    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW;
     const bool in_prefix = !CAUSAL || n < prefix_of(a, b); // else only queries m >= n see this key
     float ak = 0.f, av = 0.f;
     for (int hh = 0; hh < a.G; ++hh) {
@@ -933,7 +1036,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
         for (int64_t c0 = 0; c0 < a.Sq; c0 += NT) {
             const int64_t m = c0 + tid;
             float p = 0.f, ds = 0.f;
-            if (m < a.Sq && (in_prefix || m >= n)) {
+            if (m < a.Sq && (in_prefix || m >= n) && (!WIN || (m >= n - a.wr && m <= n + a.wl))) {
                 float dot = 0.f, dp = 0.f;
                 for (int d = 0; d < D; ++d) {
                     dot += ks[d] * load_f32(Q + m * D + d);
@@ -1028,9 +1131,34 @@ static int full_check(const char *who, int dtype, int64_t B, int64_t Hq, int64_t
 using namespace kf;
 using namespace kf::full;
 
-// The two families share their host path. `causal` selects the prefix-LM instantiations and labels (kf_attn_prefix_*); without it
+// The three families share their host path. `mode` selects the instantiations and labels: M_PREFIX the prefix-LM ones
+// (kf_attn_prefix_*), M_WINDOW the window ones (kf_attn_window_*; prefix_len carries nothing, the window is in `win`); with M_FULL
 // prefix_len is not read and the launches are kf_attn_full_*'s own.
-static int full_fwd(const char *who, bool causal, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+template <typename F> static inline int with_mode(Mode mode, F &&f) {
+    return mode == M_FULL ? f(std::integral_constant<int, M_FULL>{})
+                          : mode == M_PREFIX ? f(std::integral_constant<int, M_PREFIX>{}) : f(std::integral_constant<int, M_WINDOW>{});
+}
+struct Window { int64_t left, right; };
+static const char *const kFwdLabel[3][2] = {{"attn_full_fwd_mfma_d128", "attn_full_fwd_mfma_d64"},
+                                            {"attn_prefix_fwd_mfma_d128", "attn_prefix_fwd_mfma_d64"},
+                                            {"attn_window_fwd_mfma_d128", "attn_window_fwd_mfma_d64"}};
+static const char *const kDqLabel[3][2] = {{"attn_full_bwd_dq_mfma_d128", "attn_full_bwd_dq_mfma_d64"},
+                                           {"attn_prefix_bwd_dq_mfma_d128", "attn_prefix_bwd_dq_mfma_d64"},
+                                           {"attn_window_bwd_dq_mfma_d128", "attn_window_bwd_dq_mfma_d64"}};
+static const char *const kDkvLabel[3][2] = {{"attn_full_bwd_dkv_mfma_d128", "attn_full_bwd_dkv_mfma_d64"},
+                                            {"attn_prefix_bwd_dkv_mfma_d128", "attn_prefix_bwd_dkv_mfma_d64"},
+                                            {"attn_window_bwd_dkv_mfma_d128", "attn_window_bwd_dkv_mfma_d64"}};
+static const char *const kGenericLabel[3][3] = {{"attn_full_fwd_generic", "attn_full_bwd_dq_generic", "attn_full_bwd_dkv_generic"},
+                                                {"attn_prefix_fwd_generic", "attn_prefix_bwd_dq_generic", "attn_prefix_bwd_dkv_generic"},
+                                                {"attn_window_fwd_generic", "attn_window_bwd_dq_generic", "attn_window_bwd_dkv_generic"}};
+// the window as the kernels carry it: an unbounded side, or one wider than any extent, is kNoEdge
+static void set_window(FullArgs &a, Mode mode, Window win) {
+    if (mode != M_WINDOW) return;
+    a.wl = win.left < 0 || win.left > kNoEdge ? kNoEdge : win.left;
+    a.wr = win.right < 0 || win.right > kNoEdge ? kNoEdge : win.right;
+}
+
+static int full_fwd(const char *who, Mode mode, Window win, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
                     const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
                     const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
     const void *ops[4] = {q, k, v, o};
@@ -1040,22 +1168,24 @@ static int full_fwd(const char *who, bool causal, int dtype, int64_t B, int64_t 
     int rc = full_check(who, dtype, B, Hq, Hkv, Sq, Skv, D, scale, ops, lay, 4, a, plan);
     if (rc != KF_OK || plan == PLAN_NONE) return rc;
     a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.out = (char *)o; a.lse = lse; a.kv_len = kv_len;
-    a.prefix_len = causal ? prefix_len : nullptr;
+    a.prefix_len = mode == M_PREFIX ? prefix_len : nullptr;
+    set_window(a, mode, win);
     hipStream_t st = as_stream(stream);
     const bool bf = dtype == KF_BF16, d64 = D == 64;
     if (plan == PLAN_MFMA) {
         const unsigned grid = (unsigned)(B * Hq * ((Sq + TQ - 1) / TQ));
-        KF_PROF(causal ? (d64 ? "attn_prefix_fwd_mfma_d64" : "attn_prefix_fwd_mfma_d128") : (d64 ? "attn_full_fwd_mfma_d64" : "attn_full_fwd_mfma_d128"), st);
-        return with_flags([&](auto BF, auto D64, auto C) { return launch(attn_full_fwd_kernel<BF, D64 ? 64 : 128, C>, grid, NT, 2 * SLOT, st, a); }, bf, d64,
-                          causal);
+        KF_PROF(kFwdLabel[mode][d64], st);
+        return with_mode(mode, [&](auto M) {
+            return with_flags([&](auto BF, auto D64) { return launch(attn_full_fwd_kernel<BF, D64 ? 64 : 128, M>, grid, NT, 2 * SLOT, st, a); }, bf, d64);
+        });
     }
-    KF_PROF(causal ? "attn_prefix_fwd_generic" : "attn_full_fwd_generic", st);
+    KF_PROF(kGenericLabel[mode][0], st);
     return with_dtype(dtype, [&](auto t) {
-        return with_flags([&](auto C) { return launch(attn_full_fwd_generic_kernel<decltype(t), C>, (unsigned)(B * Hq * Sq), NT, 0, st, a); }, causal);
+        return with_mode(mode, [&](auto M) { return launch(attn_full_fwd_generic_kernel<decltype(t), M>, (unsigned)(B * Hq * Sq), NT, 0, st, a); });
     });
 }
 
-static int full_bwd(const char *who, bool causal, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+static int full_bwd(const char *who, Mode mode, Window win, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
                     const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
                     const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
                     const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
@@ -1073,7 +1203,8 @@ static int full_bwd(const char *who, bool causal, int dtype, int64_t B, int64_t 
     a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.o = (const char *)o; a.d_o = (const char *)d_o;
     a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv;
     a.lse_r = lse; a.delta = (float *)workspace; a.kv_len = kv_len;
-    a.prefix_len = causal ? prefix_len : nullptr;
+    a.prefix_len = mode == M_PREFIX ? prefix_len : nullptr;
+    set_window(a, mode, win);
     hipStream_t st = as_stream(stream);
     const bool bf = dtype == KF_BF16, d64 = D == 64;
     const int64_t nrows = B * Hq * Sq;
@@ -1084,16 +1215,18 @@ static int full_bwd(const char *who, bool causal, int dtype, int64_t B, int64_t 
             if (rc != KF_OK) return rc;
         }
         {
-            KF_PROF(causal ? (d64 ? "attn_prefix_bwd_dq_mfma_d64" : "attn_prefix_bwd_dq_mfma_d128") : (d64 ? "attn_full_bwd_dq_mfma_d64" : "attn_full_bwd_dq_mfma_d128"), st);
+            KF_PROF(kDqLabel[mode][d64], st);
             const unsigned grid = (unsigned)(B * Hq * ((Sq + TQ - 1) / TQ));
-            rc = with_flags([&](auto BF, auto D64, auto C) { return launch(attn_full_bwd_dq_kernel<BF, D64 ? 64 : 128, C>, grid, NT, DQ_LDS, st, a); }, bf, d64,
-                            causal);
+            rc = with_mode(mode, [&](auto M) {
+                return with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dq_kernel<BF, D64 ? 64 : 128, M>, grid, NT, DQ_LDS, st, a); }, bf, d64);
+            });
             if (rc != KF_OK) return rc;
         }
-        KF_PROF(causal ? (d64 ? "attn_prefix_bwd_dkv_mfma_d64" : "attn_prefix_bwd_dkv_mfma_d128") : (d64 ? "attn_full_bwd_dkv_mfma_d64" : "attn_full_bwd_dkv_mfma_d128"), st);
+        KF_PROF(kDkvLabel[mode][d64], st);
         const unsigned grid = (unsigned)(B * Hkv * ((Skv + TQ - 1) / TQ));
-        return with_flags([&](auto BF, auto D64, auto C) { return launch(attn_full_bwd_dkv_kernel<BF, D64 ? 64 : 128, C>, grid, NT, KV_LDS, st, a); }, bf, d64,
-                          causal);
+        return with_mode(mode, [&](auto M) {
+            return with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dkv_kernel<BF, D64 ? 64 : 128, M>, grid, NT, KV_LDS, st, a); }, bf, d64);
+        });
     }
     return with_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -1103,19 +1236,19 @@ static int full_bwd(const char *who, bool causal, int dtype, int64_t B, int64_t 
             if (rc != KF_OK) return rc;
         }
         {
-            KF_PROF(causal ? "attn_prefix_bwd_dq_generic" : "attn_full_bwd_dq_generic", st);
-            rc = with_flags([&](auto C) { return launch(attn_full_bwd_dq_generic_kernel<T, C>, (unsigned)nrows, NT, 0, st, a); }, causal);
+            KF_PROF(kGenericLabel[mode][1], st);
+            rc = with_mode(mode, [&](auto M) { return launch(attn_full_bwd_dq_generic_kernel<T, M>, (unsigned)nrows, NT, 0, st, a); });
             if (rc != KF_OK) return rc;
         }
-        KF_PROF(causal ? "attn_prefix_bwd_dkv_generic" : "attn_full_bwd_dkv_generic", st);
-        return with_flags([&](auto C) { return launch(attn_full_bwd_dkv_generic_kernel<T, C>, (unsigned)(B * Hkv * Skv), NT, 0, st, a); }, causal);
+        KF_PROF(kGenericLabel[mode][2], st);
+        return with_mode(mode, [&](auto M) { return launch(attn_full_bwd_dkv_generic_kernel<T, M>, (unsigned)(B * Hkv * Skv), NT, 0, st, a); });
     });
 }
 
 extern "C" int kf_attn_full_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
                                 const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
                                 void *o, const kf_attn_layout *lo, float *lse, void *stream) {
-    return full_fwd("kf_attn_full_fwd", false, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, stream);
+    return full_fwd("kf_attn_full_fwd", M_FULL, Window{-1, -1}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, stream);
 }
 
 extern "C" int kf_attn_full_bwd_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, size_t *bytes) {
@@ -1133,14 +1266,14 @@ extern "C" int kf_attn_full_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, i
                                 const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
                                 const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv, void *workspace,
                                 size_t workspace_bytes, void *stream) {
-    return full_bwd("kf_attn_full_bwd", false, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq, dk,
+    return full_bwd("kf_attn_full_bwd", M_FULL, Window{-1, -1}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq, dk,
                     ldk, dv, ldv, workspace, workspace_bytes, stream);
 }
 
 extern "C" int kf_attn_prefix_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
                                   const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v,
                                   const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
-    return full_fwd("kf_attn_prefix_fwd", true, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, prefix_len, q, lq, k, lk, v, lv, o, lo, lse, stream);
+    return full_fwd("kf_attn_prefix_fwd", M_PREFIX, Window{-1, -1}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, prefix_len, q, lq, k, lk, v, lv, o, lo, lse, stream);
 }
 
 extern "C" int kf_attn_prefix_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
@@ -1148,6 +1281,30 @@ extern "C" int kf_attn_prefix_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv,
                                   const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
                                   const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
                                   const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream) {
-    return full_bwd("kf_attn_prefix_bwd", true, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, prefix_len, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq,
+    return full_bwd("kf_attn_prefix_bwd", M_PREFIX, Window{-1, -1}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, prefix_len, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq,
                     dk, ldk, dv, ldv, workspace, workspace_bytes, stream);
+}
+
+// The two windows an older family already is take its kernels, so their results have its bits: (-1, -1) is full attention, (-1, 0)
+// padded-causal (kf_attn_prefix_* without a prefix). The refusals still carry this entry's name.
+static Mode window_mode(int64_t wl, int64_t wr) { return wl < 0 && wr < 0 ? M_FULL : (wl < 0 && wr == 0 ? M_PREFIX : M_WINDOW); }
+
+extern "C" int kf_attn_window_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
+                                  int64_t window_left, int64_t window_right, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
+                                  const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+    KF_REQUIRE(window_left >= -1 && window_right >= -1, KF_ERR_INVALID, "kf_attn_window_fwd: a window side is a key count >= 0 or -1 (unbounded), not (%lld, %lld)",
+               (long long)window_left, (long long)window_right);
+    return full_fwd("kf_attn_window_fwd", window_mode(window_left, window_right), Window{window_left, window_right}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len,
+                    nullptr, q, lq, k, lk, v, lv, o, lo, lse, stream);
+}
+
+extern "C" int kf_attn_window_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
+                                  int64_t window_left, int64_t window_right, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
+                                  const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
+                                  const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
+                                  const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream) {
+    KF_REQUIRE(window_left >= -1 && window_right >= -1, KF_ERR_INVALID, "kf_attn_window_bwd: a window side is a key count >= 0 or -1 (unbounded), not (%lld, %lld)",
+               (long long)window_left, (long long)window_right);
+    return full_bwd("kf_attn_window_bwd", window_mode(window_left, window_right), Window{window_left, window_right}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len,
+                    nullptr, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq, dk, ldk, dv, ldv, workspace, workspace_bytes, stream);
 }
