@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table, kf_attn_fwd_gqa, kf_attn_bwd_gqa_workspace_bytes, kf_attn_bwd_gqa, kf_glu_fwd, kf_glu_bwd, KF_ACT_*, kf_attn_full_fwd, kf_attn_full_bwd_workspace_bytes, kf_attn_full_bwd, kf_softmax_fwd, kf_softmax_bwd, KF_SOFTMAX, KF_LOG_SOFTMAX):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
+#define KF_ABI_VERSION 7 /* 7 (no signature changed; later additive: kf_cross_entropy_*, KF_CE_*, kf_adamw_workspace_bytes, kf_adamw_step, kf_adamw_tensor, kf_rope, kf_rope_table, kf_attn_fwd_gqa, kf_attn_bwd_gqa_workspace_bytes, kf_attn_bwd_gqa, kf_glu_fwd, kf_glu_bwd, KF_ACT_*, kf_attn_full_fwd, kf_attn_full_bwd_workspace_bytes, kf_attn_full_bwd, kf_softmax_fwd, kf_softmax_bwd, KF_SOFTMAX, KF_LOG_SOFTMAX, kf_qk_norm_rope_fwd, kf_qk_norm_rope_bwd_workspace_bytes, kf_qk_norm_rope_bwd):kf_attn_* run the matrix-core kernels on ANY sequence lengths with Skv >= Sq (no multiple-of-128 rule), the backward workspace's row-constant arrays pad Sq to 32 and its dS part has a second, half-size layout (the causal half: taken when the workspace does not hold full rows for every pair, or under KF_ATTN_DS_TRI) - a caller must size the workspace with THIS library's query, kf_index_add drops indices outside [-nrows, nrows); 6: + KF_ERR_OOM from kf_malloc, kf_gemm_epilogue.c_f32 / kf_gemm_problem.c_f32 (float output behind 16-bit operands); 2: + kf_reduce_moments*, KF_EW_*_SCALAR, kf_graph_*, kf_attn_*_scaled; 3: + kf_sort*; 4: + kf_knobs_reload, kf_norm_*, kf_index_get, kf_gemm_ex, KF_EPI_*; 5: + kf_gemm_grouped_single_grid, kf_allreduce_sum_multi, kf_profile_samples, kf_attn_bwd accepts any workspace >= the statistics (all additive) */
 
 /* ---- status ------------------------------------------------------------------------------ */
 enum {
@@ -691,6 +691,47 @@ int kf_softmax_fwd(int kind, int dtype, int64_t rows, int64_t V, float scale, co
                    void *stream);
 int kf_softmax_bwd(int kind, int dtype, int64_t rows, int64_t V, float scale, const void *y, int64_t ldy, const void *dy, int64_t lddy,
                    void *dx, int64_t lddx, void *stream);
+
+/* ---- per-head QK-norm fused with the rotary embedding (no reference counterpart: the RMS norm over every q and k head that
+ *      Chameleon, Qwen3, Gemma-3 and OLMo-2 put between the QKV projection and attention) ---- */
+/*
+ * x, y, dy, dx: [B*S, W], W = (Hq + Hk + Hv) D, each with a row stride ld* >= W in elements; the heads of a token in the order
+ * q | k | v; wq, wk, dwq, dwk: [D]; one dtype in {KF_F32, KF_BF16, KF_F16} for all of them. A NULL weight means 1, a NULL dw* is not
+ * computed. Hq, Hk, Hv >= 0 with Hq + Hk >= 1 (Hq = H, Hk = Hv = 0: the separate q of a cross-attention layer).
+ * rotary_dim R: even, 0 <= R <= D. R = 0 is the norm alone (a ViT): cos, sin and positions are then ignored and may be NULL. Tables
+ * (f32 [table_rows, R/2]), positions (int64 [B*S] or NULL: p = t % S) and the pairs (interleaved) are exactly kf_rope's.
+ *     forward    for every q head (weight wq) and every k head (weight wk) of every token
+ *                rstd = 1 / sqrt(mean_d x_d^2 + eps),  n_d = x_d rstd w_d,  y = kf_rope's rotation of n over its leading R dims
+ *     backward   rstd and xhat = x rstd recomputed from x; g = the inverse rotation of dy (identity beyond R), gw = g w,
+ *                m = mean_d(gw_d xhat_d):  dx_d = rstd (gw_d - xhat_d m),  dwq_d = sum over tokens and q heads of g_d xhat_d, dwk likewise
+ * all in f32 on the stored values with ONE rounding, at the store. The composition of kf_norm_fwd (KF_NORM_RMS) and kf_rope rounds n
+ * to the storage type in between, so its bits differ from this entry's in f16 and bf16. The sum of squares is a plain f32 sum: where
+ * it overflows (|x| ~ 1e18 and above, depending on D) the result is what the formula gives in f32, rstd = 0 and y = 0. eps scales
+ * tiny inputs as the formula says (x = 1e-20, eps = 1e-6: y = 1e-17 w). An all-zero head gives zeros (eps > 0). A NaN or Inf stays
+ * inside its head in y and dx (and reaches dw*). A position outside [0, table_rows) makes that token's rotated elements of y NaN,
+ * and in the backward all of dx of that token's q and k heads and the rotated dims of dw*; nothing is read outside the table.
+ * v heads are copied bit for bit out of place (dx = dy in the backward) and not written in place. Allowed aliases, bitwise equal to
+ * the out-of-place call: y == x with ldy == ldx; dx == dy with lddx == lddy. Every other overlap of an output with an input is
+ * refused; dx must not overlap x. Columns W .. ld of an output row are never written.
+ * The weight sums leave each block as one f32 row [2][D] of the workspace (kf_qk_norm_rope_bwd_workspace_bytes; needed only when dwq
+ * or dwk is given) and a second small kernel adds the rows in a fixed order: no atomics, bitwise reproducible, and the workspace
+ * needs no initialisation. The backward keeps nothing but x.
+ * With every head start, both tables and the weights 16-byte aligned, D a multiple of two 16-byte packs (D / pack <= 128) and R = 0
+ * or R/2 a multiple of the pack, the call moves 16-byte packs; an odd leading dimension or base keeps the same lanes on the same
+ * elements (the same bits); any other geometry (R = 2, an odd D) takes an element kernel. Offsets are 64-bit. Neither entry
+ * synchronises or allocates: calls can be captured with kf_graph_*. B, S or D of 0 is KF_OK without a launch. Every argument is
+ * checked before any device call: KF_ERR_INVALID (dtype, negative extents, Hq + Hk < 1, R odd or > D, interleaved not 0 / 1, eps
+ * negative or not finite, a leading dimension < W, a null operand, R > 0 without tables, table_rows < 1, no positions with
+ * S > table_rows, a base not aligned to its element, a forbidden overlap, a workspace that is too small).
+ */
+int kf_qk_norm_rope_fwd(int dtype, int64_t B, int64_t S, int64_t Hq, int64_t Hk, int64_t Hv, int64_t D, int64_t rotary_dim,
+                        int interleaved, double eps, const void *wq, const void *wk, const float *cos, const float *sin,
+                        int64_t table_rows, const int64_t *positions, const void *x, int64_t ldx, void *y, int64_t ldy, void *stream);
+int kf_qk_norm_rope_bwd_workspace_bytes(int dtype, int64_t B, int64_t S, int64_t Hq, int64_t Hk, int64_t Hv, int64_t D, size_t *bytes);
+int kf_qk_norm_rope_bwd(int dtype, int64_t B, int64_t S, int64_t Hq, int64_t Hk, int64_t Hv, int64_t D, int64_t rotary_dim,
+                        int interleaved, double eps, const void *wq, const void *wk, const float *cos, const float *sin,
+                        int64_t table_rows, const int64_t *positions, const void *x, int64_t ldx, const void *dy, int64_t lddy,
+                        void *dx, int64_t lddx, void *dwq, void *dwk, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128

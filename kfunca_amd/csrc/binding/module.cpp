@@ -17,6 +17,7 @@
 #include "softmax.h"
 #include "ops.h"
 #include "optim.h"
+#include "qk_norm.h"
 #include "rope.h"
 #include "tensor.h"
 #include "tensor_iterator.h"
@@ -446,6 +447,22 @@ PYBIND11_MODULE(_C, m) {
     m.def("rope", [](const Tensor &x, const Tensor &cos, const Tensor &sin, py::object positions, bool interleaved) {
         return gpu::rope(x, cos, sin, positions.is_none() ? Tensor() : positions.cast<Tensor>(), interleaved);
     }, py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("positions") = py::none(), py::arg("interleaved") = false);
+    m.def("qk_norm_rope", [](const Tensor &qkv, py::object q_weight, py::object k_weight, py::object cos, py::object sin, int64_t B, int64_t S, int64_t H,
+                             py::object kv_heads, py::object positions, bool interleaved, double eps) {
+        auto opt = [](const py::object &o) { return o.is_none() ? Tensor() : o.cast<Tensor>(); };
+        return gpu::qk_norm_rope(qkv, opt(q_weight), opt(k_weight), opt(cos), opt(sin), B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>(),
+                                 opt(positions), interleaved, eps);
+    }, py::arg("qkv"), py::arg("q_weight"), py::arg("k_weight"), py::arg("cos"), py::arg("sin"), py::arg("B"), py::arg("S"), py::arg("H"),
+          py::arg("kv_heads") = -1, py::arg("positions") = py::none(), py::arg("interleaved") = false, py::arg("eps") = 1e-6,
+          "qk_norm_rope(qkv, q_weight, k_weight, cos, sin, B, S, H, kv_heads=-1, positions=None, interleaved=False, eps=1e-6): the per-head "
+          "QK-norm of Chameleon / Qwen3 / Gemma-3 / OLMo-2 fused with the rotary embedding, on the contiguous packed projection "
+          "[B*S, (H + 2 kv_heads) D] (q | k | v heads; kv_heads = -1 means H). For every q head (q_weight) and every k head (k_weight): "
+          "rstd = 1 / sqrt(mean(x^2) + eps), n = x * rstd * w, then the rotation of rope_qkv over the leading rotary_dim dims; v is copied. "
+          "Everything is f32 on the stored values with a single rounding, at the store (rms_norm followed by rope_qkv rounds n in between, so "
+          "its bits differ). Returns a new packed tensor for attention_qkv, causal_attention_qkv and the GQA operators. cos = sin = None is "
+          "the norm alone; a weight may be None (1, no gradient). Differentiable in qkv, q_weight and k_weight (the tables get no gradient): "
+          "the backward keeps only its input (qkv, the weights, the tables and the positions) and recomputes rstd. The weight multiplies as "
+          "given: for the Gemma convention (1 + w) pass 1 + w.");
     // gated activations (one launch each way; the packed [..., 2F] gate | up projection is read in place): torch's F.gelu argument name
     auto gelu_kind = [](const std::string &approximate) {
         CHECK_FAIL(approximate == "none" || approximate == "tanh", approximate, " is not a valid value for approximate ('none' or 'tanh')");

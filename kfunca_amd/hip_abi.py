@@ -52,6 +52,7 @@ EXPORTS = [
     "kf_rope", "kf_rope_table",
     "kf_glu_fwd", "kf_glu_bwd",
     "kf_softmax_fwd", "kf_softmax_bwd",
+    "kf_qk_norm_rope_fwd", "kf_qk_norm_rope_bwd_workspace_bytes", "kf_qk_norm_rope_bwd",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
     "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa",
@@ -208,6 +209,11 @@ def lib():
         _lib.kf_glu_bwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
         _lib.kf_softmax_fwd.argtypes = [C.c_int, C.c_int, i64, i64, C.c_float, vp, i64, vp, i64, vp]
         _lib.kf_softmax_bwd.argtypes = [C.c_int, C.c_int, i64, i64, C.c_float, vp, i64, vp, i64, vp, i64, vp]
+        _lib.kf_qk_norm_rope_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, i64, C.c_int, C.c_double, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64,
+                                             vp]
+        _lib.kf_qk_norm_rope_bwd_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.POINTER(sz)]
+        _lib.kf_qk_norm_rope_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, i64, C.c_int, C.c_double, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64,
+                                             vp, i64, vp, vp, vp, sz, vp]
         _lib.kf_comm_unique_id.argtypes = [C.c_char_p]
         _lib.kf_comm_init.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int, C.c_int]
         _lib.kf_comm_destroy.argtypes = [vp]
@@ -738,6 +744,41 @@ def softmax_fwd(kind, dtype, rows, V, scale, x, ldx, y, ldy, stream=None):
 def softmax_bwd(kind, dtype, rows, V, scale, y, ldy, dy, lddy, dx, lddx, stream=None):
     """The backward of softmax_fwd from its OUTPUT y and dy (kf_softmax_bwd). dx may be dy (same leading dimension)."""
     check(lib().kf_softmax_bwd(kind, dtype, rows, V, scale, y, ldy, dy, lddy, dx, lddx, stream))
+
+
+def qk_norm_rope_fwd(dtype, B, S, Hq, Hk, Hv, D, x, ldx, y=None, ldy=None, wq=None, wk=None, cos=None, sin=None, table_rows=0, rotary_dim=0,
+                     positions=None, interleaved=False, eps=1e-6, stream=None):
+    """Per-head RMS norm of the q and k heads of the packed [B*S, (Hq + Hk + Hv) D] projection fused with the rotary embedding
+    (kf_qk_norm_rope_fwd): n = x rstd w per head, then kf_rope's rotation over the leading rotary_dim dims, in f32 with one rounding.
+    Leading dimensions in elements; y = None: in place (y = x, ldy = ldx). wq / wk = None: weight 1. rotary_dim = 0: the norm alone
+    (cos, sin, positions are ignored); otherwise cos / sin are f32 [table_rows, rotary_dim / 2] device tables as for rope."""
+    if y is None:
+        y, ldy = x, ldx
+    check(lib().kf_qk_norm_rope_fwd(dtype, B, S, Hq, Hk, Hv, D, rotary_dim, int(interleaved), float(eps), wq, wk, cos, sin, table_rows, positions,
+                                    x, ldx, y, ldx if ldy is None else ldy, stream))
+
+
+def qk_norm_rope_bwd_workspace_bytes(dtype, B, S, Hq, Hk, Hv, D) -> int:
+    """Bytes of f32 scratch kf_qk_norm_rope_bwd needs for dwq / dwk (none is needed without them); it needs no initialisation."""
+    need = C.c_size_t(0)
+    check(lib().kf_qk_norm_rope_bwd_workspace_bytes(dtype, B, S, Hq, Hk, Hv, D, C.byref(need)))
+    return need.value
+
+
+def qk_norm_rope_bwd(dtype, B, S, Hq, Hk, Hv, D, x, ldx, dy, lddy, dx=None, lddx=None, dwq=None, dwk=None, wq=None, wk=None, cos=None, sin=None,
+                     table_rows=0, rotary_dim=0, positions=None, interleaved=False, eps=1e-6, workspace=None, workspace_bytes=None, stream=None):
+    """The backward of qk_norm_rope_fwd from its INPUT x and dy (kf_qk_norm_rope_bwd): rstd and xhat are recomputed, nothing else is kept.
+    dx = None: dx = dy in place (v heads untouched). dwq / dwk = None: not computed. When one is wanted and no workspace is given, one of
+    qk_norm_rope_bwd_workspace_bytes is allocated for the call and returned (keep it until the stream is synchronised)."""
+    if dx is None:
+        dx, lddx = dy, lddy
+    own = None
+    if (dwq or dwk) and workspace is None:
+        own = DevBuf(max(qk_norm_rope_bwd_workspace_bytes(dtype, B, S, Hq, Hk, Hv, D), 4))
+        workspace, workspace_bytes = own.ptr, own.nbytes
+    check(lib().kf_qk_norm_rope_bwd(dtype, B, S, Hq, Hk, Hv, D, rotary_dim, int(interleaved), float(eps), wq, wk, cos, sin, table_rows, positions,
+                                    x, ldx, dy, lddy, dx, lddy if lddx is None else lddx, dwq, dwk, workspace, workspace_bytes or 0, stream))
+    return own  # keep alive until the stream is synchronised
 
 
 def device_sync():
