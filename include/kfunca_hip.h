@@ -606,6 +606,50 @@ int kf_attn_window_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq
                        const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Document-masked softmax attention: one row of [B, H, S, D] holds several independent sequences packed end to end (packed documents
+ * in LM pre-training, packed images of a vision encoder); a token attends inside its own document only. Self-attention: Sq = Skv = S.
+ *
+ * kf_attn_doc_table turns the documents' cumulative lengths into the per-token tables the kernels read. cu_doclens: int64
+ * [B, n_docs + 1] on the device. With c_j = clamp(cu[b, j], 0, S) and c_0 taken as 0 whatever it holds, document j of row b holds the
+ * tokens c_j <= m < c_{j+1} (a zero-length document owns no token: a ragged list is padded by repeating its last value) and
+ * len_b = c_n. Written: kv_len[b] = len_b (int64 [B]); for a token of document j doc_start[b, m] = c_j and doc_end[b, m] = c_{j+1}
+ * (int32 [B, S]); for m >= len_b doc_start = doc_end = len_b. cu[b, :] must be nondecreasing; if it is not the mask is unspecified, but
+ * every value written lies in [0, S] with start <= end. One launch, one thread per token (a binary search over its row), no atomics,
+ * capturable; profile label attn_doc_table. KF_ERR_INVALID: n_docs < 1, a negative extent, a null pointer; B or S equal to 0 is KF_OK
+ * without a launch. The tables are built once per batch and serve every layer, forward and backward.
+ *
+ * kf_attn_doc_fwd / kf_attn_doc_bwd:
+ *     len_b = clamp(kv_len[b], 0, S)   (kv_len == NULL: S)
+ *     query m sees key n   <=>   n < len_b  and  doc_start[b, m] <= n < doc_end[b, m]  and  (causal == 0 or n <= m)
+ * causal: 0 or 1, anything else is KF_ERR_INVALID (checked first). doc_start and doc_end are required: NULL is KF_ERR_INVALID wherever
+ * a NULL operand is. The tables must describe a partition of the tokens into consecutive intervals - what kf_attn_doc_table writes;
+ * then the relation is symmetric, and the dK/dV kernel reads the same two arrays at the key index to learn which queries see a key.
+ * Every entry is clamped when it is read, so no table content moves an access outside an operand.
+ * Everything not said here is kf_attn_full_*'s contract with this entry's name in kf_last_error(): operands, grouped K/V heads, the
+ * layout rule, lse (lse = -inf and o = 0 as zero bits for a token in no document; dq = 0 there; rows of dk and dv that no query sees
+ * are written as zeros), K and V rows at n >= len_b never read, no atomics and bitwise reproducible, the argument checks and their
+ * statuses, zero extents, capturability. S >= 2^31 is KF_ERR_UNSUPPORTED (the tables are 32-bit). The workspace is
+ * kf_attn_full_bwd_workspace_bytes(dtype, B, Hq, Hkv, S, S, D)'s; there is no second size query.
+ * Kernels: the kernels of kf_attn_full_* compiled with the document mask - the window variant's interval per lane, read from the
+ * tables: a query block walks the key tiles from that of its first row's start to that of its last row's end, a key block the query
+ * tiles likewise; a wave skips tiles outside the interval of its 32 rows; tiles an edge crosses select on their scores. Profile labels
+ * attn_doc_fwd_mfma_d64 / _d128, attn_doc_bwd_dq_mfma_*, attn_doc_bwd_dkv_mfma_*, attn_doc_*_generic; the delta pre-pass keeps
+ * attn_full_bwd_delta (attn_full_bwd_delta_generic).
+ */
+int kf_attn_doc_table(int64_t B, int64_t S, int64_t n_docs, const int64_t *cu_doclens, int64_t *kv_len, int32_t *doc_start,
+                      int32_t *doc_end, void *stream);
+int kf_attn_doc_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D, float scale, int causal,
+                    const int64_t *kv_len, const int32_t *doc_start, const int32_t *doc_end, const void *q, const kf_attn_layout *lq,
+                    const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, void *o,
+                    const kf_attn_layout *lo, float *lse, void *stream);
+int kf_attn_doc_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D, float scale, int causal,
+                    const int64_t *kv_len, const int32_t *doc_start, const int32_t *doc_end, const void *q, const kf_attn_layout *lq,
+                    const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, const void *o,
+                    const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
+                    const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- rotary position embeddings (no reference counterpart: the position signal between the QKV projection and attention) ---- */
 /*
  * x, y: [B, H, S, D] addressed by kf_attn_layout element strides of B, H, S; D is contiguous; dtype in {KF_F32, KF_BF16, KF_F16};

@@ -410,11 +410,31 @@ PYBIND11_MODULE(_C, m) {
         out = {v[0], v[1]};
         return &out;
     };
-    m.def("attention", [opt, win](const Tensor &q, const Tensor &k, const Tensor &v, py::object kv_len, bool causal, py::object prefix_len, py::object window) {
+    // doc_mask = doc_mask(cu_doclens, S): the document mask of packed rows - several sequences end to end in one row, attention inside each
+    py::class_<gpu::DocMask>(m, "DocMask", py::module_local(),
+                             "The per-token tables of a document mask (doc_mask(cu_doclens, S)): kv_len Long [B], doc_start and doc_end Int [B, S], B, S. "
+                             "Built once per batch, passed as doc_mask= to attention and attention_qkv by every layer.")
+        .def_readonly("kv_len", &gpu::DocMask::kv_len)
+        .def_readonly("doc_start", &gpu::DocMask::doc_start)
+        .def_readonly("doc_end", &gpu::DocMask::doc_end)
+        .def_readonly("B", &gpu::DocMask::B)
+        .def_readonly("S", &gpu::DocMask::S);
+    m.def("doc_mask", &gpu::doc_mask, py::arg("cu_doclens"), py::arg("S"),
+          "doc_mask(cu_doclens, S) -> DocMask. cu_doclens: Long [B, n_docs + 1] on the device, the cumulative document lengths of each packed row:\n"
+          "cu[b, 0] = 0 and document j of row b holds the tokens cu[b, j] <= m < cu[b, j+1]; a row with fewer documents repeats its last value\n"
+          "(a zero-length document owns no token); values are clamped to [0, S], rows must be nondecreasing. Tokens at or beyond cu[b, -1] are\n"
+          "in no document. One launch; the DocMask is reused by every layer, forward and backward.");
+    auto doc = [](const char *op, const py::object &d) -> const gpu::DocMask * {
+        if (d.is_none()) return nullptr;
+        if (!py::isinstance<gpu::DocMask>(d)) throw py::value_error(std::string(op) + ": doc_mask is a DocMask (doc_mask(cu_doclens, S)) or None");
+        return d.cast<const gpu::DocMask *>();
+    };
+    m.def("attention", [opt, win, doc](const Tensor &q, const Tensor &k, const Tensor &v, py::object kv_len, bool causal, py::object prefix_len, py::object window,
+                                       py::object doc_mask) {
         gpu::AttentionWindow w;
-        return gpu::attention(q, k, v, opt(kv_len), causal, opt(prefix_len), win("attention", window, w));
+        return gpu::attention(q, k, v, opt(kv_len), causal, opt(prefix_len), win("attention", window, w), doc("attention", doc_mask));
     }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kv_len") = py::none(), py::arg("causal") = false, py::arg("prefix_len") = py::none(),
-          py::arg("window") = py::none(),
+          py::arg("window") = py::none(), py::arg("doc_mask") = py::none(),
           "Softmax attention of q [B, Hq, Sq, D] over k, v [B, Hkv, Skv, D]. kv_len: Long [B], batch b sees keys n < kv_len[b]. causal=True adds\n"
           "the prefix-LM mask: query m sees key n iff n < kv_len[b] and (n < prefix_len[b] or n <= m), top-left aligned; prefix_len: Long [B]\n"
           "or None (no prefix: causal attention over a padded batch), refused with causal=False. A plain causal call without lengths is\n"
@@ -422,17 +442,22 @@ PYBIND11_MODULE(_C, m) {
           "window: None, or a pair (left, right) for sliding-window attention: query m sees key n iff n < kv_len[b] and m - left <= n <= m + right,\n"
           "top-left aligned. Each side is a non-negative int or None (unbounded on that side); negative values are refused. causal=True with a\n"
           "window means right = 0 (a right side other than 0 or None is refused); window together with prefix_len is refused. A query that\n"
-          "sees no key gives a zero row.");
-    m.def("attention_qkv", [opt, win](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object kv_len, bool causal,
-                                      py::object prefix_len, py::object window) {
+          "sees no key gives a zero row.\n"
+          "doc_mask: None, or a DocMask (doc_mask(cu_doclens, S)) for packed rows: each row holds several documents end to end and query m sees\n"
+          "key n iff both lie in the same document (causal=True: and n <= m). Self-attention only (Sq = Skv = S of the mask); doc_mask together\n"
+          "with kv_len, prefix_len or window is refused, and so is a mask built for another B, S or device. A token in no document gives a\n"
+          "zero row.");
+    m.def("attention_qkv", [opt, win, doc](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object kv_len, bool causal,
+                                           py::object prefix_len, py::object window, py::object doc_mask) {
         gpu::AttentionWindow w;
         return gpu::attention_qkv(qkv, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>(), opt(kv_len), causal, opt(prefix_len),
-                                  win("attention_qkv", window, w));
+                                  win("attention_qkv", window, w), doc("attention_qkv", doc_mask));
     }, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none(), py::arg("kv_len") = py::none(),
-          py::arg("causal") = false, py::arg("prefix_len") = py::none(), py::arg("window") = py::none(),
+          py::arg("causal") = false, py::arg("prefix_len") = py::none(), py::arg("window") = py::none(), py::arg("doc_mask") = py::none(),
           "attention on the packed projection [B*S, (H + 2*kv_heads)*D] (columns q | k | v), read in place; the result is [B*S, H*D]. kv_len,\n"
           "causal and prefix_len as in attention (Sq = Skv = S). A plain causal call without lengths is faster through causal_attention_qkv.\n"
-          "window: as in attention.");
+          "window: as in attention.\n"
+          "doc_mask: as in attention (a DocMask built for this B and S).");
     // rotary position embeddings: f64-accurate tables, and the rotation of q and k in place in the packed projection (one launch each way)
     m.def("rope_table", [](int64_t max_positions, int64_t rotary_dim, double base, int device) {
         auto [c, sn] = gpu::rope_table(max_positions, rotary_dim, base, device);

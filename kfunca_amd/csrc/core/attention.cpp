@@ -1,6 +1,6 @@
 // namespace gpu: the attention operators over the C ABI's attention entries - causal_attention, causal_attention_gqa and
 // causal_attention_qkv (ops.h; nn_ops.cpp:6-8 + the checks of causal_attention_kernel.cu:9-20), attention and attention_qkv (attn_full.h).
-// Five families of entries (the causal pair, full attention and its prefix-LM and sliding-window forms), one host path: check, plan the padding, pad,
+// Six families of entries (the causal pair, full attention and its prefix-LM, sliding-window and document-masked forms), one host path: check, plan the padding, pad,
 // allocate, call, un-pad.
 #include <cmath>
 
@@ -25,13 +25,17 @@ enum class Family {
     Full,      // kf_attn_full_fwd / kf_attn_full_bwd: no mask but an optional per-batch key length
     Prefix,    // kf_attn_prefix_fwd / kf_attn_prefix_bwd: Full's operands and checks; causal beyond an optional per-batch prefix
     Window,    // kf_attn_window_fwd / kf_attn_window_bwd: Full's operands and checks; keys m - left .. m + right of query m
+    Doc,       // kf_attn_doc_fwd / kf_attn_doc_bwd: Full's operands and checks, Sq = Skv; the keys of the query's own document
 };
-bool full_like(Family f) { return f == Family::Full || f == Family::Prefix || f == Family::Window; }
+bool full_like(Family f) { return f == Family::Full || f == Family::Prefix || f == Family::Window || f == Family::Doc; }
 // the length arrays of attention / attention_qkv: undefined tensors for the other families; with them the window of Family::Window
 // (-1: unbounded on that side), which the backward keeps beside the lengths
+// and the tables of Family::Doc (a DocMask's, kv among them) with its causal flag
 struct Lens {
     Tensor kv, prefix;
     int64_t wl = -1, wr = -1;
+    Tensor doc_start, doc_end;
+    bool doc_causal = false;
 };
 
 // One call as the C ABI takes it: the sizes handed down (padded ones where the host pads), the scale of the REAL head size, and the
@@ -45,6 +49,8 @@ struct Call {
     const kf_attn_layout *lx, *lo;
     bool padded;
     int64_t wl, wr;
+    const int32_t *doc_start, *doc_end;
+    int doc_causal;
 };
 
 void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o, float *lse) {
@@ -66,6 +72,10 @@ void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o
         break;
     case Family::Window:
         DEV_CALL(kf_attn_window_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.wl, c.wr, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        break;
+    case Family::Doc:
+        DEV_CALL(kf_attn_doc_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, c.doc_causal, c.kv_len, c.doc_start, c.doc_end, q, c.lx, k, c.lx, v, c.lx, o, c.lo,
+                                 lse, st));
         break;
     }
 }
@@ -96,6 +106,10 @@ void run_bwd(const Call &c, const void *q, const void *k, const void *v, const v
     case Family::Window:
         DEV_CALL(kf_attn_window_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.wl, c.wr, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo,
                                     dq, c.lx, dk, c.lx, dv, c.lx, ws, bytes, st));
+        break;
+    case Family::Doc:
+        DEV_CALL(kf_attn_doc_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, c.doc_causal, c.kv_len, c.doc_start, c.doc_end, q, c.lx, k, c.lx, v, c.lx, o, c.lo,
+                                 lse, go, c.lo, dq, c.lx, dk, c.lx, dv, c.lx, ws, bytes, st));
         break;
     }
 }
@@ -128,6 +142,7 @@ DataPtr bwd_scratch(const Call &c, size_t &bytes) {
     case Family::Full: // one size, no smaller form to retry with
     case Family::Prefix:
     case Family::Window:
+    case Family::Doc:
         DEV_CALL(kf_attn_full_bwd_workspace_bytes(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, &bytes));
         return DeviceAllocator::GetInstance()->allocate(bytes > 0 ? bytes : 1, c.device);
     }
@@ -160,8 +175,11 @@ Tensor check_len(const Tensor &kv_len, int64_t B, int device, const char *name =
     CHECK_FAIL(kv_len.numel() == B && kv_len.device() == device, "attention: ", name, " must hold B = ", B, " elements on the operands' device");
     return kv_len.dense();
 }
-Lens check_lens(const Lens &l, int64_t B, int device) { return {check_len(l.kv, B, device), check_len(l.prefix, B, device, "prefix_len"), l.wl, l.wr}; }
+Lens check_lens(const Lens &l, int64_t B, int device) {
+    return {check_len(l.kv, B, device), check_len(l.prefix, B, device, "prefix_len"), l.wl, l.wr, l.doc_start, l.doc_end, l.doc_causal};
+}
 const int64_t *len_ptr(const Tensor &kv_len) { return kv_len.defined() ? static_cast<const int64_t *>(kv_len.data_ptr()) : nullptr; }
+const int32_t *tab_ptr(const Tensor &t) { return t.defined() ? static_cast<const int32_t *>(t.data_ptr()) : nullptr; }
 
 // The extents handed down. The MFMA kernels want D = 64 or 128 (and, f32, whole tiles of 32 rows); everything else takes the generic
 // vector-ALU kernel (two orders of magnitude slower). Zero columns change neither Q K^T nor P V (the softmax scale stays 1 / sqrt(D) of
@@ -203,7 +221,7 @@ Tensor unpad(const Tensor &t, int64_t rows, int64_t cols) {
 Call contiguous_call(Family f, const Tensor &q, const Tensor &k, const PadPlan &pp, const Lens &len) {
     const bool padded = pp.Sq != q.shape(2) || pp.Skv != k.shape(2) || pp.D != q.shape(3);
     return {f, code(q.dtype()), q.device(), q.shape(0), q.shape(1), k.shape(1), pp.Sq, pp.Skv, pp.D, 1.0f / std::sqrt((float)q.shape(3)),
-            len_ptr(len.kv), len_ptr(len.prefix), nullptr, nullptr, padded, len.wl, len.wr};
+            len_ptr(len.kv), len_ptr(len.prefix), nullptr, nullptr, padded, len.wl, len.wr, tab_ptr(len.doc_start), tab_ptr(len.doc_end), len.doc_causal};
 }
 
 std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len) {
@@ -277,7 +295,7 @@ PackedLay packed_layouts(int64_t S, int64_t H, int64_t Hkv, int64_t D) {
 // family CausalMha is Hkv = H here: K at column H D, V at 2 H D (the strided entries); otherwise K at H D, V at (H + Hkv) D
 Call packed_call(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D, const PackedLay &L, const Lens &len) {
     return {f, code(qkv.dtype()), qkv.device(), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), len_ptr(len.kv), len_ptr(len.prefix), &L.qkv, &L.flat, false,
-            len.wl, len.wr};
+            len.wl, len.wr, tab_ptr(len.doc_start), tab_ptr(len.doc_end), len.doc_causal};
 }
 
 class PackedAttentionGradFunction : public GradFunction {
@@ -310,8 +328,8 @@ private:
     int64_t B_, S_, H_, Hkv_;
 };
 
-// f: CausalMha for causal_attention_qkv(qkv, B, S, H) (Hkv = H, the [B*S, 3*H*D] texts), CausalGqa for its kv_heads form, Full, Prefix
-// and Window for attention_qkv
+// f: CausalMha for causal_attention_qkv(qkv, B, S, H) (Hkv = H, the [B*S, 3*H*D] texts), CausalGqa for its kv_heads form, Full, Prefix,
+// Window and Doc for attention_qkv
 Tensor packed_attention(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, const Lens &lens) {
     const char *op = full_like(f) ? "attention_qkv" : "causal_attention_qkv";
     CHECK_FAIL(qkv.defined() && qkv.dim() == 2 && qkv.is_dense(), op,
@@ -359,6 +377,24 @@ std::tuple<Tensor, Tensor, Tensor> causal_attention_bwd(const Tensor &q, const T
 }
 Tensor causal_attention(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalMha, q, k, v, Lens()); }
 Tensor causal_attention_gqa(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalGqa, q, k, v, Lens()); }
+// A document mask is a family of its own: the mask carries its key lengths, so kv_len beside it - like a prefix or a window, masks
+// this package does not combine with it - is refused, and so is a mask built for another batch, length or device (B_, S_, device:
+// the operands'; Sq: the query length, Sq != Skv being cross-attention between packed rows).
+static Family doc_family(const char *op, bool causal, const Tensor &prefix_len, const AttentionWindow *window, Lens &lens, const DocMask *doc, int64_t B_,
+                         int64_t Sq, int64_t S_, int device) {
+    CHECK_FAIL(!lens.kv.defined() && !prefix_len.defined() && !window, op,
+               ": doc_mask cannot be combined with kv_len, prefix_len or window (the mask carries the rows' lengths; a window or a prefix inside "
+               "documents is not supported)");
+    CHECK_FAIL(doc->kv_len.defined() && doc->doc_start.defined() && doc->doc_end.defined(), op, ": doc_mask is empty (build it with doc_mask(cu_doclens, S))");
+    CHECK_FAIL(Sq == S_, op, ": doc_mask needs self-attention, Sq = Skv (got Sq = ", Sq, ", Skv = ", S_, ")");
+    CHECK_FAIL(doc->B == B_ && doc->S == S_, op, ": doc_mask was built for B = ", doc->B, ", S = ", doc->S, ", the operands have B = ", B_, ", S = ", S_);
+    CHECK_FAIL(doc->kv_len.device() == device, op, ": doc_mask must be on the operands' device");
+    lens.kv = doc->kv_len;
+    lens.doc_start = doc->doc_start;
+    lens.doc_end = doc->doc_end;
+    lens.doc_causal = causal;
+    return Family::Doc;
+}
 // causal = false is the full family's path, call for call; a prefix belongs to the causal mask. Without a window the calls are those
 // made before windows existed. With one: causal closes its right side (right = 0), so another right side contradicts it, and a window
 // beside a prefix is no mask this package has.
@@ -375,10 +411,32 @@ static Family masked_family(const char *op, bool causal, const Tensor &prefix_le
     return causal ? Family::Prefix : Family::Full;
 }
 Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, bool causal, const Tensor &prefix_len,
-                 const AttentionWindow *window) {
+                 const AttentionWindow *window, const DocMask *doc_mask) {
     Lens lens{kv_len, prefix_len};
-    const Family f = masked_family("attention", causal, prefix_len, window, lens);
+    if (doc_mask) check_operands(Family::Doc, q, k, v); // the shapes the mask is compared with
+    const Family f = doc_mask ? doc_family("attention", causal, prefix_len, window, lens, doc_mask, q.shape(0), q.shape(2), k.shape(2), q.device())
+                              : masked_family("attention", causal, prefix_len, window, lens);
     return contiguous_attention(f, q, k, v, lens);
+}
+
+// One launch (kf_attn_doc_table); the three tensors are dense and live on cu_doclens' device.
+DocMask doc_mask(const Tensor &cu_doclens, int64_t S) {
+    CHECK_FAIL(cu_doclens.defined() && cu_doclens.dim() == 2 && cu_doclens.dtype() == ScalarType::Long && cu_doclens.shape(1) >= 2,
+               "doc_mask expects cu_doclens of type Long and shape [B, n_docs + 1] with n_docs >= 1");
+    CHECK_FAIL(S >= 0 && S < (int64_t(1) << 31), "doc_mask: S ", S, " outside [0, 2^31)");
+    const Tensor cu = cu_doclens.dense();
+    const int64_t B = cu.shape(0), n = cu.shape(1) - 1;
+    const int device = cu.device();
+    DocMask m;
+    m.B = B;
+    m.S = S;
+    m.kv_len = zeros({B}, ScalarType::Long, device); // (S = 0 launches nothing: every length is 0)
+    m.doc_start = empty({B, S}, ScalarType::Int, device);
+    m.doc_end = empty({B, S}, ScalarType::Int, device);
+    if (B > 0 && S > 0)
+        DEV_CALL(kf_attn_doc_table(B, S, n, static_cast<const int64_t *>(cu.data_ptr()), static_cast<int64_t *>(m.kv_len.data_ptr()),
+                                   static_cast<int32_t *>(m.doc_start.data_ptr()), static_cast<int32_t *>(m.doc_end.data_ptr()), dev::stream(device)));
+    return m;
 }
 
 Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H) { return packed_attention(Family::CausalMha, qkv, B, S, H, H, Lens()); }
@@ -387,9 +445,10 @@ Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, 
     return causal_attention_qkv(qkv, B, S, H);
 }
 Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len, bool causal, const Tensor &prefix_len,
-                     const AttentionWindow *window) {
+                     const AttentionWindow *window, const DocMask *doc_mask) {
     Lens lens{kv_len, prefix_len};
-    const Family f = masked_family("attention_qkv", causal, prefix_len, window, lens);
+    const Family f = doc_mask ? doc_family("attention_qkv", causal, prefix_len, window, lens, doc_mask, B, S, S, qkv.defined() ? qkv.device() : 0)
+                              : masked_family("attention_qkv", causal, prefix_len, window, lens);
     return packed_attention(f, qkv, B, S, H, kv_heads < 0 ? H : kv_heads, lens);
 }
 

@@ -1,5 +1,5 @@
 // namespace gpu: full (non-causal) softmax attention with an optional per-batch key length (kf_attn_full_fwd, kf_attn_full_bwd) and its
-// prefix-LM / padded-causal form (kf_attn_prefix_fwd, kf_attn_prefix_bwd) and its sliding-window form (kf_attn_window_fwd, kf_attn_window_bwd), with autograd. No reference counterpart: the self-attention of a vision / audio encoder (every token sees every token), cross-attention
+// prefix-LM / padded-causal form (kf_attn_prefix_fwd, kf_attn_prefix_bwd) and its sliding-window form (kf_attn_window_fwd, kf_attn_window_bwd) and its document-masked form for packed rows (kf_attn_doc_fwd, kf_attn_doc_bwd), with autograd. No reference counterpart: the self-attention of a vision / audio encoder (every token sees every token), cross-attention
 // (Sq text queries over Skv image keys, in either size order) and padded batches (keys beyond a sample's own length are invisible).
 #pragma once
 
@@ -24,13 +24,27 @@ namespace gpu {
 // key n iff n < kv_len[b], n >= m - left and n <= m + right, top-left aligned; -1 is "unbounded on that side", anything below is
 // refused. causal = true with a window means right = 0 (a right side above 0 is refused); a window beside prefix_len is refused.
 // A query that sees no key (m - left >= kv_len[b]) gives a zero row and zero gradients; a key no query sees has zero gradients.
+// doc_mask (kf_attn_doc_table, kf_attn_doc_fwd, kf_attn_doc_bwd): null (the calls above, unchanged) or the document mask of packed rows:
+// one row of [B, H, S, D] holds several independent sequences end to end, and query m sees key n iff both lie in the same document
+// (and, with causal = true, n <= m). Self-attention only (Sq = Skv = S of the mask); beside kv_len, prefix_len or a window it is
+// refused. A token in no document (the padded tail of a row) gives a zero row and zero gradients.
 struct AttentionWindow { int64_t left, right; };
+// doc_mask(cu_doclens, S): cu_doclens Long [B, n + 1] on the device, the cumulative document lengths of each row (cu[b, 0] = 0; document
+// j holds tokens cu[b, j] <= m < cu[b, j + 1]; a shorter list is padded by repeating its last value; values are clamped to [0, S]).
+// Returns the tables the kernels read: kv_len Long [B] (the tokens of row b that lie in a document), doc_start and doc_end Int [B, S]
+// (the interval of each token's document; both kv_len[b] beyond it). Built once per batch - one launch - and reused by every layer,
+// forward and backward.
+struct DocMask {
+    Tensor kv_len, doc_start, doc_end;
+    int64_t B = 0, S = 0;
+};
+DocMask doc_mask(const Tensor &cu_doclens, int64_t S);
 Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, bool causal = false, const Tensor &prefix_len = Tensor(),
-                 const AttentionWindow *window = nullptr);
+                 const AttentionWindow *window = nullptr, const DocMask *doc_mask = nullptr);
 // attention_qkv(qkv, B, S, H, kv_heads, kv_len): the packed projection [B*S, (H + 2*Hkv)*D] (columns q | k | v; kv_heads < 0: Hkv = H)
 // is read in place, the result is [B*S, H*D] and the backward writes one packed gradient - the layouts causal_attention_qkv builds.
-// causal, prefix_len, window: as in attention (Sq = Skv = S).
+// causal, prefix_len, window, doc_mask: as in attention (Sq = Skv = S).
 Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len, bool causal = false,
-                     const Tensor &prefix_len = Tensor(), const AttentionWindow *window = nullptr);
+                     const Tensor &prefix_len = Tensor(), const AttentionWindow *window = nullptr, const DocMask *doc_mask = nullptr);
 
 } // namespace gpu

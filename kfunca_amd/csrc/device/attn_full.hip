@@ -42,6 +42,16 @@
 // lo <= r < hi per lane (win_lim). A row may see no key of the first tile its block visits, or no key at all: the masked forward body
 // carries such a row with a stand-in for its maximum (f_qk_sm), and the backward bodies select its p to 0 before anything is
 // multiplied by it (its lse is -inf). (-1, -1) and (-1, 0) are dispatched to the two older families on the host.
+// The document variant (kf_attn_doc_*: several independent sequences packed end to end in one row, self-attention, Sq = Skv = S) is a
+// fourth MODE of the same kernels:
+//   query m sees key n  <=>  n < len_b and doc_start[b, m] <= n < doc_end[b, m] and (causal == 0 or n <= m)
+// The interval of the window variant, read from a per-token table (kf_attn_doc_table writes it from the documents' cumulative lengths)
+// instead of computed from m: each lane loads its row's (start, end) once, the block's first and last row give its tile range, the
+// wave's first and last row the tile skip and the choice of body, and the lane's own pair goes to the masked bodies of the window
+// variant (MASK 3) unchanged. The tables describe a partition of the tokens into consecutive intervals, so both columns are
+// nondecreasing along a row - which is what makes the first and last row of a block or wave its extremes - and the relation is
+// symmetric: the dK/dV kernel reads the same two arrays at the KEY index to learn which queries see a key. Every entry is clamped on
+// load, so no table content moves an access outside an operand; a table that is no partition gives an unspecified mask, nothing worse.
 // No kernel uses atomics; every result is bitwise reproducible run to run.
 #include <math.h>
 
@@ -74,9 +84,11 @@ struct FullArgs {
     Lay lq, lk, lv, lo, ldo, ldq, ldk, ldv;
     const int64_t *prefix_len; // [B] on the device, or null (the prefix-LM variant only; last, so no other member moves)
     int64_t wl, wr;            // the window variant only: keys m - wl .. m + wr; an unbounded side is kNoEdge
+    const int32_t *doc_start, *doc_end; // the document variant only: [B, S] on the device, the keys start <= n < end of each token
+    int causal;                         // the document variant only: 1 adds n <= m
 };
 
-enum Mode { M_FULL = 0, M_PREFIX = 1, M_WINDOW = 2 }; // the mask a kernel is compiled with
+enum Mode { M_FULL = 0, M_PREFIX = 1, M_WINDOW = 2, M_DOC = 3 }; // the mask a kernel is compiled with
 constexpr int64_t kNoEdge = (int64_t)1 << 40;         // a window side no index reaches (extents are at most 2^31): m - wl < 0, m + wr >= Skv
 
 __device__ __forceinline__ int64_t key_len(const FullArgs &a, int64_t b) {
@@ -317,6 +329,55 @@ __device__ __forceinline__ void win_lim(const FullArgs &a, int64_t len, int64_t 
     cnt = max(min(nl, clamp_i(qw + a.wr + 1 - kv0, -32, TK) + xl) - lo, 0);
 }
 
+// document variant, forward and dQ: the keys lo <= n < hi that query m of batch b sees, clamped into [0, len] (the key tiles walked and
+// the rows loaded follow from these alone); with causal the interval ends at the query itself. m < Sq.
+__device__ __forceinline__ int doc_lo(const FullArgs &a, int64_t b, int64_t m, int64_t len) { return clamp_i(a.doc_start[b * a.Sq + m], 0, (int)len); }
+__device__ __forceinline__ int doc_hi(const FullArgs &a, int64_t b, int64_t m, int64_t len) {
+    const int e = clamp_i(a.doc_end[b * a.Sq + m], 0, (int)len);
+    return a.causal && e > m + 1 ? (int)(m + 1) : e;
+}
+// document variant, dK/dV: the queries lo <= m < hi that see key n of batch b - the same two arrays read at the key (the relation is
+// symmetric), clamped into [0, Sq]; with causal the interval starts at the key itself. n < Skv = Sq.
+__device__ __forceinline__ int doc_qlo(const FullArgs &a, int64_t b, int64_t n) {
+    const int s = clamp_i(a.doc_start[b * a.Sq + n], 0, (int)a.Sq);
+    return a.causal && s < n ? (int)n : s;
+}
+__device__ __forceinline__ int doc_qhi(const FullArgs &a, int64_t b, int64_t n) { return clamp_i(a.doc_end[b * a.Sq + n], 0, (int)a.Sq); }
+// the rows of the tile at t0 inside lo <= r < hi, as win_in takes them: first row and row count
+__device__ __forceinline__ void doc_lim(int lo_abs, int hi_abs, int64_t t0, int &lo, int &cnt) {
+    lo = clamp_i(lo_abs - t0, 0, TK);
+    cnt = max(clamp_i(hi_abs - t0, 0, TK) - lo, 0);
+}
+// forward / dQ: the key tiles of query block xb, from the tile of the first key its first row sees to the tile of the last key its last
+// row (below Sq) sees; doc_lo and doc_hi lie in [0, len], so both tiles lie in [0, ceil(len / 64)]
+__device__ __forceinline__ int doc_first_tile(const FullArgs &a, int64_t b, int64_t len, int64_t xb) { return doc_lo(a, b, xb * TQ, len) / TK; }
+__device__ __forceinline__ int doc_last_tile(const FullArgs &a, int64_t b, int64_t len, int64_t xb) {
+    const int64_t last = (a.Sq < xb * TQ + TQ ? a.Sq : xb * TQ + TQ) - 1;
+    return (doc_hi(a, b, last, len) + TK - 1) / TK;
+}
+// forward / dQ: the interval of the lane's own row (empty for a row beyond Sq) and, wave-uniform, those of the wave's first row and of
+// its last row below Sq. Both columns are nondecreasing along a row, so the wave sees the keys lo_first .. hi_last - 1 and nothing else,
+// and every row of it sees every key of lo_last .. hi_first - 1.
+struct DocRows { int lo, hi, lo_first, lo_last, hi_first, hi_last; };
+template <bool DOC>
+__device__ __forceinline__ DocRows doc_rows(const FullArgs &a, int64_t b, int64_t len, int64_t qw, int64_t m, bool active) {
+    DocRows r{0, 0, 0, 0, 0, 0};
+    if constexpr (DOC) {
+        if (m < a.Sq) {
+            r.lo = doc_lo(a, b, m, len);
+            r.hi = doc_hi(a, b, m, len);
+        }
+        if (active) {
+            const int64_t last = (a.Sq < qw + 32 ? a.Sq : qw + 32) - 1;
+            r.lo_first = __builtin_amdgcn_readfirstlane(doc_lo(a, b, qw, len));
+            r.lo_last = __builtin_amdgcn_readfirstlane(doc_lo(a, b, last, len));
+            r.hi_first = __builtin_amdgcn_readfirstlane(doc_hi(a, b, qw, len));
+            r.hi_last = __builtin_amdgcn_readfirstlane(doc_hi(a, b, last, len));
+        }
+    }
+    return r;
+}
+
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
@@ -431,7 +492,7 @@ __device__ __forceinline__ void f_pv(const char *vt, const int (&vo)[DB][2], con
 template <bool BF, int D, int MODE>
 __global__ __launch_bounds__(NT, MODE != M_FULL && D == 64 ? 2 : 1) void attn_full_fwd_kernel(const FullArgs a) {
     using frag_t = typename AFrag<BF>::type;
-    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW;
+    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW, DOC = MODE == M_DOC;
     constexpr int KS = D / 16, DB = D / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
@@ -439,8 +500,8 @@ __global__ __launch_bounds__(NT, MODE != M_FULL && D == 64 ? 2 : 1) void attn_fu
     const int64_t bh = blockIdx.x / nxb, xb = block_of<MODE>(blockIdx.x % nxb, bh, nxb), b = bh / a.H, h = bh % a.H, g = h / a.G;
     const int64_t len = key_len(a, b);
     const int64_t pre = CAUSAL ? prefix_of(a, b) : 0;
-    const int nt = (int)((key_bound<MODE>(a, len, pre, xb) + TK - 1) / TK);
-    const int tf = first_tile<MODE>(a, xb); // 0 but under a window; there nt <= tf when no query of the block sees a key
+    const int nt = DOC ? doc_last_tile(a, b, len, xb) : (int)((key_bound<MODE>(a, len, pre, xb) + TK - 1) / TK);
+    const int tf = DOC ? doc_first_tile(a, b, len, xb) : first_tile<MODE>(a, xb); // 0 but under a window or a document mask; there nt <= tf when no query of the block sees a key
     const char *Kg = a.k + b * a.lk.sb + g * a.lk.sh;
     const char *Vg = a.v + b * a.lv.sb + g * a.lv.sh;
     int ko[KS], vo[DB][2];
@@ -454,6 +515,7 @@ __global__ __launch_bounds__(NT, MODE != M_FULL && D == 64 ? 2 : 1) void attn_fu
     const float c = a.scale * kLog2e;
     const int64_t qw = xb * TQ + wid * 32, m = qw + xl;
     const bool active = qw < a.Sq; // wave-uniform
+    const DocRows dr = doc_rows<DOC>(a, b, len, qw, m, active);
 
     frag_t qf[KS];
 #pragma unroll
@@ -499,6 +561,17 @@ __global__ __launch_bounds__(NT, MODE != M_FULL && D == 64 ? 2 : 1) void attn_fu
                 if (kv0 + TK > len || qw + 31 - a.wl > kv0 || qw + a.wr < kv0 + TK - 1) {
                     int lo, cnt;
                     win_lim(a, len, qw, kv0, xl, lo, cnt);
+                    f_qk_sm<BF, 3, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl, cnt, lo);
+                } else f_qk_sm<BF, 0, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
+                f_pv<BF, DB>(cur + TILE, vo, pf, o);
+            }
+        } else if constexpr (DOC) {
+            // (wave-uniform) skip a tile that lies wholly outside the keys of the wave's rows; the masked body (the window variant's:
+            // an interval per lane) unless every row sees all 64 keys - a tile the length cuts has hi_first <= len < kv0 + 64
+            if (active && kv0 + TK > dr.lo_first && kv0 < dr.hi_last) {
+                if (dr.lo_last > kv0 || dr.hi_first < kv0 + TK) {
+                    int lo, cnt;
+                    doc_lim(dr.lo, dr.hi, kv0, lo, cnt);
                     f_qk_sm<BF, 3, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl, cnt, lo);
                 } else f_qk_sm<BF, 0, D>(cur, qf, ko, o, pf, m_i, l_i, c, kv0, len, hl);
                 f_pv<BF, DB>(cur + TILE, vo, pf, o);
@@ -613,7 +686,7 @@ constexpr int DQ_LDS = 2 * SLOT + 4 * QSLAB;  // two K | V slots + four dO slabs
 template <bool BF, int D, int MODE>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) {
     using frag_t = typename AFrag<BF>::type;
-    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW;
+    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW, DOC = MODE == M_DOC;
     constexpr int KS = D / 16, DB = D / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
@@ -621,8 +694,8 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) 
     const int64_t bh = blockIdx.x / nxb, xb = block_of<MODE>(blockIdx.x % nxb, bh, nxb), b = bh / a.H, h = bh % a.H, g = h / a.G;
     const int64_t len = key_len(a, b);
     const int64_t pre = CAUSAL ? prefix_of(a, b) : 0;
-    const int nt = (int)((key_bound<MODE>(a, len, pre, xb) + TK - 1) / TK);
-    const int tf = first_tile<MODE>(a, xb); // 0 but under a window; there nt <= tf when no query of the block sees a key
+    const int nt = DOC ? doc_last_tile(a, b, len, xb) : (int)((key_bound<MODE>(a, len, pre, xb) + TK - 1) / TK);
+    const int tf = DOC ? doc_first_tile(a, b, len, xb) : first_tile<MODE>(a, xb); // 0 but under a window or a document mask; there nt <= tf when no query of the block sees a key
     const char *Kg = a.k + b * a.lk.sb + g * a.lk.sh;
     const char *Vg = a.v + b * a.lv.sb + g * a.lv.sh;
     char *doslab = smem + 2 * SLOT + wid * QSLAB; // this wave's dO rows, same swizzled image as a K tile (B operand of dP^T)
@@ -637,6 +710,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) 
     const float c = a.scale * kLog2e;
     const int64_t qw = xb * TQ + wid * 32, m = qw + xl;
     const bool active = qw < a.Sq;
+    const DocRows dr = doc_rows<DOC>(a, b, len, qw, m, active);
 
     frag_t qf[KS];
 #pragma unroll
@@ -689,6 +763,14 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_kernel(const FullArgs a) 
                 if (kv0 + TK > len || qw + 31 - a.wl > kv0 || qw + a.wr < kv0 + TK - 1) {
                     int lo, cnt;
                     win_lim(a, len, qw, kv0, xl, lo, cnt);
+                    q_tile<BF, 3, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl, cnt, lo);
+                } else q_tile<BF, 0, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
+            }
+        } else if constexpr (DOC) { // the forward's skip and body choice; a row with lse = -inf sees no key, so it never meets the unmasked body
+            if (active && kv0 + TK > dr.lo_first && kv0 < dr.hi_last) {
+                if (dr.lo_last > kv0 || dr.hi_first < kv0 + TK) {
+                    int lo, cnt;
+                    doc_lim(dr.lo, dr.hi, kv0, lo, cnt);
                     q_tile<BF, 3, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl, cnt, lo);
                 } else q_tile<BF, 0, D>(cur, doslab, qf, ko, vo, dq, c, lse2, dlt, kv0, len, hl);
             }
@@ -779,7 +861,7 @@ __device__ __forceinline__ void kv_tile(const char *buf, const typename AFrag<BF
 template <bool BF, int D, int MODE>
 __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a) {
     using frag_t = typename AFrag<BF>::type;
-    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW;
+    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW, DOC = MODE == M_DOC;
     constexpr int KS = D / 16, DB = D / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, xl = lane & 31, hl = lane >> 5;
@@ -796,9 +878,18 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a)
     // window variant: the keys k0 .. k0 + 127 are seen by the queries k0 - wr .. k0 + 127 + wl: query tiles t0 .. tl, none when tl < t0
     const int64_t wlo = k0 - a.wr, whi = k0 + TQ - 1 + a.wl; // (read under WIN only)
     const int64_t tl = (whi < a.Sq - 1 ? whi : a.Sq - 1) / TK;
-    const int64_t t0 = WIN ? (wlo > 0 ? wlo / TK : 0) : (CAUSAL && k0 >= pre ? k0 / TK : 0);
-    const int64_t nq = WIN ? tl - t0 + 1 : nqt - t0; // query tiles per head
-    if (k0 >= len || ((CAUSAL || WIN) && nq <= 0)) { // (workgroup-uniform) a key block beyond the batch's length, or unseen: its dK and dV rows are zeros
+    // document variant: the keys k0 .. min(k0 + 128, len) - 1 are seen by the queries from the first one of key k0 to the last one of the
+    // last of them (both columns are nondecreasing): query tiles dlo / 64 .. (dhi - 1) / 64, none when the interval is empty
+    int dlo = 0, dhi = 0;
+    if constexpr (DOC) {
+        if (k0 < len) {
+            dlo = doc_qlo(a, b, k0);
+            dhi = doc_qhi(a, b, (k0 + TQ < len ? k0 + TQ : len) - 1);
+        }
+    }
+    const int64_t t0 = DOC ? dlo / TK : (WIN ? (wlo > 0 ? wlo / TK : 0) : (CAUSAL && k0 >= pre ? k0 / TK : 0));
+    const int64_t nq = DOC ? (dhi > dlo ? (dhi - 1) / TK - t0 + 1 : 0) : (WIN ? tl - t0 + 1 : nqt - t0); // query tiles per head
+    if (k0 >= len || ((CAUSAL || WIN || DOC) && nq <= 0)) { // (workgroup-uniform) a key block beyond the batch's length, or unseen: its dK and dV rows are zeros
         const int64_t rows = a.Skv - k0 < TQ ? a.Skv - k0 : TQ;
         for (int id = threadIdx.x; id < rows * (D / 8); id += NT) {
             const int row = id / (D / 8), ch = id % (D / 8);
@@ -819,6 +910,22 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a)
     const bool dead = n >= len;        // this lane's key does not exist
     const bool work = kw < len;        // wave-uniform: the wave has a visible key
     const bool ragged = kw + 32 > len; // wave-uniform: some lane's key is beyond len
+    // document variant: the queries that see the lane's own key (none when it is dead) and, wave-uniform, those of the wave's first key
+    // and of its last key below len
+    int qlo = 0, qhi = 0, qlo_first = 0, qlo_last = 0, qhi_first = 0, qhi_last = 0;
+    if constexpr (DOC) {
+        if (!dead) {
+            qlo = doc_qlo(a, b, n);
+            qhi = doc_qhi(a, b, n);
+        }
+        if (work) {
+            const int64_t last = (kw + 32 < len ? kw + 32 : len) - 1;
+            qlo_first = __builtin_amdgcn_readfirstlane(doc_qlo(a, b, kw));
+            qlo_last = __builtin_amdgcn_readfirstlane(doc_qlo(a, b, last));
+            qhi_first = __builtin_amdgcn_readfirstlane(doc_qhi(a, b, kw));
+            qhi_last = __builtin_amdgcn_readfirstlane(doc_qhi(a, b, last));
+        }
+    }
 
     frag_t kf[KS], vf[KS];
 #pragma unroll
@@ -879,6 +986,16 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_kernel(const FullArgs a)
                     kv_tile<BF, 3, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl, lo, dead ? 0 : max(hi - lo, 0));
                 } else kv_tile<BF, 0, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
             }
+        } else if constexpr (DOC) {
+            // (wave-uniform) the window variant's skip and body choice with the table's intervals: skip a tile none of the wave's keys is
+            // seen from; the unmasked body only where every key of the wave exists and is seen by all 64 queries (whose lse is finite then)
+            if (work && q0 + TK > qlo_first && q0 < qhi_last) {
+                if (ragged || qlo_last > q0 || qhi_first < q0 + TK) {
+                    int lo, cnt;
+                    doc_lim(qlo, qhi, q0, lo, cnt);
+                    kv_tile<BF, 3, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl, lo, cnt);
+                } else kv_tile<BF, 0, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
+            }
         } else if (work) {
             if (ragged) kv_tile<BF, 1, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
             else kv_tile<BF, 0, D>(cur, kf, vf, ko, vo, dk, dv, c, dead, hl);
@@ -914,16 +1031,19 @@ __device__ __forceinline__ float g_block_reduce(float v, float *red) { // every 
 // on the query in dK/dV
 // WIN (window variant): the keys max(0, m - wl) <= n < min(len, m + wr + 1) - a first key besides the bound in the forward and dQ (an
 // empty interval leaves o = 0, lse = -inf and dq = 0), the predicate n - wr <= m <= n + wl in dK/dV
+// DOC (document variant): the same with the interval read from the table - doc_lo .. doc_hi of the query, doc_qlo .. doc_qhi of the key
 template <int MODE>
 __device__ __forceinline__ int64_t g_key_bound(const FullArgs &a, int64_t b, int64_t m) {
     const int64_t len = key_len(a, b);
     if constexpr (MODE == M_FULL) return len;
     if constexpr (MODE == M_WINDOW) return len < m + a.wr + 1 ? len : m + a.wr + 1;
+    if constexpr (MODE == M_DOC) return doc_hi(a, b, m, len);
     const int64_t pre = prefix_of(a, b), vis = pre > m + 1 ? pre : m + 1;
     return len < vis ? len : vis;
 }
 template <int MODE>
-__device__ __forceinline__ int64_t g_key_first(const FullArgs &a, int64_t m) {
+__device__ __forceinline__ int64_t g_key_first(const FullArgs &a, int64_t b, int64_t m) {
+    if constexpr (MODE == M_DOC) return doc_lo(a, b, m, key_len(a, b));
     if constexpr (MODE != M_WINDOW) return 0;
     return m > a.wl ? m - a.wl : 0;
 }
@@ -940,7 +1060,7 @@ __global__ __launch_bounds__(NT) void attn_full_fwd_generic_kernel(const FullArg
     if (tid < D) qs[tid] = load_f32(Q + tid);
     __syncthreads();
     float acc = 0.f, mrun = -INFINITY, lrun = 0.f;
-    for (int64_t c0 = g_key_first<MODE>(a, m); c0 < len; c0 += NT) {
+    for (int64_t c0 = g_key_first<MODE>(a, b, m); c0 < len; c0 += NT) {
         const int64_t n = c0 + tid;
         float s = -INFINITY;
         if (n < len) {
@@ -989,7 +1109,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dq_generic_kernel(const Full
     const float lse = a.lse_r[bh * a.Sq + m], dlt = a.delta[bh * a.Sq + m];
     __syncthreads();
     float acc = 0.f;
-    for (int64_t c0 = g_key_first<MODE>(a, m); c0 < len; c0 += NT) {
+    for (int64_t c0 = g_key_first<MODE>(a, b, m); c0 < len; c0 += NT) {
         const int64_t n = c0 + tid;
         float ds = 0.f;
         if (n < len) {
@@ -1027,8 +1147,13 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
         vs[tid] = load_f32((const T *)a.v + (bg * a.Skv + n) * D + tid);
     }
     __syncthreads();
-    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW;
+    constexpr bool CAUSAL = MODE == M_PREFIX, WIN = MODE == M_WINDOW, DOC = MODE == M_DOC;
     const bool in_prefix = !CAUSAL || n < prefix_of(a, b); // else only queries m >= n see this key
+    int64_t dlo = 0, dhi = 0; // document variant: the queries dlo <= m < dhi see this key
+    if constexpr (DOC) {
+        dlo = doc_qlo(a, b, n);
+        dhi = doc_qhi(a, b, n);
+    }
     float ak = 0.f, av = 0.f;
     for (int hh = 0; hh < a.G; ++hh) {
         const int64_t bh = b * a.H + g * a.G + hh;
@@ -1036,7 +1161,7 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
         for (int64_t c0 = 0; c0 < a.Sq; c0 += NT) {
             const int64_t m = c0 + tid;
             float p = 0.f, ds = 0.f;
-            if (m < a.Sq && (in_prefix || m >= n) && (!WIN || (m >= n - a.wr && m <= n + a.wl))) {
+            if (m < a.Sq && (in_prefix || m >= n) && (!WIN || (m >= n - a.wr && m <= n + a.wl)) && (!DOC || (m >= dlo && m < dhi))) {
                 float dot = 0.f, dp = 0.f;
                 for (int d = 0; d < D; ++d) {
                     dot += ks[d] * load_f32(Q + m * D + d);
@@ -1059,6 +1184,39 @@ __global__ __launch_bounds__(NT) void attn_full_bwd_dkv_generic_kernel(const Ful
         }
     }
     if (tid < D) { store_canonical(dK + tid, ak * a.scale); store_canonical(dV + tid, av); }
+}
+
+// ==========================================================================================
+// document table (kf_attn_doc_table): one thread per token, a binary search over its row's cumulative lengths
+// ==========================================================================================
+// c_j = clamp(cu[b, j], 0, S), c_0 = 0 whatever it holds; token m < c_n belongs to the LAST document j with c_j <= m (a zero-length
+// document owns nothing). The search keeps c_lo <= m < c_hi, so whatever the row holds the pair written has 0 <= start <= end <= S.
+__global__ __launch_bounds__(NT) void attn_doc_table_kernel(const int64_t *cu, int64_t B, int64_t S, int64_t n_docs, int64_t *kv_len, int32_t *doc_start,
+                                                            int32_t *doc_end) {
+    const int64_t idx = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (idx >= B * S) return;
+    const int64_t b = idx / S, m = idx - b * S;
+    const int64_t *row = cu + b * (n_docs + 1);
+    auto c = [&](int64_t j) -> int64_t {
+        if (j == 0) return 0;
+        const int64_t x = row[j];
+        return x < 0 ? 0 : (x > S ? S : x);
+    };
+    const int64_t len = c(n_docs);
+    if (m == 0) kv_len[b] = len;
+    int64_t s = len, e = len;
+    if (m < len) {
+        int64_t lo = 0, hi = n_docs;
+        while (hi - lo > 1) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (c(mid) <= m) lo = mid;
+            else hi = mid;
+        }
+        s = c(lo);
+        e = c(hi);
+    }
+    doc_start[idx] = (int32_t)s;
+    doc_end[idx] = (int32_t)e;
 }
 
 // ==========================================================================================
@@ -1131,36 +1289,53 @@ static int full_check(const char *who, int dtype, int64_t B, int64_t Hq, int64_t
 using namespace kf;
 using namespace kf::full;
 
-// The three families share their host path. `mode` selects the instantiations and labels: M_PREFIX the prefix-LM ones
-// (kf_attn_prefix_*), M_WINDOW the window ones (kf_attn_window_*; prefix_len carries nothing, the window is in `win`); with M_FULL
-// prefix_len is not read and the launches are kf_attn_full_*'s own.
+// The four families share their host path. `mode` selects the instantiations and labels: M_PREFIX the prefix-LM ones
+// (kf_attn_prefix_*), M_WINDOW the window ones (kf_attn_window_*; prefix_len carries nothing, the window is in `win`), M_DOC the
+// document ones (kf_attn_doc_*; the tables and the causal flag are in `doc`); with M_FULL prefix_len is not read and the launches are
+// kf_attn_full_*'s own.
 template <typename F> static inline int with_mode(Mode mode, F &&f) {
     return mode == M_FULL ? f(std::integral_constant<int, M_FULL>{})
-                          : mode == M_PREFIX ? f(std::integral_constant<int, M_PREFIX>{}) : f(std::integral_constant<int, M_WINDOW>{});
+                          : mode == M_PREFIX ? f(std::integral_constant<int, M_PREFIX>{})
+                                             : mode == M_WINDOW ? f(std::integral_constant<int, M_WINDOW>{}) : f(std::integral_constant<int, M_DOC>{});
 }
 struct Window { int64_t left, right; };
-static const char *const kFwdLabel[3][2] = {{"attn_full_fwd_mfma_d128", "attn_full_fwd_mfma_d64"},
+struct DocTables { const int32_t *start, *end; int causal; }; // the document variant's tables ([B, S] on the device) and its causal flag
+static const char *const kFwdLabel[4][2] = {{"attn_full_fwd_mfma_d128", "attn_full_fwd_mfma_d64"},
                                             {"attn_prefix_fwd_mfma_d128", "attn_prefix_fwd_mfma_d64"},
-                                            {"attn_window_fwd_mfma_d128", "attn_window_fwd_mfma_d64"}};
-static const char *const kDqLabel[3][2] = {{"attn_full_bwd_dq_mfma_d128", "attn_full_bwd_dq_mfma_d64"},
+                                            {"attn_window_fwd_mfma_d128", "attn_window_fwd_mfma_d64"},
+                                            {"attn_doc_fwd_mfma_d128", "attn_doc_fwd_mfma_d64"}};
+static const char *const kDqLabel[4][2] = {{"attn_full_bwd_dq_mfma_d128", "attn_full_bwd_dq_mfma_d64"},
                                            {"attn_prefix_bwd_dq_mfma_d128", "attn_prefix_bwd_dq_mfma_d64"},
-                                           {"attn_window_bwd_dq_mfma_d128", "attn_window_bwd_dq_mfma_d64"}};
-static const char *const kDkvLabel[3][2] = {{"attn_full_bwd_dkv_mfma_d128", "attn_full_bwd_dkv_mfma_d64"},
+                                           {"attn_window_bwd_dq_mfma_d128", "attn_window_bwd_dq_mfma_d64"},
+                                           {"attn_doc_bwd_dq_mfma_d128", "attn_doc_bwd_dq_mfma_d64"}};
+static const char *const kDkvLabel[4][2] = {{"attn_full_bwd_dkv_mfma_d128", "attn_full_bwd_dkv_mfma_d64"},
                                             {"attn_prefix_bwd_dkv_mfma_d128", "attn_prefix_bwd_dkv_mfma_d64"},
-                                            {"attn_window_bwd_dkv_mfma_d128", "attn_window_bwd_dkv_mfma_d64"}};
-static const char *const kGenericLabel[3][3] = {{"attn_full_fwd_generic", "attn_full_bwd_dq_generic", "attn_full_bwd_dkv_generic"},
+                                            {"attn_window_bwd_dkv_mfma_d128", "attn_window_bwd_dkv_mfma_d64"},
+                                            {"attn_doc_bwd_dkv_mfma_d128", "attn_doc_bwd_dkv_mfma_d64"}};
+static const char *const kGenericLabel[4][3] = {{"attn_full_fwd_generic", "attn_full_bwd_dq_generic", "attn_full_bwd_dkv_generic"},
                                                 {"attn_prefix_fwd_generic", "attn_prefix_bwd_dq_generic", "attn_prefix_bwd_dkv_generic"},
-                                                {"attn_window_fwd_generic", "attn_window_bwd_dq_generic", "attn_window_bwd_dkv_generic"}};
+                                                {"attn_window_fwd_generic", "attn_window_bwd_dq_generic", "attn_window_bwd_dkv_generic"},
+                                                {"attn_doc_fwd_generic", "attn_doc_bwd_dq_generic", "attn_doc_bwd_dkv_generic"}};
 // the window as the kernels carry it: an unbounded side, or one wider than any extent, is kNoEdge
 static void set_window(FullArgs &a, Mode mode, Window win) {
     if (mode != M_WINDOW) return;
     a.wl = win.left < 0 || win.left > kNoEdge ? kNoEdge : win.left;
     a.wr = win.right < 0 || win.right > kNoEdge ? kNoEdge : win.right;
 }
+// the document variant's tables: required once there is something to launch (as the operands are), and 32-bit, so S stays below 2^31
+static int set_doc(const char *who, FullArgs &a, Mode mode, const DocTables &doc) {
+    if (mode != M_DOC) return KF_OK;
+    KF_REQUIRE(doc.start && doc.end, KF_ERR_INVALID, "%s: null doc_start or doc_end (kf_attn_doc_table writes them)", who);
+    KF_REQUIRE(a.Sq < (1ll << 31), KF_ERR_UNSUPPORTED, "%s: the document tables are 32-bit, S must be below 2^31", who);
+    a.doc_start = doc.start;
+    a.doc_end = doc.end;
+    a.causal = doc.causal;
+    return KF_OK;
+}
 
 static int full_fwd(const char *who, Mode mode, Window win, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
                     const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
-                    const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+                    const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream, DocTables doc = DocTables{nullptr, nullptr, 0}) {
     const void *ops[4] = {q, k, v, o};
     const kf_attn_layout *lay[4] = {lq, lk, lv, lo};
     FullArgs a;
@@ -1170,6 +1345,8 @@ static int full_fwd(const char *who, Mode mode, Window win, int dtype, int64_t B
     a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.out = (char *)o; a.lse = lse; a.kv_len = kv_len;
     a.prefix_len = mode == M_PREFIX ? prefix_len : nullptr;
     set_window(a, mode, win);
+    rc = set_doc(who, a, mode, doc);
+    if (rc != KF_OK) return rc;
     hipStream_t st = as_stream(stream);
     const bool bf = dtype == KF_BF16, d64 = D == 64;
     if (plan == PLAN_MFMA) {
@@ -1189,7 +1366,7 @@ static int full_bwd(const char *who, Mode mode, Window win, int dtype, int64_t B
                     const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
                     const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
                     const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
-                    const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream) {
+                    const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream, DocTables doc = DocTables{nullptr, nullptr, 0}) {
     const void *ops[8] = {q, k, v, o, d_o, dq, dk, dv};
     const kf_attn_layout *lay[8] = {lq, lk, lv, lo, ldo, ldq, ldk, ldv};
     FullArgs a;
@@ -1205,6 +1382,8 @@ static int full_bwd(const char *who, Mode mode, Window win, int dtype, int64_t B
     a.lse_r = lse; a.delta = (float *)workspace; a.kv_len = kv_len;
     a.prefix_len = mode == M_PREFIX ? prefix_len : nullptr;
     set_window(a, mode, win);
+    rc = set_doc(who, a, mode, doc);
+    if (rc != KF_OK) return rc;
     hipStream_t st = as_stream(stream);
     const bool bf = dtype == KF_BF16, d64 = D == 64;
     const int64_t nrows = B * Hq * Sq;
@@ -1307,4 +1486,36 @@ extern "C" int kf_attn_window_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv,
                (long long)window_left, (long long)window_right);
     return full_bwd("kf_attn_window_bwd", window_mode(window_left, window_right), Window{window_left, window_right}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len,
                     nullptr, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq, dk, ldk, dv, ldv, workspace, workspace_bytes, stream);
+}
+
+// ---- the document variant: several sequences packed end to end in one row (kf_attn_doc_*) ----
+extern "C" int kf_attn_doc_table(int64_t B, int64_t S, int64_t n_docs, const int64_t *cu_doclens, int64_t *kv_len, int32_t *doc_start, int32_t *doc_end,
+                                 void *stream) {
+    KF_REQUIRE(B >= 0 && S >= 0, KF_ERR_INVALID, "kf_attn_doc_table: negative extent");
+    KF_REQUIRE(n_docs >= 1, KF_ERR_INVALID, "kf_attn_doc_table: n_docs %lld must be at least 1", (long long)n_docs);
+    KF_REQUIRE(cu_doclens && kv_len && doc_start && doc_end, KF_ERR_INVALID, "kf_attn_doc_table: null pointer");
+    if (B == 0 || S == 0) return KF_OK;
+    KF_REQUIRE(S < (1ll << 31) && (B * S + NT - 1) / NT < (1ll << 31) && B <= (1ll << 31), KF_ERR_UNSUPPORTED,
+               "kf_attn_doc_table: the tables are 32-bit and the grid holds 2^31 workgroups: S must be below 2^31 and B S below 2^39");
+    hipStream_t st = as_stream(stream);
+    KF_PROF("attn_doc_table", st);
+    return launch(attn_doc_table_kernel, (unsigned)((B * S + NT - 1) / NT), NT, 0, st, cu_doclens, B, S, n_docs, kv_len, doc_start, doc_end);
+}
+
+extern "C" int kf_attn_doc_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D, float scale, int causal, const int64_t *kv_len,
+                               const int32_t *doc_start, const int32_t *doc_end, const void *q, const kf_attn_layout *lq, const void *k,
+                               const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
+    KF_REQUIRE(causal == 0 || causal == 1, KF_ERR_INVALID, "kf_attn_doc_fwd: causal is 0 or 1, not %d", causal);
+    return full_fwd("kf_attn_doc_fwd", M_DOC, Window{-1, -1}, dtype, B, Hq, Hkv, S, S, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, stream,
+                    DocTables{doc_start, doc_end, causal});
+}
+
+extern "C" int kf_attn_doc_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D, float scale, int causal, const int64_t *kv_len,
+                               const int32_t *doc_start, const int32_t *doc_end, const void *q, const kf_attn_layout *lq, const void *k,
+                               const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse,
+                               const void *d_o, const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
+                               const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream) {
+    KF_REQUIRE(causal == 0 || causal == 1, KF_ERR_INVALID, "kf_attn_doc_bwd: causal is 0 or 1, not %d", causal);
+    return full_bwd("kf_attn_doc_bwd", M_DOC, Window{-1, -1}, dtype, B, Hq, Hkv, S, S, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq,
+                    dk, ldk, dv, ldv, workspace, workspace_bytes, stream, DocTables{doc_start, doc_end, causal});
 }

@@ -56,7 +56,7 @@ EXPORTS = [
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
     "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa",
-    "kf_attn_full_fwd", "kf_attn_full_bwd_workspace_bytes", "kf_attn_full_bwd", "kf_attn_prefix_fwd", "kf_attn_prefix_bwd", "kf_attn_window_fwd", "kf_attn_window_bwd", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
+    "kf_attn_full_fwd", "kf_attn_full_bwd_workspace_bytes", "kf_attn_full_bwd", "kf_attn_prefix_fwd", "kf_attn_prefix_bwd", "kf_attn_window_fwd", "kf_attn_window_bwd", "kf_attn_doc_table", "kf_attn_doc_fwd", "kf_attn_doc_bwd", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
 ]
 
 
@@ -203,6 +203,10 @@ def lib():
         _lib.kf_attn_window_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, i64, i64, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
         _lib.kf_attn_window_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, i64, i64, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp,
                                             vp, lp, vp, lp, vp, lp, vp, sz, vp]
+        _lib.kf_attn_doc_table.argtypes = [i64, i64, i64, vp, vp, vp, vp, vp]
+        _lib.kf_attn_doc_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, C.c_int, vp, vp, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
+        _lib.kf_attn_doc_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, C.c_int, vp, vp, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp,
+                                         vp, lp, vp, lp, vp, lp, vp, sz, vp]
         _lib.kf_rope.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, vp, vp, lp, vp, lp, vp]
         _lib.kf_rope_table.argtypes = [C.c_double, i64, i64, vp, vp, vp]
         _lib.kf_glu_fwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp]
@@ -704,6 +708,31 @@ def attn_window_bwd(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, k, v, o, lse, d_o, 
     L = _gqa_layouts(layouts, 8)
     check(lib().kf_attn_window_bwd(dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, window_left, window_right, q, L[0], k, L[1], v, L[2], o, L[3], lse,
                                    d_o, L[4], dq, L[5], dk, L[6], dv, L[7], workspace, workspace_bytes, stream))
+
+
+def attn_doc_table(B, S, n_docs, cu_doclens, kv_len, doc_start, doc_end, stream=None):
+    """The per-token tables of document-masked attention (kf_attn_doc_table). cu_doclens: device pointer to int64 [B, n_docs + 1], the
+    cumulative document lengths of each row; written: kv_len int64 [B], doc_start and doc_end int32 [B, S] (device pointers)."""
+    check(lib().kf_attn_doc_table(B, S, n_docs, cu_doclens, kv_len, doc_start, doc_end, stream))
+
+
+def attn_doc_fwd(dtype, B, Hq, Hkv, S, D, scale, q, k, v, o, lse=None, kv_len=None, doc_start=None, doc_end=None, causal=False, layouts=None,
+                 stream=None):
+    """Document-masked attention forward (kf_attn_doc_fwd) of a packed row, Sq = Skv = S: query m sees key n iff n < kv_len[b],
+    doc_start[b, m] <= n < doc_end[b, m] and (not causal or n <= m). doc_start, doc_end: device pointers to int32 [B, S]
+    (attn_doc_table writes them; required); kv_len: device pointer to int64 [B], or None; layouts as attn_full_fwd."""
+    L = _gqa_layouts(layouts, 4)
+    check(lib().kf_attn_doc_fwd(dtype, B, Hq, Hkv, S, D, scale, int(causal), kv_len, doc_start, doc_end, q, L[0], k, L[1], v, L[2], o, L[3], lse,
+                                stream))
+
+
+def attn_doc_bwd(dtype, B, Hq, Hkv, S, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, workspace, workspace_bytes, kv_len=None, doc_start=None,
+                 doc_end=None, causal=False, layouts=None, stream=None):
+    """Document-masked attention backward (kf_attn_doc_bwd). The workspace is attn_full_bwd_workspace_bytes(dtype, B, Hq, Hkv, S, S, D);
+    layouts as attn_full_bwd."""
+    L = _gqa_layouts(layouts, 8)
+    check(lib().kf_attn_doc_bwd(dtype, B, Hq, Hkv, S, D, scale, int(causal), kv_len, doc_start, doc_end, q, L[0], k, L[1], v, L[2], o, L[3], lse,
+                                d_o, L[4], dq, L[5], dk, L[6], dv, L[7], workspace, workspace_bytes, stream))
 
 
 def rope(dtype, B, H, S, D, x, lx, y=None, ly=None, cos=None, sin=None, table_rows=None, rotary_dim=None, h_rot=None, positions=None,
