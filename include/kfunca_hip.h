@@ -777,6 +777,43 @@ int kf_qk_norm_rope_bwd(int dtype, int64_t B, int64_t S, int64_t Hq, int64_t Hk,
                         int64_t table_rows, const int64_t *positions, const void *x, int64_t ldx, const void *dy, int64_t lddy,
                         void *dx, int64_t lddx, void *dwq, void *dwk, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- segmented (expert) GEMM with device-side offsets (no reference counterpart: the expert product of a mixture-of-experts layer -
+ *      Mixtral, Qwen3-MoE, DeepSeek-V3 - and both of its backward products; the routing is softmax, topk, sort and embedding) ---- */
+/*
+ * offsets: int64 [E + 1] in DEVICE memory, E >= 1: expert e owns the rows offsets[e] <= r < offsets[e + 1] of operands whose rows are
+ * sorted by expert. No entry reads them back: nothing synchronises, allocates or uses atomics, every output element is written by exactly
+ * one workgroup and every sum runs in an order that depends on the arguments only, so results are bitwise reproducible and calls can be
+ * captured with kf_graph_*. The kernels sanitise the offsets themselves: o'_0 = clamp(o_0, 0, T), o'_e = clamp(max(o_e, o'_(e-1)), 0, T);
+ * malformed offsets change which rows belong to whom, never what memory is touched.
+ *     segment_offsets   offsets[e] = the number of ids < e for e = 0 .. E: a lower bound over ASCENDING ids (one binary search per
+ *                       entry), so ids below 0 or at least E fall outside [offsets[0], offsets[E]). n == 0 gives zeros.
+ *     gemm_segmented    C[r, :] = alpha A[r, :] op(W_e) + beta C[r, :] for the rows of segment e. A is [T, K] with pitch lda, C is [T, N];
+ *                       W_e = W + e w_stride (elements) is stored [K, N] when trans_b == 0 and [N, K] when trans_b == 1 (the dX form),
+ *                       pitch ldw. A row that no segment covers gets beta C: +0 bit for bit when beta == 0 (a dropped token has a zero
+ *                       output and a zero gradient). beta == 0 never reads C.
+ *     wgrad             dW_e[M, N] = alpha A[seg_e, :]^T B[seg_e, :] + beta dW_e, A [T, M], B [T, N], dW_e = dW + e dw_stride with
+ *                       pitch lddw; an empty segment gives beta dW_e. Rows outside segment e never enter dW_e, not even as a factor of
+ *                       zero: a neighbour's Inf or NaN stays out.
+ * dtype is KF_BF16, KF_F16 or KF_F32 for every operand; the arithmetic is f32 with one rounding per output element. 16-bit operands
+ * with N % 128 == 0, the fixed contraction a multiple of 64 (wgrad: M % 128 == 0 and N % 128 == 0), pitches and strides multiples of 8
+ * and 16-byte aligned bases run on the matrix cores (128 x 128 x 64 tiles that never straddle a segment, LDS-DMA staging, a four-stage
+ * ring); anything else takes a plain kernel with the same semantics. Row offsets are 64-bit. The workspace
+ * (workspace_bytes(dtype, T, E): the sanitised offsets and a table of T / 128 + E + 2 row tiles, 16-byte aligned) needs no
+ * initialisation and is rewritten by every call. Every argument is checked before any device call: KF_ERR_INVALID for null pointers,
+ * negative extents, E < 1, a pitch below its extent, an expert stride below one expert's extent, a dtype outside the three, trans_b
+ * outside {0, 1}, a base not aligned to its element, a workspace that is missing, too small or misaligned. A zero T, N, K or M is
+ * KF_OK without a launch.
+ */
+int kf_segment_offsets(const int64_t *sorted_ids, int64_t n, int64_t E, int64_t *offsets /* [E+1] */, void *stream);
+int kf_gemm_segmented_workspace_bytes(int dtype, int64_t T, int64_t E, size_t *bytes);
+int kf_gemm_segmented(int dtype, int trans_b, int64_t T, int64_t N, int64_t K, int64_t E, const int64_t *offsets,
+                      float alpha, const void *A, int64_t lda, const void *W, int64_t ldw, int64_t w_stride,
+                      float beta, void *C, int64_t ldc, void *workspace, size_t workspace_bytes, void *stream);
+int kf_gemm_segmented_wgrad(int dtype, int64_t T, int64_t M, int64_t N, int64_t E, const int64_t *offsets,
+                            float alpha, const void *A, int64_t lda, const void *B, int64_t ldb,
+                            float beta, void *dW, int64_t lddw, int64_t dw_stride,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128
 int kf_comm_unique_id(char id[KF_COMM_ID_BYTES]);

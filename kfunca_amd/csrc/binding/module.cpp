@@ -13,6 +13,7 @@
 #include "attn_full.h"
 #include "comm.h"
 #include "device_api.h"
+#include "expert_linear.h"
 #include "glu.h"
 #include "softmax.h"
 #include "ops.h"
@@ -501,6 +502,20 @@ PYBIND11_MODULE(_C, m) {
     m.def("silu", [](const Tensor &x) { return gpu::activation(KF_ACT_SILU, x); }, py::arg("x"));
     m.def("gelu", [gelu_kind](const Tensor &x, const std::string &approximate) { return gpu::activation(gelu_kind(approximate), x); },
           py::arg("x"), py::arg("approximate") = "none");
+    // the expert product of a mixture-of-experts layer: row segments with device-side boundaries, each through its own weight
+    m.def("segment_offsets", &gpu::segment_offsets, py::arg("sorted_ids"), py::arg("num_experts"),
+          "segment_offsets(sorted_ids, num_experts): Long [num_experts + 1], offsets[e] = the number of the ascending Long ids that are < e, so "
+          "expert e owns the sorted rows offsets[e] .. offsets[e + 1]; ids below 0 or at least num_experts fall outside every segment. The "
+          "result stays on the device: nothing is read back. In an MoE layer sorted_ids are the keys of the stable sort of the flattened "
+          "topk expert ids, and the sort's positions are the permutation that expert_linear's rows follow.");
+    m.def("expert_linear", &gpu::expert_linear, py::arg("x"), py::arg("w"), py::arg("offsets"),
+          "expert_linear(x [T, Din], w [E, Din, Dout], offsets [E + 1]) -> [T, Dout]: y[r] = x[r] @ w[e] for offsets[e] <= r < offsets[e + 1], "
+          "float, half or bfloat16; a row no expert covers is zero and has a zero gradient. Differentiable in x and w (an empty expert's "
+          "gradient is zero); offsets (segment_offsets, on the device) gets no gradient. x may be row-pitched, w is contiguous. A layer is "
+          "composed from the existing operators: p = softmax(x @ router); gate, ids = p.topk(k); keys, pos = ids.view(-1).sort() (stable); "
+          "offsets = segment_offsets(keys, E); xs = embedding(x, pos // k) (the row gather, whose backward is the reproducible index-add); "
+          "h = expert_linear(xs, w_gate_up, offsets); a = swiglu(h); ys = expert_linear(a, w_down, offsets); y = sum over k of gate * "
+          "embedding(ys, inverse permutation).");
     // the distribution over a dimension (an MoE router, sampling, distillation): one launch each way, the backward from the kept result
     m.def("softmax", &gpu::softmax, py::arg("x"), py::arg("dim") = -1, py::arg("scale") = 1.0f,
           "softmax(x, dim=-1, scale=1.0): exp(scale * x) normalised to sum 1 over dimension dim of a float, half or bfloat16 tensor, in f32 "

@@ -53,6 +53,7 @@ EXPORTS = [
     "kf_glu_fwd", "kf_glu_bwd",
     "kf_softmax_fwd", "kf_softmax_bwd",
     "kf_qk_norm_rope_fwd", "kf_qk_norm_rope_bwd_workspace_bytes", "kf_qk_norm_rope_bwd",
+    "kf_segment_offsets", "kf_gemm_segmented_workspace_bytes", "kf_gemm_segmented", "kf_gemm_segmented_wgrad",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
     "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa",
@@ -218,6 +219,10 @@ def lib():
         _lib.kf_qk_norm_rope_bwd_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.POINTER(sz)]
         _lib.kf_qk_norm_rope_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, i64, C.c_int, C.c_double, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64,
                                              vp, i64, vp, vp, vp, sz, vp]
+        _lib.kf_segment_offsets.argtypes = [vp, i64, i64, vp, vp]
+        _lib.kf_gemm_segmented_workspace_bytes.argtypes = [C.c_int, i64, i64, C.POINTER(sz)]
+        _lib.kf_gemm_segmented.argtypes = [C.c_int, C.c_int, i64, i64, i64, i64, vp, C.c_float, vp, i64, vp, i64, i64, C.c_float, vp, i64, vp, sz, vp]
+        _lib.kf_gemm_segmented_wgrad.argtypes = [C.c_int, i64, i64, i64, i64, vp, C.c_float, vp, i64, vp, i64, C.c_float, vp, i64, i64, vp, sz, vp]
         _lib.kf_comm_unique_id.argtypes = [C.c_char_p]
         _lib.kf_comm_init.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int, C.c_int]
         _lib.kf_comm_destroy.argtypes = [vp]
@@ -808,6 +813,32 @@ def qk_norm_rope_bwd(dtype, B, S, Hq, Hk, Hv, D, x, ldx, dy, lddy, dx=None, lddx
     check(lib().kf_qk_norm_rope_bwd(dtype, B, S, Hq, Hk, Hv, D, rotary_dim, int(interleaved), float(eps), wq, wk, cos, sin, table_rows, positions,
                                     x, ldx, dy, lddy, dx, lddy if lddx is None else lddx, dwq, dwk, workspace, workspace_bytes or 0, stream))
     return own  # keep alive until the stream is synchronised
+
+
+def segment_offsets(sorted_ids, n, E, offsets, stream=None):
+    """kf_segment_offsets: offsets[e] = the number of the n ascending int64 ids that are < e, for e = 0 .. E (device pointers)."""
+    check(lib().kf_segment_offsets(sorted_ids, n, E, offsets, stream))
+
+
+def gemm_segmented_workspace_bytes(dtype, T, E) -> int:
+    """Bytes of scratch kf_gemm_segmented and kf_gemm_segmented_wgrad need (the sanitised offsets and the row-tile table); 16-byte
+    aligned, no initialisation."""
+    need = C.c_size_t(0)
+    check(lib().kf_gemm_segmented_workspace_bytes(dtype, T, E, C.byref(need)))
+    return need.value
+
+
+def gemm_segmented(dtype, trans_b, T, N, K, E, offsets, alpha, A, lda, W, ldw, w_stride, beta, Cp, ldc, workspace, workspace_bytes, stream=None):
+    """kf_gemm_segmented: C[r, :] = alpha A[r, :] op(W_e) + beta C[r, :] for offsets[e] <= r < offsets[e + 1]; W_e = W + e w_stride is
+    [K, N] (trans_b = 0) or [N, K] (trans_b = 1). offsets is a device pointer; rows no segment covers get beta C."""
+    check(lib().kf_gemm_segmented(dtype, int(trans_b), T, N, K, E, offsets, alpha, A, lda, W, ldw, w_stride, beta, Cp, ldc, workspace, workspace_bytes,
+                                  stream))
+
+
+def gemm_segmented_wgrad(dtype, T, M, N, E, offsets, alpha, A, lda, B, ldb, beta, dW, lddw, dw_stride, workspace, workspace_bytes, stream=None):
+    """kf_gemm_segmented_wgrad: dW_e = alpha A[seg_e, :]^T B[seg_e, :] + beta dW_e with A [T, M], B [T, N], dW_e = dW + e dw_stride."""
+    check(lib().kf_gemm_segmented_wgrad(dtype, T, M, N, E, offsets, alpha, A, lda, B, ldb, beta, dW, lddw, dw_stride, workspace, workspace_bytes,
+                                        stream))
 
 
 def device_sync():
