@@ -814,6 +814,69 @@ int kf_gemm_segmented_wgrad(int dtype, int64_t T, int64_t M, int64_t N, int64_t 
                             float beta, void *dW, int64_t lddw, int64_t dw_stride,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- mixture-of-experts token routing on the device (no reference counterpart: what surrounds the expert product above - the plan,
+ *      the gate, the dispatch and the weighted combine of Mixtral, Qwen3-MoE, DeepSeek-V3 - with both directions of each) ---- */
+/*
+ * T tokens choose k experts out of E each; n = T k, and pair p = t k + j is token t's j-th choice. ids: int64 [n] in DEVICE memory (the
+ * indices of a top-k). The plan sorts the pairs by expert once; everything else moves rows by its two 32-bit tables, so no backward
+ * sorts and no entry reads an extent back: nothing synchronises, allocates or uses atomics, every sum runs in a fixed order (bitwise
+ * reproducible), and calls can be captured with kf_graph_*. n >= 2^31 is KF_ERR_UNSUPPORTED (the tables are 32-bit).
+ *     plan          key_p = ids[p] if 0 <= ids[p] < E, else E: such a pair is DROPPED (kf_segment_offsets' rule for ids outside [0, E)).
+ *                   A stable ascending sort of the pairs by key (kf_sort): row_pair[r] (int32 [n]) = the pair in sorted row r,
+ *                   pair_row[p] (int32 [n]) = its inverse, offsets[e] (int64 [E + 1]) = the number of pairs with key < e, so
+ *                   offsets[0] = 0, offsets[E] = n_valid, and the dropped pairs fill the rows [n_valid, n) in pair order. offsets feeds
+ *                   kf_gemm_segmented unchanged. n == 0 still writes zero offsets. The workspace (kf_moe_plan_workspace_bytes: the keys,
+ *                   the sorted keys and positions and kf_sort's scratch; 16-byte aligned) needs no initialisation.
+ *     gate_fwd      s_j = p[t, ids[t, j]] (p: [T, E], pitch ldp), 0 for a dropped pair. gate[t, j] = s_j (normalize == 0) or s_j / S
+ *                   (normalize == 1), S = s_0 + ... + s_(k-1) summed in that order in f32; S = 0 gives what the formula gives.
+ *     gate_bwd      writes EVERY element of dp [T, E]: zeros, then dp[t, ids[t, j]] += ds_j in the order j (f32, rounded once), with
+ *                   ds_j = dgate_j (normalize == 0) or (dgate_j - sum_i dgate_i gate_i) / S (normalize == 1: S recomputed from p, gate the
+ *                   forward's stored result, the sum in the order i over the pairs that are not dropped). Dropped pairs contribute nothing.
+ *     dispatch      xs[r, :] = x[row_pair[r] / k, :] for r < n, bit for bit. A row_pair[r] outside [0, n) writes the row as +0 and reads
+ *                   nothing.
+ *     combine       y[t, :] = sum_j gate[t, j] ys[pair_row[t, j], :], accumulated in f32 from +0 in the order j = 0 .. k-1 (a product,
+ *                   then a sum), rounded once. gate == NULL means 1: the backward of dispatch, dx[t] = sum_j dxs[pair_row[t, j]]. n_valid
+ *                   is a DEVICE pointer to one int64 (pass offsets + E), read by the kernel and clamped to [0, n]; NULL means n. A pair
+ *                   whose pair_row lies outside [0, n_valid) is skipped: neither its row nor its gate is read (a NaN gate of a dropped
+ *                   pair stays out). A token with no live pair gets +0. The first 8 rows of a token are loaded together; pairs beyond 8
+ *                   are added one at a time.
+ *     combine_bwd   for every pair p = (t, j) with r = pair_row[p] in [0, n): dys[r, :] = gate[t, j] dy[t, :] for a live pair (one
+ *                   product, one rounding), dy[t, :] bit for bit when gate == NULL, +0 when r >= n_valid. dgate[t, j] = sum_c dy[t, c]
+ *                   ys[r, c] for a live pair, else +0: f32, in an order that depends on cols only, one rounding. dgate == NULL is
+ *                   allowed (the gate needs no gradient; ys may then be NULL too); gate == NULL requires dgate == NULL. One pass: dy[t] is
+ *                   read once per token for k <= 8 (once per 8 pairs beyond). With tables that are a permutation every row of dys is
+ *                   written exactly once. An entry outside [0, n) names no row.
+ * Every index a kernel reads is range-checked where it is read: malformed ids or tables change what is computed, never what memory is
+ * touched.
+ * No operand may alias another: an output must not overlap an input or another output (there is no in-place form; a combine writes
+ * y[t] while other workgroups still read ys). This is not checked.
+ * dtype is KF_F32, KF_BF16 or KF_F16 for every floating operand; the arithmetic is f32 with one rounding per output element. Rows have
+ * leading dimensions in elements (ld* >= the row's extent) and 64-bit row offsets; columns beyond the extent are never written. Bases
+ * need the alignment of an element only: with the row operands 16-byte aligned and cols and their leading dimensions multiples of
+ * 16 / sizeof(element) a call moves 16-byte packs, anything else takes the element path, where the same lanes own the same elements:
+ * the same bits. Regimes, from cols alone: cols <= 1024 one wave per row, longer rows one 256-thread block per row. Profile labels
+ * moe_plan, moe_gate_fwd, moe_gate_bwd, moe_dispatch, moe_combine, moe_combine_bwd.
+ * Every argument is checked before any device call, with the entry's name in kf_last_error(): KF_ERR_INVALID for null required pointers
+ * (with T == 0 the plan's ids and tables may be NULL), negative extents, k < 1, E < 1, a leading dimension below its extent, a dtype
+ * outside the three, normalize outside {0, 1}, a base not aligned to its element (ids, offsets and n_valid to 8 bytes, the tables to 4),
+ * a workspace that is missing, too small or not 16-byte aligned. T == 0, and cols == 0 where nothing is left to write, is KF_OK without
+ * a launch.
+ */
+int kf_moe_plan_workspace_bytes(int64_t T, int64_t k, int64_t E, size_t *bytes);
+int kf_moe_plan(const int64_t *ids, int64_t T, int64_t k, int64_t E, int64_t *offsets /* [E+1] */, int32_t *row_pair /* [T k] */,
+                int32_t *pair_row /* [T k] */, void *workspace, size_t workspace_bytes, void *stream);
+int kf_moe_gate_fwd(int dtype, int64_t T, int64_t k, int64_t E, const int64_t *ids, const void *p, int64_t ldp, int normalize,
+                    void *gate, int64_t ldg, void *stream);
+int kf_moe_gate_bwd(int dtype, int64_t T, int64_t k, int64_t E, const int64_t *ids, const void *p, int64_t ldp, int normalize,
+                    const void *gate, int64_t ldg, const void *dgate, int64_t lddg, void *dp, int64_t lddp, void *stream);
+int kf_moe_dispatch(int dtype, int64_t T, int64_t k, int64_t cols, const int32_t *row_pair, const void *x, int64_t ldx,
+                    void *xs, int64_t ldxs, void *stream);
+int kf_moe_combine(int dtype, int64_t T, int64_t k, int64_t cols, const int32_t *pair_row, const int64_t *n_valid,
+                   const void *gate, int64_t ldg, const void *ys, int64_t ldys, void *y, int64_t ldy, void *stream);
+int kf_moe_combine_bwd(int dtype, int64_t T, int64_t k, int64_t cols, const int32_t *pair_row, const int64_t *n_valid,
+                       const void *gate, int64_t ldg, const void *ys, int64_t ldys, const void *dy, int64_t lddy,
+                       void *dys, int64_t lddys, void *dgate, int64_t lddg, void *stream);
+
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128
 int kf_comm_unique_id(char id[KF_COMM_ID_BYTES]);

@@ -15,6 +15,7 @@
 #include "device_api.h"
 #include "expert_linear.h"
 #include "glu.h"
+#include "moe.h"
 #include "softmax.h"
 #include "ops.h"
 #include "optim.h"
@@ -516,6 +517,44 @@ PYBIND11_MODULE(_C, m) {
           "offsets = segment_offsets(keys, E); xs = embedding(x, pos // k) (the row gather, whose backward is the reproducible index-add); "
           "h = expert_linear(xs, w_gate_up, offsets); a = swiglu(h); ys = expert_linear(a, w_down, offsets); y = sum over k of gate * "
           "embedding(ys, inverse permutation).");
+    // the routing around the expert product, on the device: the plan (one sort), the gate, the dispatch and the weighted combine
+    py::class_<gpu::MoePlan>(m, "MoePlan", py::module_local(),
+                             "The routing of T tokens to k of E experts each (moe_plan(ids, num_experts)): offsets Long [E + 1] (what expert_linear takes; "
+                             "offsets[E] = the number of live pairs), row_pair Int [T k] (the pair t k + j in sorted row r), pair_row Int [T, k] (its inverse), "
+                             "ids, T, k, E. Built once per layer, used by that layer's forward and backward.")
+        .def_readonly("offsets", &gpu::MoePlan::offsets)
+        .def_readonly("row_pair", &gpu::MoePlan::row_pair)
+        .def_readonly("pair_row", &gpu::MoePlan::pair_row)
+        .def_readonly("ids", &gpu::MoePlan::ids)
+        .def_readonly("T", &gpu::MoePlan::T)
+        .def_readonly("k", &gpu::MoePlan::k)
+        .def_readonly("E", &gpu::MoePlan::E);
+    auto moe_plan_of = [](const char *op, const py::object &o) -> const gpu::MoePlan & {
+        if (!py::isinstance<gpu::MoePlan>(o)) throw py::value_error(std::string(op) + ": plan is a MoePlan (moe_plan(ids, num_experts))");
+        return o.cast<const gpu::MoePlan &>();
+    };
+    m.def("moe_plan", &gpu::moe_plan, py::arg("ids"), py::arg("num_experts"),
+          "moe_plan(ids, num_experts) -> MoePlan. ids: Long [T, k] on the device, e.g. p.topk(k, -1, True)[1]. A stable sort of the T k (token, "
+          "choice) pairs by expert id, on the device: nothing is read back, so the layer can be captured in a graph. An id outside "
+          "[0, num_experts) drops its pair: it sorts behind every expert, expert_linear gives its row zeros and moe_combine skips it. "
+          "plan.offsets feeds expert_linear unchanged.");
+    m.def("moe_gate", [moe_plan_of](const Tensor &p, const py::object &plan, bool normalize) { return gpu::moe_gate(p, moe_plan_of("moe_gate", plan), normalize); },
+          py::arg("p"), py::arg("plan"), py::arg("normalize") = false,
+          "moe_gate(p [T, E], plan, normalize=False) -> [T, k]: gate[t, j] = p[t, plan.ids[t, j]] (0 for a dropped pair); normalize=True divides "
+          "by their sum over j (f32, in the order j). float, half or bfloat16; p may be row-pitched. Differentiable in p: one launch that "
+          "writes all of dp, zero off the chosen columns.");
+    m.def("moe_dispatch", [moe_plan_of](const Tensor &x, const py::object &plan) { return gpu::moe_dispatch(x, moe_plan_of("moe_dispatch", plan)); },
+          py::arg("x"), py::arg("plan"),
+          "moe_dispatch(x [T, d], plan) -> xs [T k, d]: xs[r] = x[plan.row_pair[r] // k], the rows in expert order for expert_linear, bit for "
+          "bit. A row-pitched x is read in place. Differentiable in x: dx[t] = the f32 sum over j of dxs[plan.pair_row[t, j]], a gather-sum "
+          "(no sort, no atomics, bitwise reproducible).");
+    m.def("moe_combine", [moe_plan_of](const Tensor &ys, const py::object &plan, py::object gate) {
+        return gpu::moe_combine(ys, moe_plan_of("moe_combine", plan), gate.is_none() ? Tensor() : gate.cast<Tensor>());
+    }, py::arg("ys"), py::arg("plan"), py::arg("gate") = py::none(),
+          "moe_combine(ys [T k, d], plan, gate=None) -> y [T, d]: y[t] = sum over j of gate[t, j] * ys[plan.pair_row[t, j]], accumulated in "
+          "f32 in the order j and rounded once; gate [T, k] (moe_gate) or None (1). Dropped pairs are skipped: neither their row nor their "
+          "gate is read. Differentiable in ys and gate in one pass: dys[pair_row[t, j]] = gate[t, j] * dy[t] (zero for a dropped pair), "
+          "dgate[t, j] = dy[t] . ys[pair_row[t, j]].");
     // the distribution over a dimension (an MoE router, sampling, distillation): one launch each way, the backward from the kept result
     m.def("softmax", &gpu::softmax, py::arg("x"), py::arg("dim") = -1, py::arg("scale") = 1.0f,
           "softmax(x, dim=-1, scale=1.0): exp(scale * x) normalised to sum 1 over dimension dim of a float, half or bfloat16 tensor, in f32 "

@@ -54,6 +54,7 @@ EXPORTS = [
     "kf_softmax_fwd", "kf_softmax_bwd",
     "kf_qk_norm_rope_fwd", "kf_qk_norm_rope_bwd_workspace_bytes", "kf_qk_norm_rope_bwd",
     "kf_segment_offsets", "kf_gemm_segmented_workspace_bytes", "kf_gemm_segmented", "kf_gemm_segmented_wgrad",
+    "kf_moe_plan_workspace_bytes", "kf_moe_plan", "kf_moe_gate_fwd", "kf_moe_gate_bwd", "kf_moe_dispatch", "kf_moe_combine", "kf_moe_combine_bwd",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
     "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa",
@@ -223,6 +224,13 @@ def lib():
         _lib.kf_gemm_segmented_workspace_bytes.argtypes = [C.c_int, i64, i64, C.POINTER(sz)]
         _lib.kf_gemm_segmented.argtypes = [C.c_int, C.c_int, i64, i64, i64, i64, vp, C.c_float, vp, i64, vp, i64, i64, C.c_float, vp, i64, vp, sz, vp]
         _lib.kf_gemm_segmented_wgrad.argtypes = [C.c_int, i64, i64, i64, i64, vp, C.c_float, vp, i64, vp, i64, C.c_float, vp, i64, i64, vp, sz, vp]
+        _lib.kf_moe_plan_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
+        _lib.kf_moe_plan.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]
+        _lib.kf_moe_gate_fwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_int, vp, i64, vp]
+        _lib.kf_moe_gate_bwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_int, vp, i64, vp, i64, vp, i64, vp]
+        _lib.kf_moe_dispatch.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, vp, i64, vp]
+        _lib.kf_moe_combine.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp]
+        _lib.kf_moe_combine_bwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
         _lib.kf_comm_unique_id.argtypes = [C.c_char_p]
         _lib.kf_comm_init.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int, C.c_int]
         _lib.kf_comm_destroy.argtypes = [vp]
@@ -839,6 +847,47 @@ def gemm_segmented_wgrad(dtype, T, M, N, E, offsets, alpha, A, lda, B, ldb, beta
     """kf_gemm_segmented_wgrad: dW_e = alpha A[seg_e, :]^T B[seg_e, :] + beta dW_e with A [T, M], B [T, N], dW_e = dW + e dw_stride."""
     check(lib().kf_gemm_segmented_wgrad(dtype, T, M, N, E, offsets, alpha, A, lda, B, ldb, beta, dW, lddw, dw_stride, workspace, workspace_bytes,
                                         stream))
+
+
+def moe_plan_workspace_bytes(T, k, E) -> int:
+    """Bytes of scratch kf_moe_plan needs (the keys, the sorted keys, the positions and the sort's own scratch); 16-byte alignment is
+    the caller's."""
+    need = C.c_size_t(0)
+    check(lib().kf_moe_plan_workspace_bytes(T, k, E, C.byref(need)))
+    return need.value
+
+
+def moe_plan(ids, T, k, E, offsets, row_pair, pair_row, workspace, workspace_bytes, stream=None):
+    """kf_moe_plan: the stable sort of the T k (token, choice) pairs by expert id (int64 ids on the device; ids outside [0, E) are dropped
+    to the tail): row_pair int32 [T k], its inverse pair_row int32 [T k] and offsets int64 [E + 1] (device pointers)."""
+    check(lib().kf_moe_plan(ids, T, k, E, offsets, row_pair, pair_row, workspace, workspace_bytes, stream))
+
+
+def moe_gate_fwd(dtype, T, k, E, ids, p, ldp, normalize, gate, ldg, stream=None):
+    """kf_moe_gate_fwd: gate[t, j] = p[t, ids[t, j]] (0 for a dropped pair), divided by their sum over j when normalize."""
+    check(lib().kf_moe_gate_fwd(dtype, T, k, E, ids, p, ldp, int(normalize), gate, ldg, stream))
+
+
+def moe_gate_bwd(dtype, T, k, E, ids, p, ldp, normalize, gate, ldg, dgate, lddg, dp, lddp, stream=None):
+    """kf_moe_gate_bwd: dp [T, E] = zeros with dp[t, ids[t, j]] += ds_j in the order j; every element of dp is written."""
+    check(lib().kf_moe_gate_bwd(dtype, T, k, E, ids, p, ldp, int(normalize), gate, ldg, dgate, lddg, dp, lddp, stream))
+
+
+def moe_dispatch(dtype, T, k, cols, row_pair, x, ldx, xs, ldxs, stream=None):
+    """kf_moe_dispatch: xs[r, :] = x[row_pair[r] / k, :] for the T k sorted rows, bit for bit."""
+    check(lib().kf_moe_dispatch(dtype, T, k, cols, row_pair, x, ldx, xs, ldxs, stream))
+
+
+def moe_combine(dtype, T, k, cols, pair_row, n_valid, gate, ldg, ys, ldys, y, ldy, stream=None):
+    """kf_moe_combine: y[t, :] = sum_j gate[t, j] ys[pair_row[t, j], :] in f32 in the order j; gate None means 1, n_valid (a device pointer
+    to one int64, offsets + E) None means T k."""
+    check(lib().kf_moe_combine(dtype, T, k, cols, pair_row, n_valid, gate, ldg, ys, ldys, y, ldy, stream))
+
+
+def moe_combine_bwd(dtype, T, k, cols, pair_row, n_valid, gate, ldg, ys, ldys, dy, lddy, dys, lddys, dgate=None, lddg=0, stream=None):
+    """kf_moe_combine_bwd: dys[pair_row[t, j], :] = gate[t, j] dy[t, :] (+0 for a dropped pair) and dgate[t, j] = dy[t, :] . ys[row, :], in
+    one pass; dgate None skips the dot products (ys may then be None)."""
+    check(lib().kf_moe_combine_bwd(dtype, T, k, cols, pair_row, n_valid, gate, ldg, ys, ldys, dy, lddy, dys, lddys, dgate, lddg, stream))
 
 
 def device_sync():
