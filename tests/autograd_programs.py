@@ -15,7 +15,15 @@ that one program can be run in either type with the same bits. Two correct engin
 Tier "smooth": f32 leaves with uniform data, the exact tier's instructions (without dtype conversions) around ONE featured fused operator
 (norms, activations, GLUs, rope, cross-entropy, the three attentions) whose input is a view, or whose output fans out into
 several consumers whose gradients the engine sums, or whose only consumer hands its backward a strided gradient - the root is a cat along
-the last dim, or the operator is the root under a stepped or permuted grad_output (smooth_case)."""
+the last dim, or the operator is the root under a stepped or permuted grad_output (smooth_case).
+
+Seed blocks. The first blocks - exact seeds 0..199, smooth seeds 0..98 (the 11 operators above) - are frozen: a digest in
+tests/test_autograd_programs_reference.py pins their instructions, leaf data and grad_outputs. Behind them, exact seeds 200..289 put one of
+nine mixture-of-experts graphs (_moe_scenario: expert_linear, moe_dispatch, moe_combine, moe_gate as a gather - all exact on the tier's values,
+with shadow bounds like gemm's) on a 2-D node of an otherwise random program, and draw them as random instructions too; smooth seeds 99..161
+feature 7 more operators in 9 cases each (_featured2: softmax, log_softmax, attention and attention_qkv in their four mask families, rope_qkv,
+qk_norm_rope, moe_gate(normalize=True) behind a softmax). KF_FUZZ_SEED shifts all blocks by SEED_STRIDE; a seed's block and case are read off
+seed % SEED_STRIDE."""
 import numpy as np
 
 LIMIT = 2.0 ** 22
@@ -23,6 +31,9 @@ BF16_LIMIT = 2.0 ** 8
 SCALARS = (0.5, 1.0, 2.0, 3.0, 4.0)
 POW2 = (0.5, 1.0, 2.0, 4.0)
 SMOOTH_OPS = ("rms_norm", "layer_norm", "silu", "gelu", "swiglu", "geglu", "rope", "cross_entropy", "attn", "attn_gqa", "attn_qkv")
+SMOOTH_OPS2 = ("softmax", "log_softmax", "attention", "attention_qkv", "rope_qkv", "qk_norm_rope", "moe_gate")   # the second smooth block's
+MOE_OPS = ("expert_linear", "moe_dispatch", "moe_combine", "moe_gate")   # exact on the exact tier's values: drawn in the second exact block only
+N_SCENARIOS = 9
 VIEW_OPS = ("permute", "getitem", "view", "split")
 
 
@@ -46,9 +57,14 @@ class Node:
 
 
 class Builder:
-    def __init__(self, rng, tier, base_dt):
-        self.rng, self.tier, self.base_dt = rng, tier, base_dt
+    def __init__(self, rng, tier, base_dt, new_block=False):
+        self.rng, self.tier, self.base_dt, self.new_block = rng, tier, base_dt, new_block
         self.nodes, self.leaves, self.instrs, self.consts, self.feat = [], [], [], [], set()
+        self.must, self.fan_extra = set(), []   # nodes the root has to reach; further inputs of the fan-in cat (second blocks only)
+        # Second smooth block, ahead of the featured operator: no broadcast operands. softmax and log_softmax do not see a shift that is constant
+        # along their dim, qk_norm_rope and the normalised gate no such factor: the gradient of an operand broadcast that way is 0 in exact
+        # arithmetic and rounding residue in f32, which torch's f32 - the noise the bound is made of - may or may not show.
+        self.no_bcast = False
 
     # ---- nodes ---------------------------------------------------------------------------------------------------------------
     def new(self, shape_or_arr, dt, bound, fbits, req, **kw):
@@ -130,7 +146,8 @@ class Builder:
             b = self.leaf(self.sub_shape(na.shape), pow2=True)
         else:
             cands = [i for i, n in enumerate(self.nodes) if n.arr.ndim == na.arr.ndim and self.bcast(na.shape, n.shape) and not n.pow2]
-            b = int(cands[int(rng.integers(0, len(cands)))]) if cands and rng.random() < 0.5 else self.operand(na.shape)
+            # (no_bcast: a fresh operand always - (x + 3) - x would hand the featured operator a constant)
+            b = int(cands[int(rng.integers(0, len(cands)))]) if cands and rng.random() < 0.5 and not self.no_bcast else self.operand(na.shape)
         if self.tier == "smooth" and a == b:   # x - x would hand the featured operator an all-zero input: nothing to measure
             b = self.operand(na.shape)
         if op != "div" and rng.random() < 0.5:
@@ -161,7 +178,7 @@ class Builder:
         modelled on - refuse operands of different rank, so the generator does not draw them: a lower-rank operand is a `view` instruction to
         [1, .., N] first, which operand() emits.)"""
         rng = self.rng
-        if rng.random() < 0.4 or len(shape) == 0:
+        if self.no_bcast or rng.random() < 0.4 or len(shape) == 0:
             return tuple(shape)
         return tuple(1 if rng.random() < 0.5 else v for v in shape)
 
@@ -169,7 +186,7 @@ class Builder:
         """A fresh leaf that broadcasts against `shape`: of its rank, or - one time in three - of lower rank and viewed up to it."""
         rng = self.rng
         full = self.sub_shape(shape)
-        lead = int(rng.integers(1, len(full))) if len(full) >= 2 and rng.random() < 0.33 else 0
+        lead = int(rng.integers(1, len(full))) if not self.no_bcast and len(full) >= 2 and rng.random() < 0.33 else 0
         if not lead:
             return self.leaf(full)
         leaf = self.leaf(full[lead:])
@@ -278,7 +295,8 @@ class Builder:
                 all(d == dim or x == y for d, (x, y) in enumerate(zip(m.shape, n.shape)))]
         ins = [a]
         for _ in range(int(rng.integers(1, 3))):
-            ins.append(a if force_repeat or rng.random() < 0.35 else int(same[int(rng.integers(0, len(same)))]))
+            # (`not same`: a is a leaf of powers of two, which `same` leaves out - it is repeated. Shifted seeds met this; the committed ones never did.)
+            ins.append(a if force_repeat or rng.random() < 0.35 or not same else int(same[int(rng.integers(0, len(same)))]))
         shape = list(n.shape)
         shape[dim] = sum(self.nodes[i].shape[dim] for i in ins)
         o = self.new(tuple(shape), n.dt, max(self.nodes[i].bound for i in ins), max(self.nodes[i].fbits for i in ins),
@@ -344,9 +362,14 @@ class Builder:
     def random_instr(self):
         w = {"binary": 5, "scalar": 3, "convert": 2 if self.tier == "exact" else 0, "permute": 2, "getitem": 3, "view": 2, "split": 1, "cat": 2,
              "gemm": 2, "embedding": 1}
+        if self.new_block and self.tier == "exact":   # (a key of its own: the first block's draws stay what they were)
+            w["moe"] = 2
         names = list(w)
         p = np.array([w[k] for k in names], float)
         return getattr(self, names[int(self.rng.choice(len(names), p=p / p.sum()))])()
+
+    def moe(self):
+        return _moe_scenario(self, int(self.rng.integers(0, N_SCENARIOS)))
 
     # ---- gradient bounds: the reverse pass over the shadow ---------------------------------------------------------------------
     def grad_bounds(self, root, gb, gf):
@@ -410,6 +433,16 @@ class Builder:
                     give(b_, al * tb_ * N[a_].bound * M, tf_ + N[a_].fbits + fa)
                 elif op == "embedding":
                     give(ins[0], b * self.consts[par].size, f)
+                elif op == "expert_linear":   # dx = dy w[e]^T: Dout terms; dw[e] = x[seg]^T dy[seg]: at most T terms
+                    x_, w_ = ins
+                    give(x_, b * N[w_].bound * N[w_].shape[2], f + N[w_].fbits)
+                    give(w_, b * N[x_].bound * N[x_].shape[0], f + N[x_].fbits)
+                elif op in ("moe_dispatch", "moe_gate"):   # a gather: the gradient sums the k pairs of a token (moe_gate: normalize=False)
+                    give(ins[0], b * self.consts[par[0]].shape[1], f)
+                elif op == "moe_combine":
+                    ys, gt = ins
+                    give(ys, b * (N[gt].bound if gt >= 0 else 1.0), f + (N[gt].fbits if gt >= 0 else 0))
+                    give(gt, b * N[ys].bound * N[ys].shape[1], f + N[ys].fbits)
                 else:   # a smooth operator: no exactness to keep
                     for i in ins:
                         give(i, b, f)
@@ -446,6 +479,251 @@ class Builder:
                     return o
             self.rollback(cp)
         return None
+
+
+# ---- the second exact block's mixture-of-experts scenarios ---------------------------------------------------------------------------
+def _sorted_ids(rng, T, E):
+    """Ascending expert ids of T rows with (T permitting) a row below 0, a row at E - both outside every segment - and an expert without rows."""
+    ids = rng.integers(0, E, size=T)
+    empty = int(rng.integers(0, E))
+    ids[ids == empty] = (empty + 1) % E
+    if T >= 3:
+        ids[0], ids[-1] = -1, E
+    return np.sort(ids).astype(np.int64)
+
+
+def _topk_ids(rng, T, E, k, drops=1):
+    """[T, k] expert ids, distinct in a row while k <= E, with `drops` pairs outside [0, E) - never two in one row."""
+    ids = np.stack([rng.permutation(max(E, k))[:k] % E for _ in range(T)]).astype(np.int64)
+    for t in rng.permutation(T)[:drops]:
+        ids[t, int(rng.integers(0, k))] = (-1, E)[int(rng.integers(0, 2))]
+    return ids
+
+
+def _moe_scenario(b, sc):
+    """One of the N_SCENARIOS small graphs of expert_linear / moe_dispatch / moe_combine / moe_gate on a 2-D node of the program; returns
+    its output node, or None where no node fits. Bounds (bound, fbits) as gemm and embedding keep them."""
+    rng, N = b.rng, b.nodes
+
+    def pick2d(min_cols=2):
+        a = b.pick(lambda n: n.arr.ndim == 2 and not n.pow2 and n.shape[0] <= 8 and min_cols <= n.shape[1] <= 8)
+        return None if a is None else b.as_dt(a, "f32")   # (expert_linear and the routing have no f64)
+
+    def window(a, width=None):   # a column window of a: row-pitched, read in place through a leading dimension
+        cols = N[a].shape[1]
+        width = cols - 1 if width is None else width
+        lo = int(rng.integers(0, cols - width + 1))
+        return b.view_op("getitem", a, N[a].arr[:, lo:lo + width], ((None, None, None), (lo, lo + width, 1)))
+
+    def weight(E, Din):
+        return b.leaf((E, Din, int(rng.integers(3, 9))), dt="f32", req=True)
+
+    def el(x, w, par):
+        nx, nw = N[x], N[w]
+        o = b.new((nx.shape[0], nw.shape[2]), "f32", nx.shape[1] * nx.bound * nw.bound, nx.fbits + nw.fbits, nx.req or nw.req)
+        b.emit("expert_linear", [o], [x, w], par)
+        return o
+
+    def offsets(T, E):   # built on the host, or by segment_offsets on the device from the sorted ids
+        ids = _sorted_ids(rng, T, E)
+        if rng.random() < 0.5:
+            return ("ids", b.const(ids), E)
+        return ("offsets", b.const(np.searchsorted(ids, np.arange(E + 1), side="left").astype(np.int64)), E)
+
+    def plan(T, E=None):
+        E = int(rng.integers(2, 5)) if E is None else E
+        k = int(rng.integers(1, 4))
+        return b.const(_topk_ids(rng, T, E, k, drops=int(rng.integers(1, 3)))), E, k
+
+    def dispatch(x, cidx, E, k):
+        n = N[x]
+        o = b.new((n.shape[0] * k, n.shape[1]), "f32", n.bound, n.fbits, n.req)
+        b.emit("moe_dispatch", [o], [x], (cidx, E))
+        return o
+
+    def combine(ys, gate, cidx, E, k):
+        n, g = N[ys], (N[gate] if gate >= 0 else None)
+        o = b.new((n.shape[0] // k, n.shape[1]), "f32", k * n.bound * (g.bound if g else 1.0), n.fbits + (g.fbits if g else 0),
+                  n.req or bool(g and g.req))
+        b.emit("moe_combine", [o], [ys, gate], (cidx, E))
+        return o
+
+    def gate_of(p, cidx, E, k):
+        n = N[p]
+        o = b.new((n.shape[0], k), "f32", n.bound, n.fbits, n.req)
+        b.emit("moe_gate", [o], [p], (cidx, E, False))
+        return o
+
+    def add(a, c):
+        o = b.new(N[a].shape, "f32", N[a].bound + N[c].bound, max(N[a].fbits, N[c].fbits), N[a].req or N[c].req)
+        b.emit("add", [o], [a, c])
+        return o
+
+    x = pick2d(3 if sc in (1, 7, 8) else 2)
+    if x is None:
+        return None
+    T, cols = N[x].shape
+    E = int(rng.integers(2, 5))
+    if sc == 0:
+        return el(x, weight(E, cols), offsets(T, E))
+    if sc == 1:   # x is a column window of a wider tensor
+        xw = window(x)
+        return el(xw, weight(E, cols - 1), offsets(T, E))
+    if sc == 2:   # the same weight reached by two expert_linear calls
+        w = weight(E, cols)
+        return add(el(x, w, offsets(T, E)), el(b.unary("muls", x, 2.0, bound=N[x].bound * 2.0), w, offsets(T, E)))
+    if sc == 3:   # the same weight reached by expert_linear and, through w[e], by gemm
+        xd, w = b.densify(x), weight(E, cols)
+        e = int(rng.integers(0, E))
+        we = b.view_op("getitem", w, N[w].arr[e], (e,))
+        y2 = b.new((T, N[w].shape[2]), "f32", cols * N[xd].bound * N[w].bound, N[xd].fbits + N[w].fbits, True)
+        b.emit("gemm", [y2], [xd, we], 1.0)
+        return add(el(x, w, offsets(T, E)), y2)
+    if sc == 4:   # dispatch and combine without a gate
+        cidx, E, k = plan(T)
+        return combine(dispatch(x, cidx, E, k), -1, cidx, E, k)
+    if sc == 5:   # dispatch, the expert product on the plan's offsets, combine under a leaf gate of powers of two
+        cidx, E, k = plan(T)
+        h = el(dispatch(x, cidx, E, k), weight(E, cols), ("plan", cidx, E))
+        return combine(h, b.leaf((T, k), dt="f32", req=True, pow2=True), cidx, E, k)
+    if sc == 6:   # a gate that needs no gradient, or rows that need none under a gate that does
+        cidx, E, k = plan(T)
+        if rng.random() < 0.5:
+            return combine(dispatch(x, cidx, E, k), b.leaf((T, k), dt="f32", req=False, pow2=True), cidx, E, k)
+        return combine(b.leaf((T * k, int(rng.integers(3, 9))), dt="f32", req=False), b.leaf((T, k), dt="f32", req=True, pow2=True), cidx, E, k)
+    # the gate gathered from p, a column window of the node (or all of it), over the node's own rows dispatched
+    E = int(rng.integers(2, min(4, cols - 1) + 1))
+    p = x if cols <= 4 and sc == 8 and rng.random() < 0.5 else window(x, E)
+    cidx, E, k = plan(T, N[p].shape[1])
+    gate = gate_of(p, cidx, E, k)
+    xs = dispatch(x, cidx, E, k)
+    if sc == 7:
+        return combine(xs, gate, cidx, E, k)
+    return combine(el(xs, weight(E, cols), ("plan", cidx, E)), gate, cidx, E, k)   # sc 8: the whole layer
+
+
+def host_offsets(par, consts, T):
+    """The offsets of an expert_linear instruction as int64 [E + 1]: (how they are made, const, E)."""
+    how, cidx, E = par
+    if how == "offsets":
+        return consts[cidx]
+    if how == "ids":
+        from tests import gemm_seg_ref
+        return gemm_seg_ref.segment_offsets(consts[cidx], E)
+    from tests import moe_ref
+    return moe_ref.plan(consts[cidx], E)[0]
+
+
+def _sanitized(offsets, T):
+    from tests import gemm_seg_ref
+    return gemm_seg_ref.sanitize(offsets, T)
+
+
+def attn_vis(mask, consts, B, Sq, Skv):
+    """bool [B, Sq, Skv] of an attention instruction's mask (family, kv_len const, prefix_len const, window, causal, cu_doclens const): built
+    by the visibility functions of the kernels' own references."""
+    from tests import attn_doc_ref, attn_full_ref, attn_prefix_ref, attn_window_ref
+    fam, kv, pre, win, causal, doc = mask
+    kv = None if kv is None else consts[kv]
+    if fam == "full":
+        return attn_full_ref.key_len_vis(kv, Sq, Skv, B)
+    if fam == "prefix":
+        return attn_prefix_ref.prefix_vis(kv, None if pre is None else consts[pre], Sq, Skv, B)
+    if fam == "window":
+        return attn_window_ref.window_vis(kv, win[0], 0 if causal else win[1], Sq, Skv, B)
+    assert fam == "doc" and Sq == Skv
+    return attn_doc_ref.doc_vis(consts[doc], Sq, causal)
+
+
+def _case_mask(b, kind, case):
+    """The mask of the attention operators' case 0..8: every family, with the edges each family has."""
+    K = lambda a: b.const(np.asarray(a, np.int64))   # noqa: E731
+    if case == 8:   # attention: keys of another length than the queries (Skv = 6); attention_qkv: a causal window with an open right side
+        return ("full", K([5, 2]), None, None, False, None) if kind == "attention" else ("window", None, None, (2, None), True, None)
+    return (lambda: ("full", K([0, 3]), None, None, False, None),            # a batch without keys
+            lambda: ("prefix", K([2, 4]), None, None, True, None),           # causal over a padded batch
+            lambda: ("prefix", None, K([3, 1]), None, True, None),           # prefix-LM
+            lambda: ("window", None, None, (1, None), False, None),
+            lambda: ("window", None, None, (None, 0), True, None),
+            lambda: ("window", K([2, 4]), None, (0, 1), False, None),        # queries 2 and 3 of batch 0 see no key
+            lambda: ("doc", None, None, None, False, K([[0, 2, 2, 3], [0, 1, 4, 4]])),   # a zero-length document; token 3 of row 0 in none
+            lambda: ("doc", None, None, None, True, K([[0, 2, 2, 3], [0, 1, 4, 4]])))[case]()
+
+
+def _featured2(b, kind, case, view_fed, fanin):
+    """The second smooth block's operators on the pool's main [T, d] tensor; case = 3 * variant + (view, fan-in, noncontig)."""
+    rng, N = b.rng, b.nodes
+    B_, S_, H_, D_ = 2, 4, 2, 8
+    T, d = B_ * S_, H_ * D_
+    variant = case // 3
+    x = b.densify(b.pick(lambda n: n.shape == (T, d) and n.req))
+
+    def smooth(op, ins, shape, par=None):
+        o = b.new(shape if isinstance(shape, np.ndarray) else tuple(shape), "f32", 1.0, 0, True)
+        b.emit(op, [o], ins, par)
+        for i in ins:
+            if i >= 0 and N[i].view:
+                b.feat.add(kind + "_from_view")
+        return o
+
+    if kind in ("softmax", "log_softmax"):
+        dim = (-1, -1, 0)[variant] if view_fed else (-1, 0, -1)[variant]
+        if view_fed and variant == 1:   # a permuted view: densified
+            x = b.view_op("permute", x, N[x].arr.transpose(1, 0), [1, 0])
+        elif view_fed:   # a column window: row-pitched, read in place
+            x = b.view_op("getitem", x, N[x].arr[:, 2:14], ((None, None, None), (2, 14, 1)))
+        shape = N[x].shape
+        if dim == 0:   # dim and the last dimension change places and back: the result is a permuted view of a dense tensor, not a dense one
+            shape = np.zeros(shape[::-1], np.int8).transpose(1, 0)
+        return smooth(kind, [x], shape, (dim, (1.0, 0.5, 2.0)[variant]))
+
+    def heads(t, h, S):   # [B*S, h*D] -> [B, h, S, D]: a dense view as it stands (view_fed), or split heads the usual way
+        if view_fed:
+            return b.view_op("view", t, N[t].arr.reshape(B_, h, S, D_), (B_, h, S, D_))
+        t4 = b.view_op("view", t, N[t].arr.reshape(B_, S, h, D_), (B_, S, h, D_))
+        return b.densify(b.view_op("permute", t4, N[t4].arr.transpose(0, 2, 1, 3), [0, 2, 1, 3]))
+
+    def packed(kv, v_req):   # cat([x, k, v]) along the columns; view-fed: a dense view of a view of it
+        k, v = b.leaf((T, kv * D_), req=True), b.leaf((T, kv * D_), req=v_req)
+        q = b.new((T, d + 2 * kv * D_), "f32", 2.0, 0, True)
+        b.emit("cat", [q], [x, k, v], 1)
+        if view_fed:
+            q = b.view_op("view", q, N[q].arr.reshape(-1), (-1,))
+            q = b.view_op("view", q, N[q].arr.reshape(T, -1), (T, -1))
+        return q
+
+    kv = H_ if case % 2 == 0 else 1
+    if kind == "attention":
+        Skv = 6 if case == 8 else S_
+        k, v = b.leaf((B_ * Skv, kv * D_), req=True), b.leaf((B_ * Skv, kv * D_), req=case % 3 != 1)
+        return smooth(kind, [heads(x, H_, S_), heads(k, kv, Skv), heads(v, kv, Skv)], (B_, H_, S_, D_), _case_mask(b, kind, case))
+    if kind == "attention_qkv":
+        return smooth(kind, [packed(kv, bool(case % 3))], (T, d), (B_, S_, H_, kv, _case_mask(b, kind, case)))
+    if kind in ("rope_qkv", "qk_norm_rope"):
+        R, inter = (8, 4, 4)[variant], bool(case % 2)
+        pos = b.const(rng.integers(0, 16, size=(T,)).astype(np.int64)) if case in (1, 3, 8) else None
+        q = packed(kv, bool(case % 3))
+        if kind == "rope_qkv":
+            return smooth(kind, [q], N[q].shape, (B_, S_, H_, kv, R, inter, pos))
+        wq = -1 if case in (1, 5) else b.leaf((D_,), req=case % 2 == 0)
+        wk = -1 if case in (2, 5) else b.leaf((D_,), req=case % 4 != 0)
+        return smooth(kind, [q, wq, wk], N[q].shape, (B_, S_, H_, kv, 0 if case in (3, 7) else R, inter, pos, 1e-6))   # R = 0: no tables
+    assert kind == "moe_gate"   # the router: softmax -> moe_gate(normalize=True) (-> moe_combine, once, where the gate fans out)
+    p = b.new((T, d), "f32", 1.0, 0, True)
+    b.emit("softmax", [p], [x], (-1, 1.0))
+    E = d
+    if view_fed:
+        p, E = b.view_op("getitem", p, N[p].arr[:, 2:14], ((None, None, None), (2, 14, 1))), 12
+    k = (2, 3, 2)[variant]
+    cidx = b.const(_topk_ids(rng, T, E, k, drops=2))
+    o = smooth(kind, [p], (T, k), (cidx, E, True))
+    if fanin:
+        xs = b.new((T * k, d), "f32", 2.0, 0, True)
+        b.emit("moe_dispatch", [xs], [x], (cidx, E))
+        y = b.new((T, d), "f32", 2.0, 0, True)
+        b.emit("moe_combine", [y], [xs, o], (cidx, E))
+        b.fan_extra = [y]
+    return o
 
 
 # ---- the smooth tier's featured operator -----------------------------------------------------------------------------------------
@@ -532,10 +810,22 @@ def make_program(seed, tier="exact"):
     assert tier in ("exact", "smooth")
     for attempt in range(200):
         rng = np.random.default_rng([seed, attempt, 0 if tier == "exact" else 1])
-        b = Builder(rng, tier, "f32" if tier == "smooth" or rng.random() < 0.6 else "f64")
+        new = in_second_block(seed, tier)
+        b = Builder(rng, tier, "f32" if tier == "smooth" or rng.random() < 0.6 else "f64", new)
         twice = seed % 4 == 3
         gb, gf = (4.0 if twice else 2.0), 1
-        if tier == "exact":
+        if tier == "exact" and new:   # a 2-D leaf, a few instructions, the seed's mixture-of-experts scenario on one of their nodes, a few more
+            b.leaf((int(rng.integers(5, 9)), int(rng.integers(3, 9))), req=True)
+            for _ in range(int(rng.integers(1, 4))):
+                b.step(b.random_instr, gb, gf)
+            o = b.step(lambda: _moe_scenario(b, (seed % SEED_STRIDE - N_EXACT) % N_SCENARIOS), gb, gf, need_req=True)
+            if o is None:
+                continue
+            b.must.add(o)
+            for _ in range(int(rng.integers(0, 3))):
+                b.step(b.random_instr, gb, gf)
+            root = b.step(b.random_instr, gb, gf, need_req=True)
+        elif tier == "exact":
             shape = tuple(int(v) for v in rng.choice((1, 2, 3, 4, 5, 6), size=int(rng.integers(1, 4))))
             b.leaf(shape, req=True)
             for _ in range(int(rng.integers(5, 12))):
@@ -545,9 +835,14 @@ def make_program(seed, tier="exact"):
             kind, mode, variant = smooth_case(seed)
             view_fed = mode == "view"
             b.leaf((8, 16), req=True)
+            b.no_bcast = new
             for _ in range(int(rng.integers(1, 4))):
                 b.step(lambda: (b.binary, b.scalar)[int(rng.integers(0, 2))](), gb, gf)
-            o = _featured(b, kind, variant, view_fed, mode == "noncontig")
+            b.no_bcast = False
+            if new:
+                o = _featured2(b, kind, 3 * variant + ("view", "fanin", "noncontig").index(mode), view_fed, mode == "fanin")
+            else:
+                o = _featured(b, kind, variant, view_fed, mode == "noncontig")
             if mode == "noncontig":
                 # the operator's ONLY consumer hands its backward a strided gradient: the root is cat([o, other], last dim), whose backward narrows
                 # the root's gradient to o's columns - or o is the root itself and the grad_output is a stepped or permuted view
@@ -565,8 +860,9 @@ def make_program(seed, tier="exact"):
                 continue
             if mode == "fanin":   # the operator's gradient: the sum of two or three consumers (the engine adds the cat's windows to the rest)
                 o2 = b.unary("muls", o, 2.0)
-                c = b.new(b.nodes[o].shape[:-1] + ((3 if seed % 2 else 2) * b.nodes[o].shape[-1],), "f32", 2.0, 0, True)
-                b.emit("cat", [c], [o, o, o2] if seed % 2 else [o, o2], b.nodes[o].arr.ndim - 1)
+                wide = (3 if seed % 2 else 2) * b.nodes[o].shape[-1] + sum(b.nodes[i].shape[-1] for i in b.fan_extra)
+                c = b.new(b.nodes[o].shape[:-1] + (wide,), "f32", 2.0, 0, True)
+                b.emit("cat", [c], ([o, o, o2] if seed % 2 else [o, o2]) + b.fan_extra, b.nodes[o].arr.ndim - 1)
             for _ in range(int(rng.integers(1, 4))):
                 b.step(b.random_instr, gb, gf)
             root = b.step(b.random_instr, gb, gf, need_req=True)
@@ -579,12 +875,129 @@ def make_program(seed, tier="exact"):
 
 
 def smooth_case(seed):
-    """(operator, how it is fed, variant) of a smooth-tier seed: 99 seeds = 11 operators x (view, fan-in) x 3 variants, then x (noncontig) x 3."""
+    """(operator, how it is fed, variant) of a smooth-tier seed: 99 seeds = 11 operators x (view, fan-in) x 3 variants, then x (noncontig) x 3;
+    the second block's 63 = 7 operators x 3 variants x (view, fan-in, noncontig)."""
+    if in_second_block(seed, "smooth"):   # 63 seeds = 7 operators x case 0..8; case = 3 * variant + (view, fan-in, noncontig)
+        s = (seed % SEED_STRIDE - N_SMOOTH) % N_SMOOTH2
+        case = s // len(SMOOTH_OPS2)
+        return SMOOTH_OPS2[s % len(SMOOTH_OPS2)], ("view", "fanin", "noncontig")[case % 3], case // 3
     s = seed % N_SMOOTH
     kind = SMOOTH_OPS[s % len(SMOOTH_OPS)]
     if s < 66:
         return kind, ("view", "fanin")[(s // 11) % 2], s // 22
     return kind, "noncontig", (s - 66) // 11
+
+
+def _col_window(n):
+    a = n.arr
+    return a.ndim == 2 and a.shape[1] > 1 and a.strides[1] == 1 and a.strides[0] > a.shape[1]   # (int8 shadow: strides in elements)
+
+
+def _cover_second_blocks(b, instrs, uses, feat):
+    """What the reached instructions of the second blocks' operators cover, read off their parameters, constants and the shadow."""
+    N, consts = b.nodes, b.consts
+    w_el, w_gemm = {}, {}
+    producer = {o: op for op, outs, _, _ in instrs for o in outs}
+
+    def routing(cidx, E):
+        ids = consts[cidx]
+        feat.add(f"moe_k{ids.shape[1]}")
+        if ((ids < 0) | (ids >= E)).any():
+            feat.add("moe_dropped_pair")
+
+    for op, outs, ins, par in instrs:
+        if op == "expert_linear":
+            x, w = ins
+            T, E = N[x].shape[0], par[2]
+            off = _sanitized(host_offsets(par, consts, T), T)
+            feat.add("expert_linear_offsets_" + par[0])
+            if (off[1:] == off[:-1]).any():
+                feat.add("expert_linear_empty_expert")
+            if off[0] > 0 or off[E] < T:
+                feat.add("expert_linear_uncovered_rows")
+            if _col_window(N[x]):
+                feat.add("expert_linear_x_column_window")
+            if producer.get(x) == "to":
+                feat.add("expert_linear_behind_a_conversion")
+            w_el[w] = w_el.get(w, 0) + 1
+        elif op == "gemm" and N[ins[1]].view and N[ins[1]].src is not None:
+            w_gemm[N[ins[1]].src] = 1
+        elif op == "moe_dispatch":
+            routing(par[0], par[1])
+            if _col_window(N[ins[0]]):
+                feat.add("moe_dispatch_x_column_window")
+        elif op == "moe_combine":
+            ys, gate = ins
+            routing(par[0], par[1])
+            feat.add("moe_combine_ys_" + ("requiring" if N[ys].req else "not_requiring"))
+            if gate < 0:
+                feat.add("moe_combine_gate_none")
+            else:
+                feat.add("moe_combine_gate_" + ("requiring" if N[gate].req else "not_requiring"))
+                feat.add("moe_combine_gate_" + ("from_moe_gate" if producer.get(gate) == "moe_gate" else "leaf"))
+        elif op == "moe_gate":
+            routing(par[0], par[1])
+            feat.add("moe_gate_normalize" if par[2] else "moe_gate_gather")
+            if _col_window(N[ins[0]]):
+                feat.add("moe_gate_p_column_window")
+        elif op in ("softmax", "log_softmax"):
+            nd = N[ins[0]].arr.ndim
+            if par[0] % nd != nd - 1:
+                feat.add(op + "_nonlast_dim")
+            if par[1] != 1.0:
+                feat.add(op + "_scale")
+            feat.add(op + ("_column_window" if _col_window(N[ins[0]]) else "_dense" if N[ins[0]].dense else "_permuted_view"))
+        elif op in ("attention", "attention_qkv"):
+            mask = par if op == "attention" else par[4]
+            fam, kv, pre, win, causal, doc = mask
+            if op == "attention":
+                Bq, Hq, Sq, _ = N[ins[0]].shape
+                Hkv, Skv = N[ins[1]].shape[1], N[ins[1]].shape[2]
+            else:
+                Bq, Sq, Hq, Hkv = par[:4]
+                Skv = Sq
+            feat.add(f"{op}_{fam}")
+            feat.add(f"{op}_hkv_" + ("h" if Hkv == Hq else "1"))
+            if Skv != Sq:
+                feat.add(op + "_skv_ne_sq")
+            if fam == "prefix":
+                feat.add(op + ("_causal_no_prefix" if pre is None else "_prefix_len"))
+            if fam == "window":
+                feat.add(op + "_window_" + ("causal" if causal else "noncausal"))
+                for side, v in zip(("left", "right"), win):
+                    feat.add(f"{op}_window_{side}_" + ("none" if v is None else "0" if v == 0 else "small"))
+            vis = attn_vis(mask, consts, Bq, Sq, Skv)
+            keyless = ~vis.any(-1)
+            if keyless.any() and not keyless.all():
+                feat.add(op + "_keyless_query")
+            if kv is not None and (consts[kv] == 0).any():
+                feat.add(op + "_kv_len_0")
+            if fam == "doc":
+                cu = consts[doc]
+                feat.add(op + ("_doc_causal" if causal else "_doc_full"))
+                if (np.diff(cu, axis=1) == 0).any():
+                    feat.add(op + "_zero_length_document")
+                if (cu[:, -1] < Sq).any():
+                    feat.add(op + "_token_in_no_document")
+        elif op in ("rope_qkv", "qk_norm_rope"):
+            Bq, Sq, Hq, kvh, R, inter, pos = par[:7]
+            D = N[ins[0]].shape[1] // (Hq + 2 * kvh)
+            feat.add(op + ("_positions" if pos is not None else "_no_positions"))
+            feat.add(op + ("_interleaved" if inter else "_rotate_half"))
+            feat.add(f"{op}_hkv_" + ("h" if kvh == Hq else "1"))
+            if 0 < R < D:
+                feat.add(op + "_r_lt_d")
+            if op == "qk_norm_rope":
+                feat.add(op + ("_no_tables" if R == 0 else "_tables"))
+                feat.add(op + ("_none_weight" if min(ins[1:]) < 0 else "_both_weights"))
+                for w in ins[1:]:
+                    if w >= 0:
+                        feat.add(op + "_weight_" + ("requiring" if N[w].req else "not_requiring"))
+    for w, n in w_el.items():
+        if N[w].req and n >= 2:
+            feat.add("expert_linear_w_reached_twice")
+        if N[w].req and w in w_gemm:
+            feat.add("expert_linear_w_also_through_gemm")
 
 
 def _finish(b, root, seed, tier, twice, force_how=None, noncontig=None):
@@ -595,7 +1008,11 @@ def _finish(b, root, seed, tier, twice, force_how=None, noncontig=None):
         if any(o in reach for o in outs):
             order.append(ins_i)
             reach.update(i for i in ins if i >= 0)
-    if tier == "smooth" and not any(b.instrs[i][0] in SMOOTH_OPS for i in order):
+    if any(m not in reach for m in b.must):
+        return None
+    # the featured operators: any of the first block's, the seed's own in the second (whose router case holds a softmax besides its moe_gate)
+    featured = () if tier == "exact" else ((smooth_case(seed)[0],) if b.new_block else SMOOTH_OPS)
+    if tier == "smooth" and not any(b.instrs[i][0] in featured for i in order):
         return None
     mode = smooth_case(seed)[1] if tier == "smooth" else None
     gbounds = b.grad_bounds(root, 4.0 if twice else 2.0, 1)
@@ -636,11 +1053,12 @@ def _finish(b, root, seed, tier, twice, force_how=None, noncontig=None):
             feat.add("embedding_negative" if (b.consts[par] < 0).any() else "embedding")
     for i in order:
         op, outs, ins, par = b.instrs[i]
-        if op in SMOOTH_OPS:
+        if op in featured:
             if uses[outs[0]] >= 2:
                 feat.add(op + "_from_fanin")
             elif mode == "fanin":
                 return None
+    _cover_second_blocks(b, [b.instrs[i] for i in order], uses, feat)
     if noncontig is not None:   # the gradient the featured operator's backward receives is strided: checked on the shadow, not assumed
         kind, o = noncontig
         if root == o:
@@ -665,7 +1083,7 @@ def _finish(b, root, seed, tier, twice, force_how=None, noncontig=None):
         feat.add("noncontig_grad_" + grads[0][1])
     return {"seed": seed, "tier": tier, "leaves": list(b.leaves), "instrs": list(b.instrs), "consts": list(b.consts), "root": root, "grads": grads,
             "nodes": [(n.shape, n.dt, n.bound, n.fbits, n.req) for n in N], "gbounds": gbounds or {}, "features": feat,
-            "reached": reach}
+            "reached": reach, "scenario": (seed % SEED_STRIDE - N_EXACT) % N_SCENARIOS if tier == "exact" and b.new_block else None}
 
 
 # ---- interpreters ---------------------------------------------------------------------------------------------------------------------
@@ -686,6 +1104,20 @@ def _grad_view(t, how, perm):
     if how == "step":
         return t[(slice(None),) * (t.dim() - 1) + (slice(None, None, 2),)]
     return t
+
+
+def _torch_attention(q, k, v, vis):
+    """where(any key visible, softmax(masked scores), 0) @ v of q [B, Hq, Sq, D] over k, v [B, Hkv, Skv, D] under vis [B, Sq, Skv]: a query without
+    a key gives a zero row and no gradient (scaled_dot_product_attention gives NaN there)."""
+    import torch
+    g = q.shape[1] // k.shape[1]
+    k, v = k.repeat_interleave(g, 1), v.repeat_interleave(g, 1)
+    m = torch.from_numpy(np.ascontiguousarray(vis))[:, None]
+    some = m.any(-1, keepdim=True)
+    s = torch.matmul(q, k.transpose(-1, -2)) / float(np.sqrt(q.shape[-1]))
+    s = torch.where(some, s.masked_fill(~m, float("-inf")), torch.zeros((), dtype=s.dtype))
+    p = torch.where(some & m, torch.softmax(s, -1), torch.zeros((), dtype=s.dtype))
+    return torch.matmul(p, v)
 
 
 def run_torch(prog, dtype=None, trace=False):
@@ -775,6 +1207,58 @@ def run_torch(prog, dtype=None, trace=False):
             hd = lambda t, h: t.reshape(Bq, Sq, h, Dq).permute(0, 2, 1, 3)   # noqa: E731
             a = F.scaled_dot_product_attention(hd(q, Hq), hd(k, kv).repeat_interleave(Hq // kv, 1), hd(v, kv).repeat_interleave(Hq // kv, 1), is_causal=True)
             r = a.permute(0, 2, 1, 3).reshape(Bq * Sq, Hq * Dq)
+        elif op in ("softmax", "log_softmax"):
+            r = (torch.softmax if op == "softmax" else torch.log_softmax)(x[0] * par[1], par[0])
+        elif op == "attention":
+            r = _torch_attention(x[0], x[1], x[2], attn_vis(par, consts, x[0].shape[0], x[0].shape[2], x[1].shape[2]))
+        elif op == "attention_qkv":
+            Bq, Sq, Hq, kv, mask = par
+            Dq = x[0].shape[1] // (Hq + 2 * kv)
+            q, k, v = torch.split(x[0], [Hq * Dq, kv * Dq, kv * Dq], 1)
+            hd = lambda t, h: t.reshape(Bq, Sq, h, Dq).permute(0, 2, 1, 3)   # noqa: E731
+            a = _torch_attention(hd(q, Hq), hd(k, kv), hd(v, kv), attn_vis(mask, consts, Bq, Sq, Sq))
+            r = a.permute(0, 2, 1, 3).reshape(Bq * Sq, Hq * Dq)
+        elif op in ("rope_qkv", "qk_norm_rope"):
+            Bq, Sq, Hq, kv, R, inter, pos = par[:7]
+            Tq, Ht = Bq * Sq, Hq + 2 * kv
+            x3 = x[0].reshape(Tq, Ht, -1)
+            n = x3[:, :Hq + kv]
+            if op == "qk_norm_rope":   # rstd = 1 / sqrt(mean x^2 + eps), n = x rstd w per q and k head; a missing weight is 1
+                one = torch.ones(x3.shape[2], dtype=x3.dtype)
+                w = torch.cat([(one if x[1] is None else x[1]).expand(Hq, -1), (one if x[2] is None else x[2]).expand(kv, -1)], 0)
+                n = n * torch.rsqrt((n * n).mean(-1, keepdim=True) + par[7]) * w[None]
+            if R:
+                c, s = (torch.from_numpy(t).to(x3.dtype) for t in rope_tables(16, R))
+                p = torch.arange(Tq) % Sq if pos is None else torch.from_numpy(consts[pos])
+                cc, ss = c[p][:, None, :], s[p][:, None, :]
+                ia = torch.arange(0, R, 2) if inter else torch.arange(R // 2)
+                ib = ia + 1 if inter else ia + R // 2
+                na, nb = n[..., ia], n[..., ib]
+                n = n.clone()
+                n[..., ia] = na * cc - nb * ss
+                n[..., ib] = nb * cc + na * ss
+            r = torch.cat([n, x3[:, Hq + kv:]], 1).reshape(Tq, -1)
+        elif op == "expert_linear":
+            Tq, E = x[0].shape[0], x[1].shape[0]
+            so = _sanitized(host_offsets(par, consts, Tq), Tq)
+            zero = lambda rows: torch.zeros(int(rows), x[1].shape[2], dtype=x[0].dtype)   # noqa: E731
+            r = torch.cat([zero(so[0])] + [x[0][int(so[e]):int(so[e + 1])] @ x[1][e] for e in range(E)] + [zero(Tq - so[E])], 0)
+        elif op in ("moe_dispatch", "moe_combine", "moe_gate"):
+            from tests import moe_ref
+            ids, E = consts[par[0]], par[1]
+            k = ids.shape[1]
+            offsets, row_pair, pair_row = moe_ref.plan(ids, E)
+            if op == "moe_dispatch":
+                r = x[0][torch.from_numpy(row_pair.astype(np.int64) // k)]
+            elif op == "moe_combine":   # dropped pairs sort behind the live ones: rows offsets[E].. are never read
+                pr = torch.from_numpy(pair_row.astype(np.int64).reshape(-1, k))
+                terms = x[0][pr] if x[1] is None else x[1][..., None] * x[0][pr]
+                r = torch.where((pr < int(offsets[E]))[..., None], terms, torch.zeros((), dtype=terms.dtype)).sum(1)
+            else:
+                ok = torch.from_numpy((ids >= 0) & (ids < E))
+                r = torch.where(ok, x[0].gather(1, torch.from_numpy(np.where((ids >= 0) & (ids < E), ids, 0))), torch.zeros((), dtype=x[0].dtype))
+                if par[2]:
+                    r = r / r.sum(1, keepdim=True)
         else:
             raise AssertionError(op)
         if trace and r is x[0]:   # torch's contiguous() / to() of a tensor that needs neither: a node of its own for the trace
@@ -802,6 +1286,13 @@ def run_kfunca(mod, prog):
     conv = {"f32": lambda t: t.float(), "f64": lambda t: t.double()}
     out = {"root": None, "grads": {}, "meta": {}, "error": None}
     up = lambda a: mod.from_numpy(np.ascontiguousarray(a), 0)   # noqa: E731
+    plans = {}
+
+    def plan_of(cidx, E):   # one plan per routing, shared by its gate, dispatch, expert product and combine as a layer shares it
+        if (cidx, E) not in plans:
+            plans[cidx, E] = mod.moe_plan(up(consts[cidx]), E)
+        return plans[cidx, E]
+
     for i, arr, req in prog["leaves"]:
         T[i] = up(arr)
         if req:
@@ -869,6 +1360,32 @@ def run_kfunca(mod, prog):
                 r = mod.causal_attention_gqa(x[0], x[1], x[2])
             elif op == "attn_qkv":
                 r = mod.causal_attention_qkv(x[0], par[0], par[1], par[2], kv_heads=par[3])
+            elif op in ("softmax", "log_softmax"):
+                r = getattr(mod, op)(x[0], dim=par[0], scale=par[1])
+            elif op in ("attention", "attention_qkv"):
+                fam, kv, pre, win, causal, doc = par if op == "attention" else par[4]
+                S_ = x[0].sizes()[2] if op == "attention" else par[1]
+                kw = dict(kv_len=None if kv is None else up(consts[kv]), causal=causal, prefix_len=None if pre is None else up(consts[pre]),
+                          window=win, doc_mask=None if doc is None else mod.doc_mask(up(consts[doc]), S_))
+                r = mod.attention(x[0], x[1], x[2], **kw) if op == "attention" else mod.attention_qkv(x[0], par[0], par[1], par[2], kv_heads=par[3], **kw)
+            elif op in ("rope_qkv", "qk_norm_rope"):
+                Bq, Sq, Hq, kv, R, inter, pos = par[:7]
+                c, s = (up(t) for t in rope_tables(16, R)) if R else (None, None)
+                posd = None if pos is None else up(consts[pos])
+                if op == "rope_qkv":
+                    r = mod.rope_qkv(x[0], c, s, Bq, Sq, Hq, kv_heads=kv, positions=posd, interleaved=inter)
+                else:
+                    r = mod.qk_norm_rope(x[0], x[1], x[2], c, s, Bq, Sq, Hq, kv_heads=kv, positions=posd, interleaved=inter, eps=par[7])
+            elif op == "expert_linear":
+                how, cidx, E = par
+                off = plan_of(cidx, E).offsets if how == "plan" else (mod.segment_offsets(up(consts[cidx]), E) if how == "ids" else up(consts[cidx]))
+                r = mod.expert_linear(x[0], x[1], off)
+            elif op == "moe_dispatch":
+                r = mod.moe_dispatch(x[0], plan_of(par[0], par[1]))
+            elif op == "moe_combine":
+                r = mod.moe_combine(x[0], plan_of(par[0], par[1]), gate=x[1])
+            elif op == "moe_gate":
+                r = mod.moe_gate(x[0], plan_of(par[0], par[1]), normalize=par[2])
             else:
                 raise AssertionError(op)
             T[o] = r
@@ -886,8 +1403,8 @@ def run_kfunca(mod, prog):
                 continue
             out["meta"][i] = (tuple(g.sizes()), str(g.dtype()).split(".")[-1])
             out["grads"][i] = g.contiguous().numpy()
-    except RuntimeError as e:
-        out["error"] = (step, str(e))
+    except (RuntimeError, ValueError, TypeError) as e:   # (the newer bindings raise the latter two: a refusal names its program all the same)
+        out["error"] = (step, f"{type(e).__name__}: {e}" if not isinstance(e, RuntimeError) else str(e))
     return out
 
 
@@ -904,10 +1421,19 @@ N_EXACT, N_SMOOTH = 200, 99          # 99 = 3 variants x (fed by a view | fan-in
 SEED_STRIDE = 1188000                # KF_FUZZ_SEED shifts both sweeps by this: a multiple of 99 and of 12, so seed % k keeps its meaning
 
 
-def sweep(tier, shift=0):
-    """The seeds of the sweep; every one of them yields a program (make_program raises otherwise): nothing is skipped."""
-    n = N_EXACT if tier == "exact" else N_SMOOTH
-    return [shift * SEED_STRIDE + s for s in range(n)]
+N_EXACT2, N_SMOOTH2 = 90, 63         # the second blocks, behind the first ones: 10 x the 9 mixture-of-experts scenarios; 7 operators x 9 cases
+
+
+def in_second_block(seed, tier):
+    return seed % SEED_STRIDE >= (N_EXACT if tier == "exact" else N_SMOOTH)
+
+
+def sweep(tier, shift=0, block=None):
+    """The seeds of the sweep (block 1 or 2: of that block alone); every one of them yields a program (make_program raises otherwise):
+    nothing is skipped."""
+    n1, n2 = (N_EXACT, N_EXACT2) if tier == "exact" else (N_SMOOTH, N_SMOOTH2)
+    lo, hi = {None: (0, n1 + n2), 1: (0, n1), 2: (n1, n1 + n2)}[block]
+    return [shift * SEED_STRIDE + s for s in range(lo, hi)]
 
 
 def compare_exact(prog, want, got):
