@@ -877,6 +877,59 @@ int kf_moe_combine_bwd(int dtype, int64_t T, int64_t k, int64_t cols, const int3
                        const void *gate, int64_t ldg, const void *ys, int64_t ldys, const void *dy, int64_t lddy,
                        void *dys, int64_t lddys, void *dgate, int64_t lddg, void *stream);
 
+/* ---- the mixture-of-experts router in front of that routing (no reference counterpart: the top-k choice and gates of Mixtral,
+ *      Qwen3-MoE and DeepSeek-V3 and the auxiliary losses of Switch / Megatron and ST-MoE, fused, with both directions of each) ---- */
+/*
+ * logits: [T, E] (pitch ldl), one row per token. One wave owns a token's E logits in registers, so 1 <= k <= min(E, 64) and E <= 1024;
+ * anything larger is KF_ERR_UNSUPPORTED. score is KF_MOE_SCORE_SOFTMAX or KF_MOE_SCORE_SIGMOID, normalize 0 or 1.
+ *     router_fwd    SELECTION: ids[t, 0 .. k) (int64 [T, k], dense) are the first k positions of the stable descending order of row t in
+ *                   kf_sort's key order for the dtype: by value, -0.0 below +0.0, NaNs by bit pattern (a NaN with the sign bit clear
+ *                   above +inf, one with it set below -inf), equal keys by lower index first. The comparison is on the stored bits and
+ *                   involves no arithmetic: ids equal the indices of this library's descending kf_sort of the row bit for bit, for both
+ *                   scores (softmax and sigmoid are monotone).
+ *                   GATE (f32, one rounding per stored element): softmax: m = the row maximum, e_v = exp(l_v - m), Z = sum_v e_v,
+ *                   s_j = e_(ids_j) / Z; sigmoid: s_j = 1 / (1 + exp(-l_(ids_j))). gate[t, j] = s_j (normalize == 0) or s_j / S
+ *                   (normalize == 1), S = s_0 + ... + s_(k-1) summed in the order j as kf_moe_gate_fwd does. A row with a NaN, a +inf or
+ *                   only -inf gives what the formula gives (NaN gates for softmax); ids stay defined by the key order in every case.
+ *     router_bwd    recomputes the row from logits and ids (the stored gate is not read) and writes EVERY element of dlogits [T, E]: the
+ *                   exact derivative of the gate formula contracted with dgate [T, k], zero where the derivative is zero (with sigmoid,
+ *                   and with softmax + normalize, off the chosen columns). An id outside [0, E) contributes nothing and reads nothing.
+ *     aux_loss_fwd  p = softmax(logits) in f32; c_e = offsets[e + 1] - offsets[e], the live pairs of expert e (offsets: int64 [E + 1] on
+ *                   the DEVICE, the plan's, read by the kernel and treated as a constant);
+ *                   L_bal = E / (T k) sum_e c_e (1 / T) sum_t p[t, e]   (the Switch / Megatron normalisation: 1 for uniform routing;
+ *                   HF-Mixtral's load_balancing_loss_func gives k times this); L_z = (1 / T) sum_t lse_t^2, lse_t = m + log Z (ST-MoE);
+ *                   loss[0] = balance_coef L_bal + z_coef L_z, parts = {L_bal, L_z} when not NULL (f32, device). No atomics: a block
+ *                   keeps the column sums and the sum of lse^2 of the rows it walks in registers, its four waves are added in wave order
+ *                   and one f32 partial row of E + 1 sums goes to the workspace (kf_moe_aux_loss_workspace_bytes, 16-byte aligned, no
+ *                   initialisation); a second kernel (one block) adds the partial rows in block order inside 16 contiguous slices, the
+ *                   slices in order, and writes the scalars: bitwise reproducible.
+ *     aux_loss_bwd  one pass over logits, EVERY element of dlogits written:
+ *                   dlogits[t, e] = dloss p_e (a_e - sum_u a_u p_u + z_t), a_e = balance_coef E c_e / (T^2 k), z_t = z_coef 2 lse_t / T;
+ *                   dloss is one f32 read from the DEVICE.
+ * dtype is KF_F32, KF_BF16 or KF_F16 for logits, gate, dgate and dlogits. Rows have leading dimensions in elements (>= their extent) and
+ * 64-bit row offsets; columns beyond the extent are never read into a result or written. Bases need the alignment of an element only
+ * (ids and offsets 8 bytes, loss / parts / dloss 4): with logits (and dlogits) 16-byte aligned and their leading dimensions multiples of
+ * 16 / sizeof(element) a row moves in 16-byte packs, otherwise the same lanes move the same elements one by one with the same arithmetic:
+ * the same bits. Nothing synchronises, allocates or reads an extent back: every entry can be captured with kf_graph_*. No operand may
+ * alias another. Profile labels moe_router_fwd, moe_router_bwd, moe_aux_fwd, moe_aux_fold, moe_aux_bwd.
+ * Every argument is checked before any device call, with the entry's name in kf_last_error(): KF_ERR_INVALID for a dtype outside the
+ * three, T < 0, E < 1, k < 1, T E or T k beyond int64, score or normalize outside {0, 1}, null or misaligned pointers, a leading
+ * dimension below its extent, a workspace that is missing, too small or not 16-byte aligned; KF_ERR_UNSUPPORTED for E > 1024 or
+ * k > min(E, 64). T == 0 is KF_OK without a launch (nothing is written).
+ */
+enum { KF_MOE_SCORE_SOFTMAX = 0, KF_MOE_SCORE_SIGMOID = 1 };
+int kf_moe_router_fwd(int dtype, int64_t T, int64_t E, int64_t k, int score, int normalize, const void *logits, int64_t ldl,
+                      int64_t *ids /* [T, k] */, void *gate, int64_t ldg, void *stream);
+int kf_moe_router_bwd(int dtype, int64_t T, int64_t E, int64_t k, int score, int normalize, const void *logits, int64_t ldl,
+                      const int64_t *ids, const void *dgate, int64_t lddg, void *dlogits, int64_t lddl, void *stream);
+int kf_moe_aux_loss_workspace_bytes(int64_t T, int64_t E, size_t *bytes);
+int kf_moe_aux_loss_fwd(int dtype, int64_t T, int64_t E, int64_t k, const void *logits, int64_t ldl,
+                        const int64_t *offsets /* [E + 1], the plan's */, float balance_coef, float z_coef, float *loss /* [1] */,
+                        float *parts /* [2] = {L_bal, L_z}, or NULL */, void *workspace, size_t workspace_bytes, void *stream);
+int kf_moe_aux_loss_bwd(int dtype, int64_t T, int64_t E, int64_t k, const void *logits, int64_t ldl, const int64_t *offsets,
+                        float balance_coef, float z_coef, const float *dloss /* device, [1] */, void *dlogits, int64_t lddl,
+                        void *stream);
+
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128
 int kf_comm_unique_id(char id[KF_COMM_ID_BYTES]);

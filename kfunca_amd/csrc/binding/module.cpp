@@ -555,6 +555,32 @@ PYBIND11_MODULE(_C, m) {
           "f32 in the order j and rounded once; gate [T, k] (moe_gate) or None (1). Dropped pairs are skipped: neither their row nor their "
           "gate is read. Differentiable in ys and gate in one pass: dys[pair_row[t, j]] = gate[t, j] * dy[t] (zero for a dropped pair), "
           "dgate[t, j] = dy[t] . ys[pair_row[t, j]].");
+    // the router in front of the plan, fused: the top-k choice with its gates, and the auxiliary losses
+    m.def("moe_route", [](const Tensor &logits, int64_t k, const std::string &score, bool normalize) {
+        int s = -1;
+        if (score == "softmax") s = KF_MOE_SCORE_SOFTMAX;
+        else if (score == "sigmoid") s = KF_MOE_SCORE_SIGMOID;
+        CHECK_FAIL(s >= 0, "moe_route: ", score, " is not a valid value for score (softmax, sigmoid)");
+        auto out = gpu::moe_route(logits, k, s, normalize);
+        return py::make_tuple(out.first, out.second);
+    }, py::arg("logits"), py::arg("k"), py::arg("score") = "softmax", py::arg("normalize") = true,
+          "moe_route(logits [T, E], k, score='softmax', normalize=True) -> (ids Long [T, k], gate [T, k]) in one launch. ids are the first k "
+          "positions of the stable descending order of each row in the sort's key order (-0.0 below +0.0, NaNs by bit pattern, equal values "
+          "by lower index): logits.topk(k)[1] bit for bit. gate = softmax(logits)[ids], or sigmoid(logits[ids]) with score='sigmoid', in f32 "
+          "with one rounding; normalize=True divides by their sum over j. float, half or bfloat16; E <= 1024, k <= min(E, 64); logits may be "
+          "row-pitched. gate is differentiable in logits (one launch that recomputes the row and writes all of dlogits); ids carries no "
+          "gradient and feeds moe_plan.");
+    m.def("moe_aux_loss", [moe_plan_of](const Tensor &logits, const py::object &plan, double balance_coef, double z_coef, bool return_parts) -> py::object {
+        Tensor parts;
+        Tensor loss = gpu::moe_aux_loss(logits, moe_plan_of("moe_aux_loss", plan), balance_coef, z_coef, return_parts ? &parts : nullptr);
+        if (return_parts) return py::make_tuple(loss, parts);
+        return py::cast(loss);
+    }, py::arg("logits"), py::arg("plan"), py::arg("balance_coef") = 1e-2, py::arg("z_coef") = 0.0, py::arg("return_parts") = false,
+          "moe_aux_loss(logits [T, E], plan, balance_coef=1e-2, z_coef=0.0, return_parts=False) -> Float [1] = balance_coef * L_bal + z_coef * "
+          "L_z with p = softmax(logits): L_bal = E / (T k) * sum_e c_e * mean_t p[t, e], c_e = plan.offsets[e + 1] - plan.offsets[e] read on "
+          "the device and treated as a constant (the Switch / Megatron normalisation, 1 for uniform routing; HF-Mixtral's value is k times "
+          "this); L_z = mean_t logsumexp(logits[t])^2 (ST-MoE). return_parts=True also returns Float [2] = (L_bal, L_z). No atomics: bitwise "
+          "reproducible. Differentiable in logits in one pass; the incoming gradient is read from the device.");
     // the distribution over a dimension (an MoE router, sampling, distillation): one launch each way, the backward from the kept result
     m.def("softmax", &gpu::softmax, py::arg("x"), py::arg("dim") = -1, py::arg("scale") = 1.0f,
           "softmax(x, dim=-1, scale=1.0): exp(scale * x) normalised to sum 1 over dimension dim of a float, half or bfloat16 tensor, in f32 "

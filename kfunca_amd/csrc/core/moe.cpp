@@ -109,7 +109,101 @@ private:
     RowView vys_, vg_;
     bool has_gate_;
 };
+// dlogits from logits, ids and the incoming gradient: the row is recomputed, the gate is not kept
+class MoeRouteGradFunction : public GradFunction {
+public:
+    MoeRouteGradFunction(const Tensor &logits, const Tensor &ids, int64_t k, int score, bool normalize, const RowView &vl)
+        : ids_(ids), k_(k), score_(score), normalize_(normalize), vl_(vl) {
+        inputs = {logits};
+    }
+    std::vector<Tensor> backward(Tensor g) override {
+        const Tensor &l = inputs[0];
+        const int64_t T = l.shape(0), E = l.shape(1);
+        const RowView dg = rows_of(g);
+        Tensor dl = empty({T, E}, l.dtype(), l.device());
+        if (T > 0)
+            DEV_CALL(kf_moe_router_bwd(code(l.dtype()), T, E, k_, score_, normalize_ ? 1 : 0, vl_.t.data_ptr(), vl_.ld, i64(ids_), dg.t.data_ptr(), dg.ld,
+                                       dl.data_ptr(), E, dev::stream(l.device())));
+        return {dl};
+    }
+
+private:
+    Tensor ids_;
+    int64_t k_;
+    int score_;
+    bool normalize_;
+    RowView vl_;
+};
+
+class MoeAuxLossGradFunction : public GradFunction {
+public:
+    MoeAuxLossGradFunction(const Tensor &logits, const MoePlan &plan, float balance_coef, float z_coef, const RowView &vl)
+        : plan_(plan), balance_coef_(balance_coef), z_coef_(z_coef), vl_(vl) {
+        inputs = {logits};
+    }
+    std::vector<Tensor> backward(Tensor g) override {
+        const Tensor &l = inputs[0];
+        Tensor gc = g.dense();
+        CHECK_FAIL(gc.dtype() == ScalarType::Float && gc.numel() == 1, "moe_aux_loss backward: unexpected gradient");
+        Tensor dl = empty({plan_.T, plan_.E}, l.dtype(), l.device());
+        DEV_CALL(kf_moe_aux_loss_bwd(code(l.dtype()), plan_.T, plan_.E, plan_.k, vl_.t.data_ptr(), vl_.ld, i64(plan_.offsets), balance_coef_, z_coef_,
+                                     static_cast<const float *>(gc.data_ptr()), dl.data_ptr(), plan_.E, dev::stream(l.device())));
+        return {dl};
+    }
+
+private:
+    MoePlan plan_;
+    float balance_coef_, z_coef_;
+    RowView vl_;
+};
 } // namespace
+
+std::pair<Tensor, Tensor> moe_route(const Tensor &logits, int64_t k, int score, bool normalize) {
+    CHECK_FAIL(logits.defined() && logits.dim() == 2, "moe_route expects logits [T, E]");
+    CHECK_FAIL(moe_dtype_ok(logits.dtype()), "moe_route supports float, half and bfloat16");
+    CHECK_FAIL(score == KF_MOE_SCORE_SOFTMAX || score == KF_MOE_SCORE_SIGMOID, "moe_route: score must be softmax or sigmoid");
+    const int64_t T = logits.shape(0), E = logits.shape(1);
+    CHECK_FAIL(E >= 1 && E <= 1024, "moe_route: E = ", E, " experts, one wave holds a token's row (1 <= E <= 1024)");
+    CHECK_FAIL(k >= 1 && k <= E && k <= 64, "moe_route: k = ", k, " must lie in [1, min(E, 64)] with E = ", E);
+    const int device = logits.device();
+    Tensor ids = empty({T, k}, ScalarType::Long, device);
+    Tensor gate = empty({T, k}, logits.dtype(), device);
+    const RowView vl = rows_of(logits);
+    if (T > 0)
+        DEV_CALL(kf_moe_router_fwd(code(logits.dtype()), T, E, k, score, normalize ? 1 : 0, vl.t.data_ptr(), vl.ld, static_cast<int64_t *>(ids.data_ptr()),
+                                   gate.data_ptr(), k, dev::stream(device)));
+    if (logits.requires_grad()) {
+        gate.set_requires_grad(true);
+        gate.set_grad_fn(new MoeRouteGradFunction(logits, ids, k, score, normalize, vl));
+    }
+    return {ids, gate};
+}
+
+Tensor moe_aux_loss(const Tensor &logits, const MoePlan &plan, double balance_coef, double z_coef, Tensor *parts) {
+    CHECK_FAIL(logits.defined() && logits.dim() == 2, "moe_aux_loss expects logits [T, E]");
+    CHECK_FAIL(moe_dtype_ok(logits.dtype()), "moe_aux_loss supports float, half and bfloat16");
+    check_plan("moe_aux_loss", plan, logits.device());
+    CHECK_FAIL(logits.shape(0) == plan.T && logits.shape(1) == plan.E, "moe_aux_loss: the plan was built for T = ", plan.T, ", E = ", plan.E, ", logits is [",
+               logits.shape(0), ", ", logits.shape(1), "]");
+    CHECK_FAIL(plan.T >= 1, "moe_aux_loss: no tokens");
+    CHECK_FAIL(plan.E <= 1024 && plan.k <= 64 && plan.k <= plan.E, "moe_aux_loss: E = ", plan.E, ", k = ", plan.k, " (E <= 1024, k <= min(E, 64))");
+    const int device = logits.device();
+    Tensor loss = empty({1}, ScalarType::Float, device);
+    if (parts) *parts = empty({2}, ScalarType::Float, device);
+    const RowView vl = rows_of(logits);
+    size_t need = 0;
+    DEV_CALL(kf_moe_aux_loss_workspace_bytes(plan.T, plan.E, &need));
+    DataPtr scratch;
+    if (need) scratch = DeviceAllocator::GetInstance()->allocate(need, device);
+    DEV_CALL(kf_moe_aux_loss_fwd(code(logits.dtype()), plan.T, plan.E, plan.k, vl.t.data_ptr(), vl.ld, i64(plan.offsets), (float)balance_coef, (float)z_coef,
+                                 static_cast<float *>(loss.data_ptr()), parts ? static_cast<float *>(parts->data_ptr()) : nullptr, scratch.get(), need,
+                                 dev::stream(device)));
+    if (logits.requires_grad()) {
+        loss.set_requires_grad(true);
+        loss.set_grad_fn(new MoeAuxLossGradFunction(logits, plan, (float)balance_coef, (float)z_coef, vl));
+    }
+    return loss;
+}
 
 MoePlan moe_plan(const Tensor &ids, int64_t num_experts) {
     CHECK_FAIL(ids.defined() && ids.dtype() == ScalarType::Long && ids.dim() == 2, "moe_plan expects ids of type Long and shape [T, k] (the indices of a topk)");

@@ -6,6 +6,7 @@
 #pragma once
 
 #include <cstdint>
+#include <utility>
 
 #include "tensor.h"
 
@@ -35,5 +36,19 @@ Tensor moe_dispatch(const Tensor &x, const MoePlan &plan);
 // pairs are skipped (neither their row nor their gate is read). Differentiable in ys and gate through one pass of kf_moe_combine_bwd:
 // dys[pair_row[t, j]] = gate[t, j] dy[t] (zero for a dropped pair), dgate[t, j] = dy[t] . ys[pair_row[t, j]].
 Tensor moe_combine(const Tensor &ys, const MoePlan &plan, const Tensor &gate = Tensor());
+
+// The router in front of the plan, fused (kf_moe_router_*, kf_moe_aux_loss_*; no reference counterpart), so that the layer reads
+//     logits = x @ router; ids, gate = moe_route(logits, k); plan = moe_plan(ids, E); aux = moe_aux_loss(logits, plan, ...)
+//
+// logits [T, E] (contiguous or row-pitched, read in place; float, half or bfloat16; E <= 1024, 1 <= k <= min(E, 64)). ids Long [T, k]:
+// the first k positions of the stable descending order of each row in the sort's key order - logits.topk(k)[1] bit for bit. gate [T, k]:
+// softmax(logits)[ids] (score 0) or sigmoid(logits[ids]) (score 1), divided by their sum over j when normalize. gate is differentiable
+// in logits (one launch, every element of dlogits written, the row recomputed); ids carries no gradient.
+std::pair<Tensor, Tensor> moe_route(const Tensor &logits, int64_t k, int score = 0, bool normalize = true);
+
+// Float [1]: balance_coef L_bal + z_coef L_z with p = softmax(logits), L_bal = E / (T k) sum_e c_e mean_t p[t, e] (c_e the plan's live
+// pairs of expert e, read on the device, a constant; 1 for uniform routing, HF-Mixtral's value is k times this) and L_z = mean_t lse_t^2.
+// parts, when given, receives Float [2] = {L_bal, L_z} (no gradient). Differentiable in logits: the gradient is read from the device.
+Tensor moe_aux_loss(const Tensor &logits, const MoePlan &plan, double balance_coef = 1e-2, double z_coef = 0.0, Tensor *parts = nullptr);
 
 } // namespace gpu

@@ -55,6 +55,7 @@ EXPORTS = [
     "kf_qk_norm_rope_fwd", "kf_qk_norm_rope_bwd_workspace_bytes", "kf_qk_norm_rope_bwd",
     "kf_segment_offsets", "kf_gemm_segmented_workspace_bytes", "kf_gemm_segmented", "kf_gemm_segmented_wgrad",
     "kf_moe_plan_workspace_bytes", "kf_moe_plan", "kf_moe_gate_fwd", "kf_moe_gate_bwd", "kf_moe_dispatch", "kf_moe_combine", "kf_moe_combine_bwd",
+    "kf_moe_router_fwd", "kf_moe_router_bwd", "kf_moe_aux_loss_workspace_bytes", "kf_moe_aux_loss_fwd", "kf_moe_aux_loss_bwd",
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
     "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa",
@@ -231,6 +232,11 @@ def lib():
         _lib.kf_moe_dispatch.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, vp, i64, vp]
         _lib.kf_moe_combine.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp]
         _lib.kf_moe_combine_bwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+        _lib.kf_moe_router_fwd.argtypes = [C.c_int, i64, i64, i64, C.c_int, C.c_int, vp, i64, vp, vp, i64, vp]
+        _lib.kf_moe_router_bwd.argtypes = [C.c_int, i64, i64, i64, C.c_int, C.c_int, vp, i64, vp, vp, i64, vp, i64, vp]
+        _lib.kf_moe_aux_loss_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
+        _lib.kf_moe_aux_loss_fwd.argtypes = [C.c_int, i64, i64, i64, vp, i64, vp, C.c_float, C.c_float, vp, vp, vp, sz, vp]
+        _lib.kf_moe_aux_loss_bwd.argtypes = [C.c_int, i64, i64, i64, vp, i64, vp, C.c_float, C.c_float, vp, vp, i64, vp]
         _lib.kf_comm_unique_id.argtypes = [C.c_char_p]
         _lib.kf_comm_init.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int, C.c_int]
         _lib.kf_comm_destroy.argtypes = [vp]
@@ -888,6 +894,37 @@ def moe_combine_bwd(dtype, T, k, cols, pair_row, n_valid, gate, ldg, ys, ldys, d
     """kf_moe_combine_bwd: dys[pair_row[t, j], :] = gate[t, j] dy[t, :] (+0 for a dropped pair) and dgate[t, j] = dy[t, :] . ys[row, :], in
     one pass; dgate None skips the dot products (ys may then be None)."""
     check(lib().kf_moe_combine_bwd(dtype, T, k, cols, pair_row, n_valid, gate, ldg, ys, ldys, dy, lddy, dys, lddys, dgate, lddg, stream))
+
+
+MOE_SCORE_SOFTMAX, MOE_SCORE_SIGMOID = range(2)
+
+
+def moe_router_fwd(dtype, T, E, k, score, normalize, logits, ldl, ids, gate, ldg, stream=None):
+    """kf_moe_router_fwd: ids [T, k] (int64) = the first k positions of the stable descending order of each row of logits [T, E] in the
+    sort's key order, gate [T, k] = softmax(logits)[ids] (score MOE_SCORE_SOFTMAX) or sigmoid(logits[ids]), over their sum when normalize."""
+    check(lib().kf_moe_router_fwd(dtype, T, E, k, int(score), int(normalize), logits, ldl, ids, gate, ldg, stream))
+
+
+def moe_router_bwd(dtype, T, E, k, score, normalize, logits, ldl, ids, dgate, lddg, dlogits, lddl, stream=None):
+    """kf_moe_router_bwd: dlogits [T, E], every element written, from logits, ids and dgate (the row is recomputed)."""
+    check(lib().kf_moe_router_bwd(dtype, T, E, k, int(score), int(normalize), logits, ldl, ids, dgate, lddg, dlogits, lddl, stream))
+
+
+def moe_aux_loss_workspace_bytes(T, E) -> int:
+    """Bytes of scratch kf_moe_aux_loss_fwd needs (one f32 partial row of E + 1 sums per block); 16-byte alignment, no initialisation."""
+    need = C.c_size_t(0)
+    check(lib().kf_moe_aux_loss_workspace_bytes(T, E, C.byref(need)))
+    return need.value
+
+
+def moe_aux_loss_fwd(dtype, T, E, k, logits, ldl, offsets, balance_coef, z_coef, loss, parts, workspace, workspace_bytes, stream=None):
+    """kf_moe_aux_loss_fwd: loss[0] = balance_coef L_bal + z_coef L_z of softmax(logits) and the plan's offsets; parts (or None) = (L_bal, L_z)."""
+    check(lib().kf_moe_aux_loss_fwd(dtype, T, E, k, logits, ldl, offsets, balance_coef, z_coef, loss, parts, workspace, workspace_bytes, stream))
+
+
+def moe_aux_loss_bwd(dtype, T, E, k, logits, ldl, offsets, balance_coef, z_coef, dloss, dlogits, lddl, stream=None):
+    """kf_moe_aux_loss_bwd: dlogits [T, E], every element written, in one pass; dloss is one f32 on the device."""
+    check(lib().kf_moe_aux_loss_bwd(dtype, T, E, k, logits, ldl, offsets, balance_coef, z_coef, dloss, dlogits, lddl, stream))
 
 
 def device_sync():
