@@ -650,6 +650,57 @@ int kf_attn_doc_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, in
                     const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The four masks above with two modifiers of the SCORES: logit soft-capping (Gemma-2, Grok) and attention sinks (gpt-oss, after
+ * StreamingLLM). One descriptor-based trio; the mask is a kf_attn_mask, its visibility vis[b, m, n] that of the chosen kind, unchanged.
+ *     x[m, n] = scale <q[b,h,m,:], k[b,h/G,n,:]>
+ *     s[m, n] = softcap > 0 ? softcap tanh(x / softcap) : x                      for visible n
+ *     Z[m]    = sum_n exp s[m, n]  +  (sink ? exp sink[h] : 0)
+ *     o[m]    = sum_n exp(s[m, n]) v[n] / Z[m],      lse[m] = log Z[m]           (natural log, f32)
+ * softcap: a host float, 0 = off; negative or not finite is KF_ERR_INVALID. sink: f32 [Hq] on the device, or NULL; the sink logit is
+ * raw, neither scaled nor capped, joins the denominator and owns no value row. Backward, with P = exp(s - lse), delta = rowsum(dO o O)
+ * and t = tanh(x / softcap):
+ *     dS = P o (dP - delta) o (1 - t^2)   (the last factor only with softcap);  dq = scale dS K, dk = scale dS^T Q, dv = P^T dO
+ *     dsink[h] = - sum_{b, m < Sq} exp(sink[h] - lse[b,h,m]) delta[b,h,m]       (f32 [Hq]; required exactly when sink is given)
+ * kf_attn_mask: kind is one of KF_ATTN_MASK_*; kv_len serves every kind; prefix_len belongs to PREFIX, window_left / window_right to
+ * WINDOW, doc_start / doc_end / causal to DOC (Sq must equal Skv), each with the meaning and the checks of its family's entries. A
+ * field of another kind must hold its neutral value - NULL, (-1, -1), 0 - or the call is KF_ERR_INVALID, as is an unknown kind or a
+ * NULL mask. Everything not said here is kf_attn_full_*'s contract with this entry's name in kf_last_error(): operands, grouped K/V
+ * heads, the all-or-none layout rule, the argument checks before any device call, zero B, Hq or Sq (KF_OK without a launch; dsink is
+ * not written then), K and V rows at n >= len_b never read, capturability. The workspace is delta, as kf_attn_full_bwd's.
+ * A row that sees no key: without a sink o = 0 (zero bits), lse = -inf; with one o = 0 (zero bits), lse = sink[h] (the stored value),
+ * dq = 0 and a zero term in dsink. The sink is folded into the forward epilogue against max(running maximum, sink), so no sink
+ * overflows: sink = +100 gives o ~ 0 and lse ~ 100, a sink too small to move the denominator gives the bits of the call without one,
+ * and sink = -inf is "no sink" exactly. No atomics anywhere, dsink included (attn_sink_grad: one workgroup per head, a fixed-order
+ * sum over (b, m)): every result is bitwise reproducible.
+ * Kernels: with softcap = 0 and sink = NULL the entries of the chosen family run - their kernels, their profile labels, their bits.
+ * With softcap > 0 the same kernels compiled with the cap (tanh from v_exp_f32 and v_rcp_f32 after the score MFMAs, the factor
+ * 1 - t^2 in the backward tile bodies): labels attn_<mask>_cap_fwd_mfma_d64 / _d128, attn_<mask>_cap_bwd_dq_mfma_*,
+ * attn_<mask>_cap_bwd_dkv_mfma_*, attn_<mask>_cap_*_generic, <mask> in full / prefix / window / doc (the windows (-1, -1) and (-1, 0)
+ * are full and prefix, as in kf_attn_window_*). A sink alone keeps the family's labels (its forward is the family's kernel compiled
+ * with the sink epilogue, its backward the family's own); attn_sink_grad follows every backward with a sink.
+ */
+enum { KF_ATTN_MASK_FULL = 0, KF_ATTN_MASK_PREFIX = 1, KF_ATTN_MASK_WINDOW = 2, KF_ATTN_MASK_DOC = 3 };
+typedef struct kf_attn_mask {
+    int kind;                           /* KF_ATTN_MASK_* */
+    const int64_t *kv_len;              /* every kind: int64 [B] on the device, or NULL */
+    const int64_t *prefix_len;          /* PREFIX: int64 [B] on the device, or NULL */
+    int64_t window_left, window_right;  /* WINDOW: key counts >= 0 or -1 (unbounded); every other kind: -1, -1 */
+    const int32_t *doc_start, *doc_end; /* DOC: int32 [B, S] on the device (kf_attn_doc_table) */
+    int causal;                         /* DOC: 0 or 1 */
+} kf_attn_mask;
+int kf_attn_ext_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                    const kf_attn_mask *mask, float softcap, const float *sink, const void *q, const kf_attn_layout *lq,
+                    const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, void *o,
+                    const kf_attn_layout *lo, float *lse, void *stream);
+int kf_attn_ext_bwd_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, size_t *bytes);
+int kf_attn_ext_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
+                    const kf_attn_mask *mask, float softcap, const float *sink, const void *q, const kf_attn_layout *lq,
+                    const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, const void *o,
+                    const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
+                    const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
+                    float *dsink, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- rotary position embeddings (no reference counterpart: the position signal between the QKV projection and attention) ---- */
 /*
  * x, y: [B, H, S, D] addressed by kf_attn_layout element strides of B, H, S; D is contiguous; dtype in {KF_F32, KF_BF16, KF_F16};

@@ -431,12 +431,26 @@ PYBIND11_MODULE(_C, m) {
         if (!py::isinstance<gpu::DocMask>(d)) throw py::value_error(std::string(op) + ": doc_mask is a DocMask (doc_mask(cu_doclens, S)) or None");
         return d.cast<const gpu::DocMask *>();
     };
-    m.def("attention", [opt, win, doc](const Tensor &q, const Tensor &k, const Tensor &v, py::object kv_len, bool causal, py::object prefix_len, py::object window,
-                                       py::object doc_mask) {
+    // softcap = a positive float, sinks = a Float tensor [Hq]: the modifiers of the scores; both None: no modifier, the calls as they were
+    auto mod = [opt](const char *op, const py::object &softcap, const py::object &sinks, gpu::AttentionModifiers &out) -> const gpu::AttentionModifiers * {
+        if (softcap.is_none() && sinks.is_none()) return nullptr;
+        if (!softcap.is_none()) {
+            if (!py::isinstance<py::float_>(softcap) && !py::isinstance<py::int_>(softcap))
+                throw py::value_error(std::string(op) + ": softcap is a positive float or None");
+            out.has_softcap = true;
+            out.softcap = softcap.cast<double>();
+        }
+        out.sinks = opt(sinks);
+        return &out;
+    };
+    m.def("attention", [opt, win, doc, mod](const Tensor &q, const Tensor &k, const Tensor &v, py::object kv_len, bool causal, py::object prefix_len,
+                                            py::object window, py::object doc_mask, py::object softcap, py::object sinks) {
         gpu::AttentionWindow w;
-        return gpu::attention(q, k, v, opt(kv_len), causal, opt(prefix_len), win("attention", window, w), doc("attention", doc_mask));
+        gpu::AttentionModifiers mo;
+        return gpu::attention(q, k, v, opt(kv_len), causal, opt(prefix_len), win("attention", window, w), doc("attention", doc_mask),
+                              mod("attention", softcap, sinks, mo));
     }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kv_len") = py::none(), py::arg("causal") = false, py::arg("prefix_len") = py::none(),
-          py::arg("window") = py::none(), py::arg("doc_mask") = py::none(),
+          py::arg("window") = py::none(), py::arg("doc_mask") = py::none(), py::arg("softcap") = py::none(), py::arg("sinks") = py::none(),
           "Softmax attention of q [B, Hq, Sq, D] over k, v [B, Hkv, Skv, D]. kv_len: Long [B], batch b sees keys n < kv_len[b]. causal=True adds\n"
           "the prefix-LM mask: query m sees key n iff n < kv_len[b] and (n < prefix_len[b] or n <= m), top-left aligned; prefix_len: Long [B]\n"
           "or None (no prefix: causal attention over a padded batch), refused with causal=False. A plain causal call without lengths is\n"
@@ -448,18 +462,25 @@ PYBIND11_MODULE(_C, m) {
           "doc_mask: None, or a DocMask (doc_mask(cu_doclens, S)) for packed rows: each row holds several documents end to end and query m sees\n"
           "key n iff both lie in the same document (causal=True: and n <= m). Self-attention only (Sq = Skv = S of the mask); doc_mask together\n"
           "with kv_len, prefix_len or window is refused, and so is a mask built for another B, S or device. A token in no document gives a\n"
-          "zero row.");
-    m.def("attention_qkv", [opt, win, doc](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object kv_len, bool causal,
-                                           py::object prefix_len, py::object window, py::object doc_mask) {
+          "zero row.\n"
+          "softcap: None, or a positive finite float: every visible score x = q.k / sqrt(D) becomes softcap * tanh(x / softcap) (logit\n"
+          "soft-capping); zero, negative and non-finite values are refused. sinks: None, or a Float tensor [Hq] on q's device (attention\n"
+          "sinks): exp(sinks[h]) joins the softmax denominator of every query of head h - a raw logit, neither scaled nor capped - and owns\n"
+          "no value row; it is a differentiable input and receives a Float [Hq] gradient. Both compose with every mask above.");
+    m.def("attention_qkv", [opt, win, doc, mod](const Tensor &qkv, int64_t B, int64_t S, int64_t H, py::object kv_heads, py::object kv_len, bool causal,
+                                                py::object prefix_len, py::object window, py::object doc_mask, py::object softcap, py::object sinks) {
         gpu::AttentionWindow w;
+        gpu::AttentionModifiers mo;
         return gpu::attention_qkv(qkv, B, S, H, kv_heads.is_none() ? -1 : kv_heads.cast<int64_t>(), opt(kv_len), causal, opt(prefix_len),
-                                  win("attention_qkv", window, w), doc("attention_qkv", doc_mask));
+                                  win("attention_qkv", window, w), doc("attention_qkv", doc_mask), mod("attention_qkv", softcap, sinks, mo));
     }, py::arg("qkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("kv_heads") = py::none(), py::arg("kv_len") = py::none(),
           py::arg("causal") = false, py::arg("prefix_len") = py::none(), py::arg("window") = py::none(), py::arg("doc_mask") = py::none(),
+          py::arg("softcap") = py::none(), py::arg("sinks") = py::none(),
           "attention on the packed projection [B*S, (H + 2*kv_heads)*D] (columns q | k | v), read in place; the result is [B*S, H*D]. kv_len,\n"
           "causal and prefix_len as in attention (Sq = Skv = S). A plain causal call without lengths is faster through causal_attention_qkv.\n"
           "window: as in attention.\n"
-          "doc_mask: as in attention (a DocMask built for this B and S).");
+          "doc_mask: as in attention (a DocMask built for this B and S).\n"
+          "softcap, sinks: as in attention (sinks is Float [H]).");
     // rotary position embeddings: f64-accurate tables, and the rotation of q and k in place in the packed projection (one launch each way)
     m.def("rope_table", [](int64_t max_positions, int64_t rotary_dim, double base, int device) {
         auto [c, sn] = gpu::rope_table(max_positions, rotary_dim, base, device);

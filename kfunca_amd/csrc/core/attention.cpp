@@ -36,6 +36,10 @@ struct Lens {
     int64_t wl = -1, wr = -1;
     Tensor doc_start, doc_end;
     bool doc_causal = false;
+    // the score modifiers of attention / attention_qkv (kf_attn_ext_*): the cap (0: off) and the sinks, Float [Hq] (undefined: none)
+    float softcap = 0.f;
+    Tensor sinks;
+    bool modified() const { return softcap > 0.f || sinks.defined(); }
 };
 
 // One call as the C ABI takes it: the sizes handed down (padded ones where the host pads), the scale of the REAL head size, and the
@@ -51,10 +55,38 @@ struct Call {
     int64_t wl, wr;
     const int32_t *doc_start, *doc_end;
     int doc_causal;
+    // the score modifiers (full-like families only): with either one the call goes to kf_attn_ext_*, without them to the family's entries
+    float softcap = 0.f;
+    const float *sink = nullptr;
+    bool modified() const { return softcap > 0.f || sink; }
 };
+
+// the mask of a full-like family as kf_attn_ext_* takes it
+kf_attn_mask ext_mask(const Call &c) {
+    kf_attn_mask m{KF_ATTN_MASK_FULL, c.kv_len, nullptr, -1, -1, nullptr, nullptr, 0};
+    if (c.family == Family::Prefix) {
+        m.kind = KF_ATTN_MASK_PREFIX;
+        m.prefix_len = c.prefix_len;
+    } else if (c.family == Family::Window) {
+        m.kind = KF_ATTN_MASK_WINDOW;
+        m.window_left = c.wl;
+        m.window_right = c.wr;
+    } else if (c.family == Family::Doc) {
+        m.kind = KF_ATTN_MASK_DOC;
+        m.doc_start = c.doc_start;
+        m.doc_end = c.doc_end;
+        m.causal = c.doc_causal;
+    }
+    return m;
+}
 
 void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o, float *lse) {
     void *st = dev::stream(c.device);
+    if (c.modified()) {
+        const kf_attn_mask m = ext_mask(c);
+        DEV_CALL(kf_attn_ext_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, &m, c.softcap, c.sink, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        return;
+    }
     switch (c.family) {
     case Family::CausalMha:
         if (c.lx) DEV_CALL(kf_attn_fwd_strided(c.dt, c.B, c.Hq, c.Sq, c.Skv, c.D, c.scale, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
@@ -81,8 +113,14 @@ void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o
 }
 
 void run_bwd(const Call &c, const void *q, const void *k, const void *v, const void *o, const float *lse, const void *go, void *dq, void *dk, void *dv,
-             void *ws, size_t bytes) {
+             void *ws, size_t bytes, float *dsink = nullptr) {
     void *st = dev::stream(c.device);
+    if (c.modified()) { // (the workspace is kf_attn_full_bwd_workspace_bytes': the two size queries agree)
+        const kf_attn_mask m = ext_mask(c);
+        DEV_CALL(kf_attn_ext_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, &m, c.softcap, c.sink, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq,
+                                 c.lx, dk, c.lx, dv, c.lx, dsink, ws, bytes, st));
+        return;
+    }
     switch (c.family) {
     case Family::CausalMha:
         if (c.lx)
@@ -176,7 +214,20 @@ Tensor check_len(const Tensor &kv_len, int64_t B, int device, const char *name =
     return kv_len.dense();
 }
 Lens check_lens(const Lens &l, int64_t B, int device) {
-    return {check_len(l.kv, B, device), check_len(l.prefix, B, device, "prefix_len"), l.wl, l.wr, l.doc_start, l.doc_end, l.doc_causal};
+    return {check_len(l.kv, B, device), check_len(l.prefix, B, device, "prefix_len"), l.wl, l.wr, l.doc_start, l.doc_end, l.doc_causal, l.softcap, l.sinks};
+}
+// the sinks of attention / attention_qkv: Float [Hq], dense, on the operands' device (the tensor itself is kept: it receives the gradient)
+void check_modifiers(const char *op, const Lens &l, int64_t Hq, int device) {
+    if (!l.sinks.defined()) return;
+    CHECK_FAIL(l.sinks.dtype() == ScalarType::Float, op, ": sinks must be of type Float");
+    CHECK_FAIL(l.sinks.dim() == 1 && l.sinks.shape(0) == Hq && l.sinks.is_dense(), op, ": sinks must be a dense tensor of shape [Hq] = [", Hq, "]");
+    CHECK_FAIL(l.sinks.device() == device, op, ": sinks must be on the operands' device");
+}
+const float *sink_ptr(const Tensor &t) { return t.defined() ? static_cast<const float *>(t.data_ptr()) : nullptr; }
+Call with_modifiers(Call c, const Lens &len) {
+    c.softcap = len.softcap;
+    c.sink = sink_ptr(len.sinks);
+    return c;
 }
 const int64_t *len_ptr(const Tensor &kv_len) { return kv_len.defined() ? static_cast<const int64_t *>(kv_len.data_ptr()) : nullptr; }
 const int32_t *tab_ptr(const Tensor &t) { return t.defined() ? static_cast<const int32_t *>(t.data_ptr()) : nullptr; }
@@ -220,8 +271,9 @@ Tensor unpad(const Tensor &t, int64_t rows, int64_t cols) {
 
 Call contiguous_call(Family f, const Tensor &q, const Tensor &k, const PadPlan &pp, const Lens &len) {
     const bool padded = pp.Sq != q.shape(2) || pp.Skv != k.shape(2) || pp.D != q.shape(3);
-    return {f, code(q.dtype()), q.device(), q.shape(0), q.shape(1), k.shape(1), pp.Sq, pp.Skv, pp.D, 1.0f / std::sqrt((float)q.shape(3)),
-            len_ptr(len.kv), len_ptr(len.prefix), nullptr, nullptr, padded, len.wl, len.wr, tab_ptr(len.doc_start), tab_ptr(len.doc_end), len.doc_causal};
+    return with_modifiers({f, code(q.dtype()), q.device(), q.shape(0), q.shape(1), k.shape(1), pp.Sq, pp.Skv, pp.D, 1.0f / std::sqrt((float)q.shape(3)),
+                           len_ptr(len.kv), len_ptr(len.prefix), nullptr, nullptr, padded, len.wl, len.wr, tab_ptr(len.doc_start), tab_ptr(len.doc_end),
+                           len.doc_causal}, len);
 }
 
 std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len) {
@@ -238,8 +290,10 @@ std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Te
     return {unpad(outp, Sq, D), unpad(lsep, Sq, 0)};
 }
 
+// dsink: with sinks, where their gradient goes (Float [Hq]; zeros when there is no query to sum over)
 std::tuple<Tensor, Tensor, Tensor> attention_backward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len, const Tensor &out,
-                                                      const Tensor &lse, const Tensor &grad_out) {
+                                                      const Tensor &lse, const Tensor &grad_out, Tensor *dsink = nullptr) {
+    if (dsink) *dsink = zeros(len.sinks.sizes(), ScalarType::Float, q.device());
     if (f == Family::CausalMha) check_operands(f, q, k, v); // causal_attention_bwd is an operator of its own (ops.h)
     CHECK_FAIL(grad_out.sizes() == q.sizes() && grad_out.dtype() == q.dtype(), full_like(f) ? "attention: the gradient does not match the output" : "");
     const int64_t Sq = q.shape(2), Skv = k.shape(2), D = q.shape(3);
@@ -255,7 +309,7 @@ std::tuple<Tensor, Tensor, Tensor> attention_backward(Family f, const Tensor &q,
     size_t bytes = 0;
     DataPtr scratch = bwd_scratch(c, bytes);
     run_bwd(c, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), static_cast<const float *>(lp.data_ptr()), gp.data_ptr(), dqp.data_ptr(),
-            dkp.data_ptr(), dvp.data_ptr(), scratch.get(), bytes);
+            dkp.data_ptr(), dvp.data_ptr(), scratch.get(), bytes, dsink ? static_cast<float *>(dsink->data_ptr()) : nullptr);
     return {unpad(dqp, Sq, D), unpad(dkp, Skv, D), unpad(dvp, Skv, D)};
 }
 
@@ -264,9 +318,12 @@ public:
     AttentionGradFunction(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len, const Tensor &out, const Tensor &lse)
         : family_(f), len_(len), out_(out), lse_(lse) {
         inputs = {q, k, v};
+        if (len.sinks.defined()) inputs.push_back(len.sinks); // a fourth differentiable input
     }
     std::vector<Tensor> backward(Tensor g) override {
-        auto [dq, dk, dv] = attention_backward(family_, inputs[0], inputs[1], inputs[2], len_, out_, lse_, g);
+        Tensor dsink;
+        auto [dq, dk, dv] = attention_backward(family_, inputs[0], inputs[1], inputs[2], len_, out_, lse_, g, len_.sinks.defined() ? &dsink : nullptr);
+        if (len_.sinks.defined()) return {dq, dk, dv, dsink};
         return {dq, dk, dv};
     }
 
@@ -279,9 +336,10 @@ private:
 // kv_len and prefix_len are checked and made dense once; the backward keeps those tensors
 Tensor contiguous_attention(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &lens) {
     check_operands(f, q, k, v);
-    const Lens len = check_lens(lens, q.shape(0), q.device());
+    Lens len = check_lens(lens, q.shape(0), q.device());
+    check_modifiers("attention", len, q.shape(1), q.device());
     auto [out, lse] = attention_forward(f, q, k, v, len);
-    out.set_requires_grad(q.requires_grad() || k.requires_grad() || v.requires_grad());
+    out.set_requires_grad(q.requires_grad() || k.requires_grad() || v.requires_grad() || (len.sinks.defined() && len.sinks.requires_grad()));
     if (out.requires_grad()) out.set_grad_fn(new AttentionGradFunction(f, q, k, v, len, out, lse));
     return out;
 }
@@ -294,8 +352,8 @@ PackedLay packed_layouts(int64_t S, int64_t H, int64_t Hkv, int64_t D) {
 }
 // family CausalMha is Hkv = H here: K at column H D, V at 2 H D (the strided entries); otherwise K at H D, V at (H + Hkv) D
 Call packed_call(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D, const PackedLay &L, const Lens &len) {
-    return {f, code(qkv.dtype()), qkv.device(), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), len_ptr(len.kv), len_ptr(len.prefix), &L.qkv, &L.flat, false,
-            len.wl, len.wr, tab_ptr(len.doc_start), tab_ptr(len.doc_end), len.doc_causal};
+    return with_modifiers({f, code(qkv.dtype()), qkv.device(), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), len_ptr(len.kv), len_ptr(len.prefix), &L.qkv,
+                           &L.flat, false, len.wl, len.wr, tab_ptr(len.doc_start), tab_ptr(len.doc_end), len.doc_causal}, len);
 }
 
 class PackedAttentionGradFunction : public GradFunction {
@@ -304,6 +362,7 @@ public:
                                 int64_t Hkv)
         : family_(f), len_(len), out_(out), lse_(lse), B_(B), S_(S), H_(H), Hkv_(Hkv) {
         inputs = {qkv};
+        if (len.sinks.defined()) inputs.push_back(len.sinks);
     }
     std::vector<Tensor> backward(Tensor g) override { // one packed gradient; dk, dv summed over each group
         const Tensor &qkv = inputs[0];
@@ -316,8 +375,11 @@ public:
         char *gp = static_cast<char *>(dqkv.data_ptr());
         size_t bytes = 0;
         DataPtr scratch = bwd_scratch(c, bytes);
+        Tensor dsink;
+        if (len_.sinks.defined()) dsink = zeros(len_.sinks.sizes(), ScalarType::Float, qkv.device());
         run_bwd(c, p, p + k_at, p + v_at, out_.data_ptr(), static_cast<const float *>(lse_.data_ptr()), gc.data_ptr(), gp, gp + k_at, gp + v_at,
-                scratch.get(), bytes);
+                scratch.get(), bytes, dsink.defined() ? static_cast<float *>(dsink.data_ptr()) : nullptr);
+        if (dsink.defined()) return {dqkv, dsink};
         return {dqkv};
     }
 
@@ -351,14 +413,15 @@ Tensor packed_attention(Family f, const Tensor &qkv, int64_t B, int64_t S, int64
         Tensor a = contiguous_attention(f, heads[0], heads[1], heads[2], lens);
         return a.permute({0, 2, 1, 3}).dense().view({B * S, d});
     }
-    const Lens len = check_lens(lens, B, qkv.device());
+    Lens len = check_lens(lens, B, qkv.device());
+    check_modifiers("attention_qkv", len, H, qkv.device());
     const int64_t es = qkv.element_size_in_bytes();
     Tensor out = empty({B * S, d}, qkv.dtype(), qkv.device());
     Tensor lse = empty({B, H, S}, ScalarType::Float, qkv.device());
     const PackedLay L = packed_layouts(S, H, Hkv, D);
     const char *p = static_cast<const char *>(qkv.data_ptr());
     run_fwd(packed_call(f, qkv, B, S, H, Hkv, D, L, len), p, p + d * es, p + (d + dkv) * es, out.data_ptr(), static_cast<float *>(lse.data_ptr()));
-    if (qkv.requires_grad()) {
+    if (qkv.requires_grad() || (len.sinks.defined() && len.sinks.requires_grad())) {
         out.set_requires_grad(true);
         out.set_grad_fn(new PackedAttentionGradFunction(f, qkv, len, out, lse, B, S, H, Hkv));
     }
@@ -410,9 +473,20 @@ static Family masked_family(const char *op, bool causal, const Tensor &prefix_le
     CHECK_FAIL(causal || !prefix_len.defined(), op, ": prefix_len needs causal = true (without the causal mask every key is visible already)");
     return causal ? Family::Prefix : Family::Full;
 }
+// softcap (0: off) and sinks as the operators take them; the cap is refused here with the operator's name, the sinks once Hq is known
+static void set_modifiers(const char *op, Lens &lens, const AttentionModifiers *mods) {
+    if (!mods) return;
+    if (mods->has_softcap) {
+        CHECK_FAIL(mods->softcap > 0.0 && std::isfinite(mods->softcap) && std::isfinite((float)mods->softcap), op, ": softcap must be positive and finite, got ",
+                   mods->softcap);
+        lens.softcap = (float)mods->softcap;
+    }
+    lens.sinks = mods->sinks;
+}
 Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, bool causal, const Tensor &prefix_len,
-                 const AttentionWindow *window, const DocMask *doc_mask) {
+                 const AttentionWindow *window, const DocMask *doc_mask, const AttentionModifiers *mods) {
     Lens lens{kv_len, prefix_len};
+    set_modifiers("attention", lens, mods);
     if (doc_mask) check_operands(Family::Doc, q, k, v); // the shapes the mask is compared with
     const Family f = doc_mask ? doc_family("attention", causal, prefix_len, window, lens, doc_mask, q.shape(0), q.shape(2), k.shape(2), q.device())
                               : masked_family("attention", causal, prefix_len, window, lens);
@@ -445,8 +519,9 @@ Tensor causal_attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, 
     return causal_attention_qkv(qkv, B, S, H);
 }
 Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len, bool causal, const Tensor &prefix_len,
-                     const AttentionWindow *window, const DocMask *doc_mask) {
+                     const AttentionWindow *window, const DocMask *doc_mask, const AttentionModifiers *mods) {
     Lens lens{kv_len, prefix_len};
+    set_modifiers("attention_qkv", lens, mods);
     const Family f = doc_mask ? doc_family("attention_qkv", causal, prefix_len, window, lens, doc_mask, B, S, S, qkv.defined() ? qkv.device() : 0)
                               : masked_family("attention_qkv", causal, prefix_len, window, lens);
     return packed_attention(f, qkv, B, S, H, kv_heads < 0 ? H : kv_heads, lens);

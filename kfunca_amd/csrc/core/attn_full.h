@@ -39,12 +39,24 @@ struct DocMask {
     int64_t B = 0, S = 0;
 };
 DocMask doc_mask(const Tensor &cu_doclens, int64_t S);
+// mods (kf_attn_ext_fwd, kf_attn_ext_bwd): null (the calls above, unchanged: their path and their bits) or the modifiers of the SCORES,
+// which compose with every mask: softcap (has_softcap; positive and finite, else refused) turns each visible score x = q.k / sqrt(D)
+// into softcap tanh(x / softcap) (Gemma-2, Grok); sinks (defined: Float [Hq], dense, on the operands' device, else refused) adds
+// exp(sinks[h]) to the softmax denominator of every query of head h - a raw logit, neither scaled nor capped, that owns no value row
+// (gpt-oss, StreamingLLM). A row that sees no key is a zero row either way. sinks is a fourth differentiable input: when it requires
+// grad it receives dsink[h] = - sum_{b, m} exp(sinks[h] - lse[b,h,m]) rowsum(dO o O)[b,h,m] as a Float [Hq].
+struct AttentionModifiers {
+    bool has_softcap = false;
+    double softcap = 0.0;
+    Tensor sinks;
+};
 Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &kv_len, bool causal = false, const Tensor &prefix_len = Tensor(),
-                 const AttentionWindow *window = nullptr, const DocMask *doc_mask = nullptr);
+                 const AttentionWindow *window = nullptr, const DocMask *doc_mask = nullptr, const AttentionModifiers *mods = nullptr);
 // attention_qkv(qkv, B, S, H, kv_heads, kv_len): the packed projection [B*S, (H + 2*Hkv)*D] (columns q | k | v; kv_heads < 0: Hkv = H)
 // is read in place, the result is [B*S, H*D] and the backward writes one packed gradient - the layouts causal_attention_qkv builds.
-// causal, prefix_len, window, doc_mask: as in attention (Sq = Skv = S).
+// causal, prefix_len, window, doc_mask, mods: as in attention (Sq = Skv = S; sinks is Float [H]).
 Tensor attention_qkv(const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t kv_heads, const Tensor &kv_len, bool causal = false,
-                     const Tensor &prefix_len = Tensor(), const AttentionWindow *window = nullptr, const DocMask *doc_mask = nullptr);
+                     const Tensor &prefix_len = Tensor(), const AttentionWindow *window = nullptr, const DocMask *doc_mask = nullptr,
+                     const AttentionModifiers *mods = nullptr);
 
 } // namespace gpu

@@ -59,7 +59,8 @@ EXPORTS = [
     "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
     "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa",
-    "kf_attn_full_fwd", "kf_attn_full_bwd_workspace_bytes", "kf_attn_full_bwd", "kf_attn_prefix_fwd", "kf_attn_prefix_bwd", "kf_attn_window_fwd", "kf_attn_window_bwd", "kf_attn_doc_table", "kf_attn_doc_fwd", "kf_attn_doc_bwd", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
+    "kf_attn_full_fwd", "kf_attn_full_bwd_workspace_bytes", "kf_attn_full_bwd", "kf_attn_prefix_fwd", "kf_attn_prefix_bwd", "kf_attn_window_fwd", "kf_attn_window_bwd", "kf_attn_doc_table", "kf_attn_doc_fwd", "kf_attn_doc_bwd",
+    "kf_attn_ext_fwd", "kf_attn_ext_bwd_workspace_bytes", "kf_attn_ext_bwd", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
 ]
 
 
@@ -98,6 +99,20 @@ class GemmProblem(C.Structure):
 class AttnLayout(C.Structure):
     """kf_attn_layout: element strides of the batch, head and row dims of one attention operand."""
     _fields_ = [("batch", C.c_int64), ("head", C.c_int64), ("row", C.c_int64)]
+
+
+ATTN_MASK_FULL, ATTN_MASK_PREFIX, ATTN_MASK_WINDOW, ATTN_MASK_DOC = 0, 1, 2, 3
+
+
+class AttnMask(C.Structure):
+    """kf_attn_mask: the mask of kf_attn_ext_*. kind is ATTN_MASK_*; a field of another kind keeps its neutral value (None, -1, 0)."""
+    _fields_ = [("kind", C.c_int), ("kv_len", C.c_void_p), ("prefix_len", C.c_void_p), ("window_left", C.c_int64), ("window_right", C.c_int64),
+                ("doc_start", C.c_void_p), ("doc_end", C.c_void_p), ("causal", C.c_int)]
+
+
+def attn_mask(kind=ATTN_MASK_FULL, kv_len=None, prefix_len=None, window_left=-1, window_right=-1, doc_start=None, doc_end=None, causal=0) -> AttnMask:
+    """An AttnMask with every field the kind does not use at its neutral value (pointers are device addresses or None)."""
+    return AttnMask(kind, kv_len, prefix_len, window_left, window_right, doc_start, doc_end, int(causal))
 
 
 class DeviceProps(C.Structure):
@@ -210,6 +225,11 @@ def lib():
         _lib.kf_attn_doc_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, C.c_int, vp, vp, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
         _lib.kf_attn_doc_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, C.c_int, vp, vp, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp,
                                          vp, lp, vp, lp, vp, lp, vp, sz, vp]
+        mp = C.POINTER(AttnMask)
+        _lib.kf_attn_ext_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, mp, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
+        _lib.kf_attn_ext_bwd_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.POINTER(sz)]
+        _lib.kf_attn_ext_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, mp, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp,
+                                         vp, lp, vp, lp, vp, lp, vp, vp, sz, vp]
         _lib.kf_rope.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, vp, vp, lp, vp, lp, vp]
         _lib.kf_rope_table.argtypes = [C.c_double, i64, i64, vp, vp, vp]
         _lib.kf_glu_fwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp]
@@ -752,6 +772,30 @@ def attn_doc_bwd(dtype, B, Hq, Hkv, S, D, scale, q, k, v, o, lse, d_o, dq, dk, d
     L = _gqa_layouts(layouts, 8)
     check(lib().kf_attn_doc_bwd(dtype, B, Hq, Hkv, S, D, scale, int(causal), kv_len, doc_start, doc_end, q, L[0], k, L[1], v, L[2], o, L[3], lse,
                                 d_o, L[4], dq, L[5], dk, L[6], dv, L[7], workspace, workspace_bytes, stream))
+
+
+def attn_ext_fwd(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, k, v, o, lse=None, mask=None, softcap=0.0, sink=None, layouts=None, stream=None):
+    """Masked attention with score modifiers, forward (kf_attn_ext_fwd): s = softcap tanh(scale q.k / softcap) when softcap > 0, and
+    exp(sink[h]) joins the softmax denominator when sink (device pointer to f32 [Hq]) is given. mask: an AttnMask (attn_mask(...));
+    None passes NULL, which the entry refuses. layouts as attn_full_fwd."""
+    L = _gqa_layouts(layouts, 4)
+    check(lib().kf_attn_ext_fwd(dtype, B, Hq, Hkv, Sq, Skv, D, scale, None if mask is None else C.byref(mask), softcap, sink, q, L[0], k, L[1], v,
+                                L[2], o, L[3], lse, stream))
+
+
+def attn_ext_bwd_workspace_bytes(dtype, B, Hq, Hkv, Sq, Skv, D) -> int:
+    need = C.c_size_t(0)
+    check(lib().kf_attn_ext_bwd_workspace_bytes(dtype, B, Hq, Hkv, Sq, Skv, D, C.byref(need)))
+    return need.value
+
+
+def attn_ext_bwd(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, workspace, workspace_bytes, mask=None, softcap=0.0,
+                 sink=None, dsink=None, layouts=None, stream=None):
+    """Masked attention with score modifiers, backward (kf_attn_ext_bwd). dsink: device pointer to f32 [Hq], required exactly when sink
+    is given. The workspace is attn_ext_bwd_workspace_bytes'; layouts as attn_full_bwd."""
+    L = _gqa_layouts(layouts, 8)
+    check(lib().kf_attn_ext_bwd(dtype, B, Hq, Hkv, Sq, Skv, D, scale, None if mask is None else C.byref(mask), softcap, sink, q, L[0], k, L[1], v,
+                                L[2], o, L[3], lse, d_o, L[4], dq, L[5], dk, L[6], dv, L[7], dsink, workspace, workspace_bytes, stream))
 
 
 def rope(dtype, B, H, S, D, x, lx, y=None, ly=None, cos=None, sin=None, table_rows=None, rotary_dim=None, h_rot=None, positions=None,
