@@ -49,41 +49,19 @@ struct Call {
     int dt, device;
     int64_t B, Hq, Hkv, Sq, Skv, D;
     float scale;
-    const int64_t *kv_len, *prefix_len;
+    kf_attn_mask mask; // the full-like families: the one form of the mask, built once from Family + Lens (call_mask)
     const kf_attn_layout *lx, *lo;
     bool padded;
-    int64_t wl, wr;
-    const int32_t *doc_start, *doc_end;
-    int doc_causal;
     // the score modifiers (full-like families only): with either one the call goes to kf_attn_ext_*, without them to the family's entries
     float softcap = 0.f;
     const float *sink = nullptr;
     bool modified() const { return softcap > 0.f || sink; }
 };
 
-// the mask of a full-like family as kf_attn_ext_* takes it
-kf_attn_mask ext_mask(const Call &c) {
-    kf_attn_mask m{KF_ATTN_MASK_FULL, c.kv_len, nullptr, -1, -1, nullptr, nullptr, 0};
-    if (c.family == Family::Prefix) {
-        m.kind = KF_ATTN_MASK_PREFIX;
-        m.prefix_len = c.prefix_len;
-    } else if (c.family == Family::Window) {
-        m.kind = KF_ATTN_MASK_WINDOW;
-        m.window_left = c.wl;
-        m.window_right = c.wr;
-    } else if (c.family == Family::Doc) {
-        m.kind = KF_ATTN_MASK_DOC;
-        m.doc_start = c.doc_start;
-        m.doc_end = c.doc_end;
-        m.causal = c.doc_causal;
-    }
-    return m;
-}
-
 void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o, float *lse) {
     void *st = dev::stream(c.device);
+    const kf_attn_mask &m = c.mask;
     if (c.modified()) {
-        const kf_attn_mask m = ext_mask(c);
         DEV_CALL(kf_attn_ext_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, &m, c.softcap, c.sink, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
         return;
     }
@@ -97,16 +75,16 @@ void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o
         DEV_CALL(kf_attn_fwd_gqa(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
         break;
     case Family::Full:
-        DEV_CALL(kf_attn_full_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        DEV_CALL(kf_attn_full_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, m.kv_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
         break;
     case Family::Prefix:
-        DEV_CALL(kf_attn_prefix_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.prefix_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        DEV_CALL(kf_attn_prefix_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, m.kv_len, m.prefix_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
         break;
     case Family::Window:
-        DEV_CALL(kf_attn_window_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.wl, c.wr, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
+        DEV_CALL(kf_attn_window_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, m.kv_len, m.window_left, m.window_right, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
         break;
     case Family::Doc:
-        DEV_CALL(kf_attn_doc_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, c.doc_causal, c.kv_len, c.doc_start, c.doc_end, q, c.lx, k, c.lx, v, c.lx, o, c.lo,
+        DEV_CALL(kf_attn_doc_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, m.causal, m.kv_len, m.doc_start, m.doc_end, q, c.lx, k, c.lx, v, c.lx, o, c.lo,
                                  lse, st));
         break;
     }
@@ -115,8 +93,8 @@ void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o
 void run_bwd(const Call &c, const void *q, const void *k, const void *v, const void *o, const float *lse, const void *go, void *dq, void *dk, void *dv,
              void *ws, size_t bytes, float *dsink = nullptr) {
     void *st = dev::stream(c.device);
+    const kf_attn_mask &m = c.mask;
     if (c.modified()) { // (the workspace is kf_attn_full_bwd_workspace_bytes': the two size queries agree)
-        const kf_attn_mask m = ext_mask(c);
         DEV_CALL(kf_attn_ext_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, &m, c.softcap, c.sink, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq,
                                  c.lx, dk, c.lx, dv, c.lx, dsink, ws, bytes, st));
         return;
@@ -134,19 +112,19 @@ void run_bwd(const Call &c, const void *q, const void *k, const void *v, const v
                                  dv, c.lx, ws, bytes, st));
         break;
     case Family::Full:
-        DEV_CALL(kf_attn_full_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq, c.lx,
+        DEV_CALL(kf_attn_full_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, m.kv_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq, c.lx,
                                   dk, c.lx, dv, c.lx, ws, bytes, st));
         break;
     case Family::Prefix:
-        DEV_CALL(kf_attn_prefix_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.prefix_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go,
+        DEV_CALL(kf_attn_prefix_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, m.kv_len, m.prefix_len, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go,
                                     c.lo, dq, c.lx, dk, c.lx, dv, c.lx, ws, bytes, st));
         break;
     case Family::Window:
-        DEV_CALL(kf_attn_window_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, c.kv_len, c.wl, c.wr, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo,
+        DEV_CALL(kf_attn_window_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, m.kv_len, m.window_left, m.window_right, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo,
                                     dq, c.lx, dk, c.lx, dv, c.lx, ws, bytes, st));
         break;
     case Family::Doc:
-        DEV_CALL(kf_attn_doc_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, c.doc_causal, c.kv_len, c.doc_start, c.doc_end, q, c.lx, k, c.lx, v, c.lx, o, c.lo,
+        DEV_CALL(kf_attn_doc_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, m.causal, m.kv_len, m.doc_start, m.doc_end, q, c.lx, k, c.lx, v, c.lx, o, c.lo,
                                  lse, go, c.lo, dq, c.lx, dk, c.lx, dv, c.lx, ws, bytes, st));
         break;
     }
@@ -224,13 +202,26 @@ void check_modifiers(const char *op, const Lens &l, int64_t Hq, int device) {
     CHECK_FAIL(l.sinks.device() == device, op, ": sinks must be on the operands' device");
 }
 const float *sink_ptr(const Tensor &t) { return t.defined() ? static_cast<const float *>(t.data_ptr()) : nullptr; }
-Call with_modifiers(Call c, const Lens &len) {
-    c.softcap = len.softcap;
-    c.sink = sink_ptr(len.sinks);
-    return c;
-}
 const int64_t *len_ptr(const Tensor &kv_len) { return kv_len.defined() ? static_cast<const int64_t *>(kv_len.data_ptr()) : nullptr; }
 const int32_t *tab_ptr(const Tensor &t) { return t.defined() ? static_cast<const int32_t *>(t.data_ptr()) : nullptr; }
+// the mask of a full-like family as the C ABI has it, the fields of another kind neutral (the causal families read none of it)
+kf_attn_mask call_mask(Family f, const Lens &len) {
+    kf_attn_mask m{KF_ATTN_MASK_FULL, len_ptr(len.kv), nullptr, -1, -1, nullptr, nullptr, 0};
+    if (f == Family::Prefix) {
+        m.kind = KF_ATTN_MASK_PREFIX;
+        m.prefix_len = len_ptr(len.prefix);
+    } else if (f == Family::Window) {
+        m.kind = KF_ATTN_MASK_WINDOW;
+        m.window_left = len.wl;
+        m.window_right = len.wr;
+    } else if (f == Family::Doc) {
+        m.kind = KF_ATTN_MASK_DOC;
+        m.doc_start = tab_ptr(len.doc_start);
+        m.doc_end = tab_ptr(len.doc_end);
+        m.causal = len.doc_causal;
+    }
+    return m;
+}
 
 // The extents handed down. The MFMA kernels want D = 64 or 128 (and, f32, whole tiles of 32 rows); everything else takes the generic
 // vector-ALU kernel (two orders of magnitude slower). Zero columns change neither Q K^T nor P V (the softmax scale stays 1 / sqrt(D) of
@@ -271,9 +262,9 @@ Tensor unpad(const Tensor &t, int64_t rows, int64_t cols) {
 
 Call contiguous_call(Family f, const Tensor &q, const Tensor &k, const PadPlan &pp, const Lens &len) {
     const bool padded = pp.Sq != q.shape(2) || pp.Skv != k.shape(2) || pp.D != q.shape(3);
-    return with_modifiers({f, code(q.dtype()), q.device(), q.shape(0), q.shape(1), k.shape(1), pp.Sq, pp.Skv, pp.D, 1.0f / std::sqrt((float)q.shape(3)),
-                           len_ptr(len.kv), len_ptr(len.prefix), nullptr, nullptr, padded, len.wl, len.wr, tab_ptr(len.doc_start), tab_ptr(len.doc_end),
-                           len.doc_causal}, len);
+    return {.family = f, .dt = code(q.dtype()), .device = q.device(), .B = q.shape(0), .Hq = q.shape(1), .Hkv = k.shape(1), .Sq = pp.Sq, .Skv = pp.Skv,
+            .D = pp.D, .scale = 1.0f / std::sqrt((float)q.shape(3)), .mask = call_mask(f, len), .lx = nullptr, .lo = nullptr, .padded = padded,
+            .softcap = len.softcap, .sink = sink_ptr(len.sinks)};
 }
 
 std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len) {
@@ -352,8 +343,9 @@ PackedLay packed_layouts(int64_t S, int64_t H, int64_t Hkv, int64_t D) {
 }
 // family CausalMha is Hkv = H here: K at column H D, V at 2 H D (the strided entries); otherwise K at H D, V at (H + Hkv) D
 Call packed_call(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D, const PackedLay &L, const Lens &len) {
-    return with_modifiers({f, code(qkv.dtype()), qkv.device(), B, H, Hkv, S, S, D, 1.0f / std::sqrt((float)D), len_ptr(len.kv), len_ptr(len.prefix), &L.qkv,
-                           &L.flat, false, len.wl, len.wr, tab_ptr(len.doc_start), tab_ptr(len.doc_end), len.doc_causal}, len);
+    return {.family = f, .dt = code(qkv.dtype()), .device = qkv.device(), .B = B, .Hq = H, .Hkv = Hkv, .Sq = S, .Skv = S, .D = D,
+            .scale = 1.0f / std::sqrt((float)D), .mask = call_mask(f, len), .lx = &L.qkv, .lo = &L.flat, .padded = false,
+            .softcap = len.softcap, .sink = sink_ptr(len.sinks)};
 }
 
 class PackedAttentionGradFunction : public GradFunction {

@@ -2,20 +2,35 @@
 // kf_attn_window_*, kf_attn_doc_*). The kernels and the host path they share with kf_attn_ext_* (attn_ext.hip) are in attn_full_kernels.h.
 #include "attn_full_kernels.h"
 
+int kf::full::plain_fwd(const char *who, const Problem &pr, const MaskPlan &p, const FwdOps &x, void *stream) {
+    return full_fwd<X_NONE>(who, pr, p, Mods{0.f, nullptr}, x, stream);
+}
+int kf::full::plain_bwd(const char *who, const char *size_query, const Problem &pr, const MaskPlan &p, const BwdOps &x, void *stream) {
+    return full_bwd<false>(who, size_query, pr, p, Mods{0.f, nullptr}, x, stream);
+}
+
+// Every entry below: the mask its arguments describe (the fields of the other kinds neutral), the one check of it, the plain path.
+static int family_fwd(const char *who, const Problem &pr, const kf_attn_mask &m, const FwdOps &x, void *stream) {
+    MaskPlan p;
+    int rc = mask_check(who, &m, pr.Sq, pr.Skv, p);
+    return rc != KF_OK ? rc : plain_fwd(who, pr, p, x, stream);
+}
+static int family_bwd(const char *who, const Problem &pr, const kf_attn_mask &m, const BwdOps &x, void *stream) {
+    MaskPlan p;
+    int rc = mask_check(who, &m, pr.Sq, pr.Skv, p);
+    return rc != KF_OK ? rc : plain_bwd(who, "kf_attn_full_bwd_workspace_bytes", pr, p, x, stream);
+}
+
 extern "C" int kf_attn_full_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
                                 const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv,
                                 void *o, const kf_attn_layout *lo, float *lse, void *stream) {
-    return full_fwd("kf_attn_full_fwd", M_FULL, Window{-1, -1}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, stream);
+    return family_fwd("kf_attn_full_fwd", {.dtype = dtype, .B = B, .Hq = Hq, .Hkv = Hkv, .Sq = Sq, .Skv = Skv, .D = D, .scale = scale},
+                      {.kind = KF_ATTN_MASK_FULL, .kv_len = kv_len, .window_left = -1, .window_right = -1},
+                      {.q = q, .lq = lq, .k = k, .lk = lk, .v = v, .lv = lv, .o = o, .lo = lo, .lse = lse}, stream);
 }
 
 extern "C" int kf_attn_full_bwd_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, size_t *bytes) {
-    KF_REQUIRE(bytes, KF_ERR_INVALID, "kf_attn_full_bwd_workspace_bytes: null out pointer");
-    FullArgs a;
-    Plan plan;
-    int rc = full_check("kf_attn_full_bwd_workspace_bytes", dtype, B, Hq, Hkv, Sq, Skv, D, 1.f, nullptr, nullptr, 0, a, plan);
-    if (rc != KF_OK) return rc;
-    *bytes = ws_bytes(B, Hq, Sq);
-    return KF_OK;
+    return ws_query("kf_attn_full_bwd_workspace_bytes", {.dtype = dtype, .B = B, .Hq = Hq, .Hkv = Hkv, .Sq = Sq, .Skv = Skv, .D = D, .scale = 1.f}, bytes);
 }
 
 extern "C" int kf_attn_full_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
@@ -23,14 +38,18 @@ extern "C" int kf_attn_full_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, i
                                 const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o, const kf_attn_layout *ldo, void *dq,
                                 const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv, void *workspace,
                                 size_t workspace_bytes, void *stream) {
-    return full_bwd("kf_attn_full_bwd", M_FULL, Window{-1, -1}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq, dk,
-                    ldk, dv, ldv, workspace, workspace_bytes, stream);
+    return family_bwd("kf_attn_full_bwd", {.dtype = dtype, .B = B, .Hq = Hq, .Hkv = Hkv, .Sq = Sq, .Skv = Skv, .D = D, .scale = scale},
+                      {.kind = KF_ATTN_MASK_FULL, .kv_len = kv_len, .window_left = -1, .window_right = -1},
+                      {.q = q, .lq = lq, .k = k, .lk = lk, .v = v, .lv = lv, .o = o, .lo = lo, .lse = lse, .d_o = d_o, .ldo = ldo, .dq = dq, .ldq = ldq,
+                       .dk = dk, .ldk = ldk, .dv = dv, .ldv = ldv, .workspace = workspace, .workspace_bytes = workspace_bytes}, stream);
 }
 
 extern "C" int kf_attn_prefix_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
                                   const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v,
                                   const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
-    return full_fwd("kf_attn_prefix_fwd", M_PREFIX, Window{-1, -1}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, prefix_len, q, lq, k, lk, v, lv, o, lo, lse, stream);
+    return family_fwd("kf_attn_prefix_fwd", {.dtype = dtype, .B = B, .Hq = Hq, .Hkv = Hkv, .Sq = Sq, .Skv = Skv, .D = D, .scale = scale},
+                      {.kind = KF_ATTN_MASK_PREFIX, .kv_len = kv_len, .prefix_len = prefix_len, .window_left = -1, .window_right = -1},
+                      {.q = q, .lq = lq, .k = k, .lk = lk, .v = v, .lv = lv, .o = o, .lo = lo, .lse = lse}, stream);
 }
 
 extern "C" int kf_attn_prefix_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
@@ -38,17 +57,18 @@ extern "C" int kf_attn_prefix_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv,
                                   const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
                                   const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
                                   const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream) {
-    return full_bwd("kf_attn_prefix_bwd", M_PREFIX, Window{-1, -1}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len, prefix_len, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq,
-                    dk, ldk, dv, ldv, workspace, workspace_bytes, stream);
+    return family_bwd("kf_attn_prefix_bwd", {.dtype = dtype, .B = B, .Hq = Hq, .Hkv = Hkv, .Sq = Sq, .Skv = Skv, .D = D, .scale = scale},
+                      {.kind = KF_ATTN_MASK_PREFIX, .kv_len = kv_len, .prefix_len = prefix_len, .window_left = -1, .window_right = -1},
+                      {.q = q, .lq = lq, .k = k, .lk = lk, .v = v, .lv = lv, .o = o, .lo = lo, .lse = lse, .d_o = d_o, .ldo = ldo, .dq = dq, .ldq = ldq,
+                       .dk = dk, .ldk = ldk, .dv = dv, .ldv = ldv, .workspace = workspace, .workspace_bytes = workspace_bytes}, stream);
 }
 
 extern "C" int kf_attn_window_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
                                   int64_t window_left, int64_t window_right, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
                                   const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
-    KF_REQUIRE(window_left >= -1 && window_right >= -1, KF_ERR_INVALID, "kf_attn_window_fwd: a window side is a key count >= 0 or -1 (unbounded), not (%lld, %lld)",
-               (long long)window_left, (long long)window_right);
-    return full_fwd("kf_attn_window_fwd", window_mode(window_left, window_right), Window{window_left, window_right}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len,
-                    nullptr, q, lq, k, lk, v, lv, o, lo, lse, stream);
+    return family_fwd("kf_attn_window_fwd", {.dtype = dtype, .B = B, .Hq = Hq, .Hkv = Hkv, .Sq = Sq, .Skv = Skv, .D = D, .scale = scale},
+                      {.kind = KF_ATTN_MASK_WINDOW, .kv_len = kv_len, .window_left = window_left, .window_right = window_right},
+                      {.q = q, .lq = lq, .k = k, .lk = lk, .v = v, .lv = lv, .o = o, .lo = lo, .lse = lse}, stream);
 }
 
 extern "C" int kf_attn_window_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale, const int64_t *kv_len,
@@ -56,10 +76,10 @@ extern "C" int kf_attn_window_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv,
                                   const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
                                   const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
                                   const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream) {
-    KF_REQUIRE(window_left >= -1 && window_right >= -1, KF_ERR_INVALID, "kf_attn_window_bwd: a window side is a key count >= 0 or -1 (unbounded), not (%lld, %lld)",
-               (long long)window_left, (long long)window_right);
-    return full_bwd("kf_attn_window_bwd", window_mode(window_left, window_right), Window{window_left, window_right}, dtype, B, Hq, Hkv, Sq, Skv, D, scale, kv_len,
-                    nullptr, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq, dk, ldk, dv, ldv, workspace, workspace_bytes, stream);
+    return family_bwd("kf_attn_window_bwd", {.dtype = dtype, .B = B, .Hq = Hq, .Hkv = Hkv, .Sq = Sq, .Skv = Skv, .D = D, .scale = scale},
+                      {.kind = KF_ATTN_MASK_WINDOW, .kv_len = kv_len, .window_left = window_left, .window_right = window_right},
+                      {.q = q, .lq = lq, .k = k, .lk = lk, .v = v, .lv = lv, .o = o, .lo = lo, .lse = lse, .d_o = d_o, .ldo = ldo, .dq = dq, .ldq = ldq,
+                       .dk = dk, .ldk = ldk, .dv = dv, .ldv = ldv, .workspace = workspace, .workspace_bytes = workspace_bytes}, stream);
 }
 
 // ---- the document variant: several sequences packed end to end in one row (kf_attn_doc_*) ----
@@ -79,9 +99,9 @@ extern "C" int kf_attn_doc_table(int64_t B, int64_t S, int64_t n_docs, const int
 extern "C" int kf_attn_doc_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D, float scale, int causal, const int64_t *kv_len,
                                const int32_t *doc_start, const int32_t *doc_end, const void *q, const kf_attn_layout *lq, const void *k,
                                const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream) {
-    KF_REQUIRE(causal == 0 || causal == 1, KF_ERR_INVALID, "kf_attn_doc_fwd: causal is 0 or 1, not %d", causal);
-    return full_fwd("kf_attn_doc_fwd", M_DOC, Window{-1, -1}, dtype, B, Hq, Hkv, S, S, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, stream,
-                    DocTables{doc_start, doc_end, causal});
+    return family_fwd("kf_attn_doc_fwd", {.dtype = dtype, .B = B, .Hq = Hq, .Hkv = Hkv, .Sq = S, .Skv = S, .D = D, .scale = scale},
+                      {.kind = KF_ATTN_MASK_DOC, .kv_len = kv_len, .window_left = -1, .window_right = -1, .doc_start = doc_start, .doc_end = doc_end, .causal = causal},
+                      {.q = q, .lq = lq, .k = k, .lk = lk, .v = v, .lv = lv, .o = o, .lo = lo, .lse = lse}, stream);
 }
 
 extern "C" int kf_attn_doc_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D, float scale, int causal, const int64_t *kv_len,
@@ -89,7 +109,8 @@ extern "C" int kf_attn_doc_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, in
                                const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse,
                                const void *d_o, const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
                                const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream) {
-    KF_REQUIRE(causal == 0 || causal == 1, KF_ERR_INVALID, "kf_attn_doc_bwd: causal is 0 or 1, not %d", causal);
-    return full_bwd("kf_attn_doc_bwd", M_DOC, Window{-1, -1}, dtype, B, Hq, Hkv, S, S, D, scale, kv_len, nullptr, q, lq, k, lk, v, lv, o, lo, lse, d_o, ldo, dq, ldq,
-                    dk, ldk, dv, ldv, workspace, workspace_bytes, stream, DocTables{doc_start, doc_end, causal});
+    return family_bwd("kf_attn_doc_bwd", {.dtype = dtype, .B = B, .Hq = Hq, .Hkv = Hkv, .Sq = S, .Skv = S, .D = D, .scale = scale},
+                      {.kind = KF_ATTN_MASK_DOC, .kv_len = kv_len, .window_left = -1, .window_right = -1, .doc_start = doc_start, .doc_end = doc_end, .causal = causal},
+                      {.q = q, .lq = lq, .k = k, .lk = lk, .v = v, .lv = lv, .o = o, .lo = lo, .lse = lse, .d_o = d_o, .ldo = ldo, .dq = dq, .ldq = ldq,
+                       .dk = dk, .ldk = ldk, .dv = dv, .ldv = ldv, .workspace = workspace, .workspace_bytes = workspace_bytes}, stream);
 }

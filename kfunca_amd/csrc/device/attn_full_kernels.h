@@ -63,8 +63,11 @@
 //   sink  one logit per query head that joins the softmax denominator and owns no value row: the forward EPILOGUE folds it into
 //         1 / l and lse against max(m_i c, sink log2(e)) (fold_sink). The backward bodies are unchanged - P is formed from lse, which
 //         holds the sink - and attn_sink_grad_kernel sums dsink from lse and the delta of the pre-pass in a fixed order.
-// This header is the whole family but its C entries: attn_full.hip holds the entries without modifiers, attn_ext.hip those with them
-// (two translation units, so the modified instantiations compile beside the others, not after them).
+// This header is the whole family but its C entries: the kernels and, below the `host` banner, the one host path - a kf_attn_mask
+// checked once (mask_check), the call in four bundles, full_fwd<X> and full_bwd<CAP>. attn_full.hip holds the per-family entries and
+// the instantiations without modifiers (plain_fwd, plain_bwd); attn_ext.hip holds kf_attn_ext_* and every modified instantiation, and
+// calls plain_fwd / plain_bwd when the modifiers are off (two translation units, so the modified instantiations compile beside the
+// others, not after them).
 #pragma once
 
 #include <math.h>
@@ -1348,10 +1351,43 @@ static bool lay_from(const kf_attn_layout *l, int es, Lay &out) {
 
 enum Plan { PLAN_NONE, PLAN_MFMA, PLAN_GENERIC };
 
-// Everything that can be refused, in one place and before any device call. `ops`: the operand pointers in the order of `lay`
-// (forward: q k v o; backward: + dO dQ dK dV). plan == PLAN_NONE with KF_OK: nothing to do (B, Hq or Sq is 0).
-static int full_check(const char *who, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
-                      const void *const *ops, const kf_attn_layout *const *lay, int nlay, FullArgs &a, Plan &plan) {
+// A call as the C entries take it, in four bundles. The operands are in the order of the prototypes, each pointer beside its layout
+// (NULL: contiguous), so an entry fills them by name and reads like the prototype it implements.
+struct Problem {
+    int dtype;
+    int64_t B, Hq, Hkv, Sq, Skv, D;
+    float scale;
+};
+struct FwdOps {
+    const void *q; const kf_attn_layout *lq;
+    const void *k; const kf_attn_layout *lk;
+    const void *v; const kf_attn_layout *lv;
+    void *o; const kf_attn_layout *lo;
+    float *lse; // written; may be null
+};
+struct BwdOps {
+    const void *q; const kf_attn_layout *lq;
+    const void *k; const kf_attn_layout *lk;
+    const void *v; const kf_attn_layout *lv;
+    const void *o; const kf_attn_layout *lo;
+    const float *lse;
+    const void *d_o; const kf_attn_layout *ldo;
+    void *dq; const kf_attn_layout *ldq;
+    void *dk; const kf_attn_layout *ldk;
+    void *dv; const kf_attn_layout *ldv;
+    void *workspace; size_t workspace_bytes;
+};
+struct Mods { // the score modifiers of kf_attn_ext_*; the entries of attn_full.hip have none
+    float softcap;     // 0: off
+    const float *sink; // [Hq] on the device, or null
+};
+
+// Everything about the problem and its operands that can be refused, in one place and before any device call. `ops`: the operand
+// pointers in the order of `lay` (forward: q k v o; backward: + dO dQ dK dV). plan == PLAN_NONE with KF_OK: nothing to do (B, Hq or Sq is 0).
+static int full_check(const char *who, const Problem &pr, const void *const *ops, const kf_attn_layout *const *lay, int nlay, FullArgs &a, Plan &plan) {
+    const int dtype = pr.dtype;
+    const int64_t B = pr.B, Hq = pr.Hq, Hkv = pr.Hkv, Sq = pr.Sq, Skv = pr.Skv, D = pr.D;
+    const float scale = pr.scale;
     plan = PLAN_NONE;
     KF_REQUIRE(dtype == KF_F32 || dtype == KF_BF16 || dtype == KF_F16, KF_ERR_INVALID, "%s: dtype %d is not f32, bf16 or f16", who, dtype);
     KF_REQUIRE(B >= 0 && Hq >= 0 && Sq >= 0 && Skv >= 0, KF_ERR_INVALID, "%s: negative extent", who);
@@ -1403,10 +1439,10 @@ static int full_check(const char *who, int dtype, int64_t B, int64_t Hq, int64_t
 using namespace kf;
 using namespace kf::full;
 
-// The four families share their host path. `mode` selects the instantiations and labels: M_PREFIX the prefix-LM ones
-// (kf_attn_prefix_*), M_WINDOW the window ones (kf_attn_window_*; prefix_len carries nothing, the window is in `win`), M_DOC the
-// document ones (kf_attn_doc_*; the tables and the causal flag are in `doc`); with M_FULL prefix_len is not read and the launches are
-// kf_attn_full_*'s own.
+// The four families and kf_attn_ext_* share their host path. A mask is the ABI's kf_attn_mask from the C entry on - a per-family entry
+// builds one from its own arguments - and mask_check turns it into a MaskPlan: the `mode` that selects the instantiations and labels
+// (M_PREFIX the prefix-LM ones, M_WINDOW the window ones, M_DOC the document ones; with M_FULL the launches are kf_attn_full_*'s own)
+// and what the kernels of that mode read.
 template <typename F> static inline int with_mode(Mode mode, F &&f) {
     return mode == M_FULL ? f(std::integral_constant<int, M_FULL>{})
                           : mode == M_PREFIX ? f(std::integral_constant<int, M_PREFIX>{})
@@ -1414,155 +1450,185 @@ template <typename F> static inline int with_mode(Mode mode, F &&f) {
 }
 struct Window { int64_t left, right; };
 struct DocTables { const int32_t *start, *end; int causal; }; // the document variant's tables ([B, S] on the device) and its causal flag
-static const char *const kFwdLabel[4][2] = {{"attn_full_fwd_mfma_d128", "attn_full_fwd_mfma_d64"},
-                                            {"attn_prefix_fwd_mfma_d128", "attn_prefix_fwd_mfma_d64"},
-                                            {"attn_window_fwd_mfma_d128", "attn_window_fwd_mfma_d64"},
-                                            {"attn_doc_fwd_mfma_d128", "attn_doc_fwd_mfma_d64"}};
-static const char *const kDqLabel[4][2] = {{"attn_full_bwd_dq_mfma_d128", "attn_full_bwd_dq_mfma_d64"},
-                                           {"attn_prefix_bwd_dq_mfma_d128", "attn_prefix_bwd_dq_mfma_d64"},
-                                           {"attn_window_bwd_dq_mfma_d128", "attn_window_bwd_dq_mfma_d64"},
-                                           {"attn_doc_bwd_dq_mfma_d128", "attn_doc_bwd_dq_mfma_d64"}};
-static const char *const kDkvLabel[4][2] = {{"attn_full_bwd_dkv_mfma_d128", "attn_full_bwd_dkv_mfma_d64"},
-                                            {"attn_prefix_bwd_dkv_mfma_d128", "attn_prefix_bwd_dkv_mfma_d64"},
-                                            {"attn_window_bwd_dkv_mfma_d128", "attn_window_bwd_dkv_mfma_d64"},
-                                            {"attn_doc_bwd_dkv_mfma_d128", "attn_doc_bwd_dkv_mfma_d64"}};
-static const char *const kGenericLabel[4][3] = {{"attn_full_fwd_generic", "attn_full_bwd_dq_generic", "attn_full_bwd_dkv_generic"},
-                                                {"attn_prefix_fwd_generic", "attn_prefix_bwd_dq_generic", "attn_prefix_bwd_dkv_generic"},
-                                                {"attn_window_fwd_generic", "attn_window_bwd_dq_generic", "attn_window_bwd_dkv_generic"},
-                                                {"attn_doc_fwd_generic", "attn_doc_bwd_dq_generic", "attn_doc_bwd_dkv_generic"}};
-// the same kernels compiled with the soft-cap (kf_attn_ext_* with softcap > 0)
-static const char *const kCapFwdLabel[4][2] = {{"attn_full_cap_fwd_mfma_d128", "attn_full_cap_fwd_mfma_d64"},
-                                               {"attn_prefix_cap_fwd_mfma_d128", "attn_prefix_cap_fwd_mfma_d64"},
-                                               {"attn_window_cap_fwd_mfma_d128", "attn_window_cap_fwd_mfma_d64"},
-                                               {"attn_doc_cap_fwd_mfma_d128", "attn_doc_cap_fwd_mfma_d64"}};
-static const char *const kCapDqLabel[4][2] = {{"attn_full_cap_bwd_dq_mfma_d128", "attn_full_cap_bwd_dq_mfma_d64"},
-                                              {"attn_prefix_cap_bwd_dq_mfma_d128", "attn_prefix_cap_bwd_dq_mfma_d64"},
-                                              {"attn_window_cap_bwd_dq_mfma_d128", "attn_window_cap_bwd_dq_mfma_d64"},
-                                              {"attn_doc_cap_bwd_dq_mfma_d128", "attn_doc_cap_bwd_dq_mfma_d64"}};
-static const char *const kCapDkvLabel[4][2] = {{"attn_full_cap_bwd_dkv_mfma_d128", "attn_full_cap_bwd_dkv_mfma_d64"},
-                                               {"attn_prefix_cap_bwd_dkv_mfma_d128", "attn_prefix_cap_bwd_dkv_mfma_d64"},
-                                               {"attn_window_cap_bwd_dkv_mfma_d128", "attn_window_cap_bwd_dkv_mfma_d64"},
-                                               {"attn_doc_cap_bwd_dkv_mfma_d128", "attn_doc_cap_bwd_dkv_mfma_d64"}};
-static const char *const kCapGenericLabel[4][3] = {{"attn_full_cap_fwd_generic", "attn_full_cap_bwd_dq_generic", "attn_full_cap_bwd_dkv_generic"},
-                                                   {"attn_prefix_cap_fwd_generic", "attn_prefix_cap_bwd_dq_generic", "attn_prefix_cap_bwd_dkv_generic"},
-                                                   {"attn_window_cap_fwd_generic", "attn_window_cap_bwd_dq_generic", "attn_window_cap_bwd_dkv_generic"},
-                                                   {"attn_doc_cap_fwd_generic", "attn_doc_cap_bwd_dq_generic", "attn_doc_cap_bwd_dkv_generic"}};
-// the window as the kernels carry it: an unbounded side, or one wider than any extent, is kNoEdge
-static void set_window(FullArgs &a, Mode mode, Window win) {
-    if (mode != M_WINDOW) return;
-    a.wl = win.left < 0 || win.left > kNoEdge ? kNoEdge : win.left;
-    a.wr = win.right < 0 || win.right > kNoEdge ? kNoEdge : win.right;
-}
+struct MaskPlan {
+    Mode mode;
+    const int64_t *kv_len, *prefix_len; // [B] on the device, or null; prefix_len of KF_ATTN_MASK_PREFIX only
+    Window win;                         // of KF_ATTN_MASK_WINDOW, else (-1, -1)
+    DocTables doc;                      // of KF_ATTN_MASK_DOC, else nulls and 0
+};
+
 // The two windows an older family already is take its kernels, so their results have its bits: (-1, -1) is full attention, (-1, 0)
-// padded-causal (kf_attn_prefix_* without a prefix). The refusals still carry the window entry's name.
+// padded-causal (kf_attn_prefix_* without a prefix). The refusals still carry the calling entry's name.
 static Mode window_mode(int64_t wl, int64_t wr) { return wl < 0 && wr < 0 ? M_FULL : (wl < 0 && wr == 0 ? M_PREFIX : M_WINDOW); }
-// the document variant's tables: required once there is something to launch (as the operands are), and 32-bit, so S stays below 2^31
-static int set_doc(const char *who, FullArgs &a, Mode mode, const DocTables &doc) {
-    if (mode != M_DOC) return KF_OK;
-    KF_REQUIRE(doc.start && doc.end, KF_ERR_INVALID, "%s: null doc_start or doc_end (kf_attn_doc_table writes them)", who);
-    KF_REQUIRE(a.Sq < (1ll << 31), KF_ERR_UNSUPPORTED, "%s: the document tables are 32-bit, S must be below 2^31", who);
-    a.doc_start = doc.start;
-    a.doc_end = doc.end;
-    a.causal = doc.causal;
+
+// The one validation of a mask: its kind and the fields that belong to it. A field of another kind must hold its neutral value (NULL,
+// -1, 0); the per-family entries have no such argument at all, and the masks they build hold those values.
+static int mask_check(const char *who, const kf_attn_mask *m, int64_t Sq, int64_t Skv, MaskPlan &p) {
+    KF_REQUIRE(m, KF_ERR_INVALID, "%s: null mask", who);
+    KF_REQUIRE(m->kind >= KF_ATTN_MASK_FULL && m->kind <= KF_ATTN_MASK_DOC, KF_ERR_INVALID, "%s: unknown mask kind %d", who, m->kind);
+    KF_REQUIRE(m->kind == KF_ATTN_MASK_PREFIX || !m->prefix_len, KF_ERR_INVALID, "%s: prefix_len belongs to KF_ATTN_MASK_PREFIX, the kind is %d", who, m->kind);
+    KF_REQUIRE(m->kind == KF_ATTN_MASK_WINDOW || (m->window_left == -1 && m->window_right == -1), KF_ERR_INVALID,
+               "%s: a window (%lld, %lld) belongs to KF_ATTN_MASK_WINDOW, the kind is %d (other kinds: -1, -1)", who, (long long)m->window_left,
+               (long long)m->window_right, m->kind);
+    KF_REQUIRE(m->kind == KF_ATTN_MASK_DOC || (!m->doc_start && !m->doc_end && m->causal == 0), KF_ERR_INVALID,
+               "%s: doc_start, doc_end and causal belong to KF_ATTN_MASK_DOC, the kind is %d", who, m->kind);
+    p = MaskPlan{(Mode)m->kind, m->kv_len, m->prefix_len, Window{-1, -1}, DocTables{nullptr, nullptr, 0}};
+    if (m->kind == KF_ATTN_MASK_WINDOW) {
+        KF_REQUIRE(m->window_left >= -1 && m->window_right >= -1, KF_ERR_INVALID, "%s: a window side is a key count >= 0 or -1 (unbounded), not (%lld, %lld)", who,
+                   (long long)m->window_left, (long long)m->window_right);
+        p.win = Window{m->window_left, m->window_right};
+        p.mode = window_mode(m->window_left, m->window_right);
+    } else if (m->kind == KF_ATTN_MASK_DOC) {
+        KF_REQUIRE(m->causal == 0 || m->causal == 1, KF_ERR_INVALID, "%s: causal is 0 or 1, not %d", who, m->causal);
+        KF_REQUIRE(Sq == Skv, KF_ERR_INVALID, "%s: a document mask is self-attention, Sq %lld must equal Skv %lld", who, (long long)Sq, (long long)Skv);
+        p.doc = DocTables{m->doc_start, m->doc_end, m->causal};
+    }
     return KF_OK;
 }
 
-// X, CAP: the modifiers of kf_attn_ext_* (attn_ext.hip), which instantiates the modified kernels; the entries of attn_full.hip pass none.
-// X_SINK keeps the labels of the kernels without modifiers, X_CAP and CAP take the _cap_ ones.
-template <int X = X_NONE>
-static int full_fwd(const char *who, Mode mode, Window win, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
-                    const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
-                    const void *v, const kf_attn_layout *lv, void *o, const kf_attn_layout *lo, float *lse, void *stream, DocTables doc = DocTables{nullptr, nullptr, 0},
-                    float softcap = 0.f, const float *sink = nullptr) {
-    const void *ops[4] = {q, k, v, o};
-    const kf_attn_layout *lay[4] = {lq, lk, lv, lo};
+// The plan as the kernels carry it; fields of another mode stay zero. An unbounded window side, or one wider than any extent, is
+// kNoEdge. The document tables are required once there is something to launch (as the operands are), and 32-bit, so S stays below 2^31.
+static int set_mask(const char *who, FullArgs &a, const MaskPlan &p) {
+    a.kv_len = p.kv_len;
+    a.prefix_len = p.prefix_len;
+    if (p.mode == M_WINDOW) {
+        a.wl = p.win.left < 0 || p.win.left > kNoEdge ? kNoEdge : p.win.left;
+        a.wr = p.win.right < 0 || p.win.right > kNoEdge ? kNoEdge : p.win.right;
+    }
+    if (p.mode != M_DOC) return KF_OK;
+    KF_REQUIRE(p.doc.start && p.doc.end, KF_ERR_INVALID, "%s: null doc_start or doc_end (kf_attn_doc_table writes them)", who);
+    KF_REQUIRE(a.Sq < (1ll << 31), KF_ERR_UNSUPPORTED, "%s: the document tables are 32-bit, S must be below 2^31", who);
+    a.doc_start = p.doc.start;
+    a.doc_end = p.doc.end;
+    a.causal = p.doc.causal;
+    return KF_OK;
+}
+
+// The profile labels of one family, without (cap = "") or with (cap = "_cap") the soft-cap: string literals, KF_PROF keeps the pointer.
+struct Labels { const char *fwd[2], *dq[2], *dkv[2], *generic[3]; }; // [d64]; generic: fwd, dQ, dK/dV
+#define KF_ATTN_LABELS(family, cap)                                                                                      \
+    {{"attn_" family cap "_fwd_mfma_d128", "attn_" family cap "_fwd_mfma_d64"},                                          \
+     {"attn_" family cap "_bwd_dq_mfma_d128", "attn_" family cap "_bwd_dq_mfma_d64"},                                    \
+     {"attn_" family cap "_bwd_dkv_mfma_d128", "attn_" family cap "_bwd_dkv_mfma_d64"},                                  \
+     {"attn_" family cap "_fwd_generic", "attn_" family cap "_bwd_dq_generic", "attn_" family cap "_bwd_dkv_generic"}}
+static const Labels kLabels[2][4] = { // [with the soft-cap: kf_attn_ext_* with softcap > 0][mode]
+    {KF_ATTN_LABELS("full", ""), KF_ATTN_LABELS("prefix", ""), KF_ATTN_LABELS("window", ""), KF_ATTN_LABELS("doc", "")},
+    {KF_ATTN_LABELS("full", "_cap"), KF_ATTN_LABELS("prefix", "_cap"), KF_ATTN_LABELS("window", "_cap"), KF_ATTN_LABELS("doc", "_cap")}};
+#undef KF_ATTN_LABELS
+
+// X, CAP: the modifiers of kf_attn_ext_* (attn_ext.hip), which instantiates the modified kernels; attn_full.hip instantiates the others
+// (plain_fwd, plain_bwd). X_SINK keeps the labels of the kernels without modifiers, X_CAP and CAP take the _cap_ ones.
+template <int X> static int full_fwd(const char *who, const Problem &pr, const MaskPlan &p, Mods mod, const FwdOps &x, void *stream) {
+    const void *ops[4] = {x.q, x.k, x.v, x.o};
+    const kf_attn_layout *lay[4] = {x.lq, x.lk, x.lv, x.lo};
     FullArgs a;
     Plan plan;
-    int rc = full_check(who, dtype, B, Hq, Hkv, Sq, Skv, D, scale, ops, lay, 4, a, plan);
+    int rc = full_check(who, pr, ops, lay, 4, a, plan);
     if (rc != KF_OK || plan == PLAN_NONE) return rc;
-    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.out = (char *)o; a.lse = lse; a.kv_len = kv_len;
-    a.prefix_len = mode == M_PREFIX ? prefix_len : nullptr;
-    set_window(a, mode, win);
-    rc = set_doc(who, a, mode, doc);
+    a.q = (const char *)x.q; a.k = (const char *)x.k; a.v = (const char *)x.v; a.out = (char *)x.o; a.lse = x.lse;
+    rc = set_mask(who, a, p);
     if (rc != KF_OK) return rc;
-    a.softcap = softcap;
-    a.sink = sink;
+    a.softcap = mod.softcap;
+    a.sink = mod.sink;
     hipStream_t st = as_stream(stream);
-    const bool bf = dtype == KF_BF16, d64 = D == 64;
+    const Mode mode = p.mode;
+    const Labels &label = kLabels[X == X_CAP][mode];
+    const int64_t B = pr.B, Hq = pr.Hq, Sq = pr.Sq;
+    const bool bf = pr.dtype == KF_BF16, d64 = pr.D == 64;
     if (plan == PLAN_MFMA) {
         const unsigned grid = (unsigned)(B * Hq * ((Sq + TQ - 1) / TQ));
-        KF_PROF(X == X_CAP ? kCapFwdLabel[mode][d64] : kFwdLabel[mode][d64], st);
+        KF_PROF(label.fwd[d64], st);
         return with_mode(mode, [&](auto M) {
             return with_flags([&](auto BF, auto D64) { return launch(attn_full_fwd_kernel<BF, D64 ? 64 : 128, M, X>, grid, NT, 2 * SLOT, st, a); }, bf, d64);
         });
     }
-    KF_PROF(X == X_CAP ? kCapGenericLabel[mode][0] : kGenericLabel[mode][0], st);
-    return with_dtype(dtype, [&](auto t) {
+    KF_PROF(label.generic[0], st);
+    return with_dtype(pr.dtype, [&](auto t) {
         return with_mode(mode, [&](auto M) { return launch(attn_full_fwd_generic_kernel<decltype(t), M, X>, (unsigned)(B * Hq * Sq), NT, 0, st, a); });
     });
 }
 
-template <bool CAP = false>
-static int full_bwd(const char *who, Mode mode, Window win, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, float scale,
-                    const int64_t *kv_len, const int64_t *prefix_len, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk,
-                    const void *v, const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
-                    const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
-                    const kf_attn_layout *ldv, void *workspace, size_t workspace_bytes, void *stream, DocTables doc = DocTables{nullptr, nullptr, 0},
-                    float softcap = 0.f) {
-    const void *ops[8] = {q, k, v, o, d_o, dq, dk, dv};
-    const kf_attn_layout *lay[8] = {lq, lk, lv, lo, ldo, ldq, ldk, ldv};
+// size_query: the workspace query of the calling family, which the workspace refusal names. mod.sink is not read: the backward kernels
+// form P from lse, which holds the sink (kf_attn_ext_bwd launches attn_sink_grad after this).
+template <bool CAP>
+static int full_bwd(const char *who, const char *size_query, const Problem &pr, const MaskPlan &p, Mods mod, const BwdOps &x, void *stream) {
+    const void *ops[8] = {x.q, x.k, x.v, x.o, x.d_o, x.dq, x.dk, x.dv};
+    const kf_attn_layout *lay[8] = {x.lq, x.lk, x.lv, x.lo, x.ldo, x.ldq, x.ldk, x.ldv};
     FullArgs a;
     Plan plan;
-    int rc = full_check(who, dtype, B, Hq, Hkv, Sq, Skv, D, scale, ops, lay, 8, a, plan);
+    int rc = full_check(who, pr, ops, lay, 8, a, plan);
     if (rc != KF_OK || plan == PLAN_NONE) return rc;
-    KF_REQUIRE(lse, KF_ERR_INVALID, "%s: null operand", who);
+    const int64_t B = pr.B, Hq = pr.Hq, Hkv = pr.Hkv, Sq = pr.Sq, Skv = pr.Skv, D = pr.D;
+    KF_REQUIRE(x.lse, KF_ERR_INVALID, "%s: null operand", who);
     const size_t need = ws_bytes(B, Hq, Sq);
-    KF_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % sizeof(float) == 0, KF_ERR_INVALID,
-               "%s: workspace of at least %zu bytes required (kf_attn_full_bwd_workspace_bytes), got %zu", who, need, workspace_bytes);
-    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.o = (const char *)o; a.d_o = (const char *)d_o;
-    a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv;
-    a.lse_r = lse; a.delta = (float *)workspace; a.kv_len = kv_len;
-    a.prefix_len = mode == M_PREFIX ? prefix_len : nullptr;
-    set_window(a, mode, win);
-    rc = set_doc(who, a, mode, doc);
+    KF_REQUIRE(x.workspace && x.workspace_bytes >= need && (uintptr_t)x.workspace % sizeof(float) == 0, KF_ERR_INVALID,
+               "%s: workspace of at least %zu bytes required (%s), got %zu", who, need, size_query, x.workspace_bytes);
+    a.q = (const char *)x.q; a.k = (const char *)x.k; a.v = (const char *)x.v; a.o = (const char *)x.o; a.d_o = (const char *)x.d_o;
+    a.dq = (char *)x.dq; a.dk = (char *)x.dk; a.dv = (char *)x.dv;
+    a.lse_r = x.lse; a.delta = (float *)x.workspace;
+    rc = set_mask(who, a, p);
     if (rc != KF_OK) return rc;
-    a.softcap = softcap;
+    a.softcap = mod.softcap;
     hipStream_t st = as_stream(stream);
-    const bool bf = dtype == KF_BF16, d64 = D == 64;
+    const Mode mode = p.mode;
+    const Labels &label = kLabels[CAP][mode];
+    const bool bf = pr.dtype == KF_BF16, d64 = D == 64;
     const int64_t nrows = B * Hq * Sq;
     if (plan == PLAN_MFMA) {
-        { // the delta pre-pass knows no mask: one kernel and one label for both families
+        { // the delta pre-pass knows no mask: one kernel and one label for every family
             KF_PROF("attn_full_bwd_delta", st);
             rc = with_flags([&](auto BF) { return launch(attn_full_delta_kernel<BF>, (unsigned)((nrows + 15) / 16), NT, 0, st, a.o, a.d_o, a.delta, nrows, a.lo, a.ldo, Sq, Hq, (int)(D / 8)); }, bf);
             if (rc != KF_OK) return rc;
         }
         {
-            KF_PROF(CAP ? kCapDqLabel[mode][d64] : kDqLabel[mode][d64], st);
+            KF_PROF(label.dq[d64], st);
             const unsigned grid = (unsigned)(B * Hq * ((Sq + TQ - 1) / TQ));
             rc = with_mode(mode, [&](auto M) {
                 return with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dq_kernel<BF, D64 ? 64 : 128, M, CAP>, grid, NT, DQ_LDS, st, a); }, bf, d64);
             });
             if (rc != KF_OK) return rc;
         }
-        KF_PROF(CAP ? kCapDkvLabel[mode][d64] : kDkvLabel[mode][d64], st);
+        KF_PROF(label.dkv[d64], st);
         const unsigned grid = (unsigned)(B * Hkv * ((Skv + TQ - 1) / TQ));
         return with_mode(mode, [&](auto M) {
             return with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dkv_kernel<BF, D64 ? 64 : 128, M, CAP>, grid, NT, KV_LDS, st, a); }, bf, d64);
         });
     }
-    return with_dtype(dtype, [&](auto t) {
+    return with_dtype(pr.dtype, [&](auto t) {
         using T = decltype(t);
         {
             KF_PROF("attn_full_bwd_delta_generic", st);
-            rc = launch(attn_full_delta_generic_kernel<T>, (unsigned)((nrows + NT - 1) / NT), NT, 0, st, (const T *)o, (const T *)d_o, a.delta, nrows, (int)D);
+            rc = launch(attn_full_delta_generic_kernel<T>, (unsigned)((nrows + NT - 1) / NT), NT, 0, st, (const T *)x.o, (const T *)x.d_o, a.delta, nrows, (int)D);
             if (rc != KF_OK) return rc;
         }
         {
-            KF_PROF(CAP ? kCapGenericLabel[mode][1] : kGenericLabel[mode][1], st);
+            KF_PROF(label.generic[1], st);
             rc = with_mode(mode, [&](auto M) { return launch(attn_full_bwd_dq_generic_kernel<T, M, CAP>, (unsigned)nrows, NT, 0, st, a); });
             if (rc != KF_OK) return rc;
         }
-        KF_PROF(CAP ? kCapGenericLabel[mode][2] : kGenericLabel[mode][2], st);
+        KF_PROF(label.generic[2], st);
         return with_mode(mode, [&](auto M) { return launch(attn_full_bwd_dkv_generic_kernel<T, M, CAP>, (unsigned)(B * Hkv * Skv), NT, 0, st, a); });
     });
 }
+
+// kf_attn_full_bwd_workspace_bytes and kf_attn_ext_bwd_workspace_bytes: one size (delta), the checks of the problem under the query's name
+static int ws_query(const char *who, const Problem &pr, size_t *bytes) {
+    KF_REQUIRE(bytes, KF_ERR_INVALID, "%s: null out pointer", who);
+    FullArgs a;
+    Plan plan;
+    int rc = full_check(who, pr, nullptr, nullptr, 0, a, plan);
+    if (rc != KF_OK) return rc;
+    *bytes = ws_bytes(pr.B, pr.Hq, pr.Sq);
+    return KF_OK;
+}
+
+// The host path without modifiers, full_fwd<X_NONE> and full_bwd<false>: defined in attn_full.hip, whose translation unit alone holds
+// those instantiations, and called from attn_ext.hip when the modifiers are off (library-internal, as kf::set_error is). `who` is the
+// C entry that was called: every refusal carries its name.
+namespace kf {
+namespace full {
+int plain_fwd(const char *who, const Problem &pr, const MaskPlan &p, const FwdOps &x, void *stream);
+int plain_bwd(const char *who, const char *size_query, const Problem &pr, const MaskPlan &p, const BwdOps &x, void *stream);
+} // namespace full
+} // namespace kf
+
