@@ -701,6 +701,52 @@ int kf_attn_ext_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, i
                     const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv, const kf_attn_layout *ldv,
                     float *dsink, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The document mask with a causal rule, a bidirectional prefix per document and a sliding window (packed rows in the local layers of
+ * Mistral, Gemma-2/3 and gpt-oss; packed prefix-LM samples). Self-attention, Sq = Skv = S. Its own trio: kf_attn_mask and its kinds are
+ * unchanged. c_j, len_b and document membership are kf_attn_doc_table's. For document j of row b,
+ * P_j = c_j + clamp(doc_prefix[b, j], 0, c_{j+1} - c_j), or c_j when doc_prefix is NULL.
+ *     query m sees key n   <=>   m and n lie in the same document j
+ *                                and (causal == 0 or n <= m or n < P_j)
+ *                                and (window_left < 0 or n >= m - window_left) and (window_right < 0 or n <= m + window_right)
+ * Such a mask is one interval of keys per query and one interval of queries per key, and kf_attn_span_table writes both (int32 [B, S]):
+ *     token m of document j as a query:  key_lo   = max(c_j, wl < 0 ? c_j : m - wl)
+ *                                        key_hi   = min(c_{j+1}, causal ? max(m + 1, P_j) : c_{j+1}, wr < 0 ? c_{j+1} : m + wr + 1)
+ *     token n of document j as a key:    query_lo = max(c_j, (causal and n >= P_j) ? n : c_j, wr < 0 ? c_j : n - wr)
+ *                                        query_hi = min(c_{j+1}, wl < 0 ? c_{j+1} : n + wl + 1)
+ * with hi = lo where hi < lo, all four equal to len_b for m >= len_b, every value in [0, S], and kv_len[b] = len_b (int64 [B]). All
+ * four columns are nondecreasing along a row. With causal = 1 a window_right of 0 lets no query see a later key, so it cancels every
+ * prefix: a prefix-LM window is (window_left, -1). doc_prefix: int64 [B, n_docs] on the device, or NULL. One launch, one thread per
+ * token, no atomics, capturable; profile label attn_span_table. KF_ERR_INVALID: n_docs < 1, a negative extent, a null pointer
+ * (doc_prefix may be NULL), causal not 0 or 1, a window side below -1, doc_prefix given with causal = 0. B or S equal to 0 is KF_OK
+ * without a launch; S >= 2^31 is KF_ERR_UNSUPPORTED. The tables are built once per batch and serve every layer that shares the mask,
+ * forward and backward.
+ *
+ * kf_attn_span_fwd / kf_attn_span_bwd: the forward and dQ read (key_lo, key_hi) at the query, dK/dV read (query_lo, query_hi) at the
+ * key. If the two pairs do not describe one relation the mask is unspecified; every entry is clamped when it is read, so no table
+ * content moves an access outside an operand. All tables are required wherever an operand is. softcap, sink and dsink follow
+ * kf_attn_ext_*'s contract (softcap is checked first, then dsink against sink). Everything else is kf_attn_doc_*'s contract with this
+ * entry's name in kf_last_error(): operands, layouts, grouped K/V heads, zero extents, the checks and their order, lse = -inf and zero
+ * bits for a token that sees nothing, zeros for rows of dk and dv that no query sees, S >= 2^31 unsupported. The workspace is
+ * kf_attn_full_bwd_workspace_bytes(dtype, B, Hq, Hkv, S, S, D)'s; there is no second size query.
+ * Kernels: none of its own. The document kernels run without their causal rule (the tables hold it) - with softcap > 0 or a sink the
+ * instantiations of kf_attn_ext_* with KF_ATTN_MASK_DOC - under the labels attn_doc_* / attn_doc_cap_*, attn_sink_grad after a backward
+ * with a sink. Called without a window and a prefix the results have the bits of kf_attn_doc_* with the same causal flag.
+ */
+int kf_attn_span_table(int64_t B, int64_t S, int64_t n_docs, const int64_t *cu_doclens, const int64_t *doc_prefix, int causal,
+                       int64_t window_left, int64_t window_right, int64_t *kv_len, int32_t *key_lo, int32_t *key_hi,
+                       int32_t *query_lo, int32_t *query_hi, void *stream);
+int kf_attn_span_fwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D, float scale, const int64_t *kv_len,
+                     const int32_t *key_lo, const int32_t *key_hi, float softcap, const float *sink, const void *q,
+                     const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v, const kf_attn_layout *lv, void *o,
+                     const kf_attn_layout *lo, float *lse, void *stream);
+int kf_attn_span_bwd(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D, float scale, const int64_t *kv_len,
+                     const int32_t *key_lo, const int32_t *key_hi, const int32_t *query_lo, const int32_t *query_hi, float softcap,
+                     const float *sink, const void *q, const kf_attn_layout *lq, const void *k, const kf_attn_layout *lk, const void *v,
+                     const kf_attn_layout *lv, const void *o, const kf_attn_layout *lo, const float *lse, const void *d_o,
+                     const kf_attn_layout *ldo, void *dq, const kf_attn_layout *ldq, void *dk, const kf_attn_layout *ldk, void *dv,
+                     const kf_attn_layout *ldv, float *dsink, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- rotary position embeddings (no reference counterpart: the position signal between the QKV projection and attention) ---- */
 /*
  * x, y: [B, H, S, D] addressed by kf_attn_layout element strides of B, H, S; D is contiguous; dtype in {KF_F32, KF_BF16, KF_F16};

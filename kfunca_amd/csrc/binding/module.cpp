@@ -420,12 +420,37 @@ PYBIND11_MODULE(_C, m) {
         .def_readonly("doc_start", &gpu::DocMask::doc_start)
         .def_readonly("doc_end", &gpu::DocMask::doc_end)
         .def_readonly("B", &gpu::DocMask::B)
-        .def_readonly("S", &gpu::DocMask::S);
-    m.def("doc_mask", &gpu::doc_mask, py::arg("cu_doclens"), py::arg("S"),
+        .def_readonly("S", &gpu::DocMask::S)
+        // a mask built with window, prefix_lens or causal: doc_start / doc_end are the keys each query sees (key_lo / key_hi), query_lo / query_hi the
+        // queries that see each key; a plain mask has neither, no window and causal False
+        .def_property_readonly("key_lo", [](const gpu::DocMask &d) { return d.doc_start; })
+        .def_property_readonly("key_hi", [](const gpu::DocMask &d) { return d.doc_end; })
+        .def_property_readonly("query_lo", [](const gpu::DocMask &d) -> py::object { return d.span ? py::cast(d.query_lo) : py::none(); })
+        .def_property_readonly("query_hi", [](const gpu::DocMask &d) -> py::object { return d.span ? py::cast(d.query_hi) : py::none(); })
+        .def_property_readonly("window", [](const gpu::DocMask &d) -> py::object {
+            if (d.window_left < 0 && d.window_right < 0) return py::none();
+            auto side = [](int64_t w) -> py::object { return w < 0 ? py::object(py::none()) : py::object(py::int_(w)); };
+            return py::make_tuple(side(d.window_left), side(d.window_right));
+        })
+        .def_readonly("causal", &gpu::DocMask::causal)
+        .def_readonly("span", &gpu::DocMask::span);
+    m.def("doc_mask", [opt, win](const Tensor &cu_doclens, int64_t S, py::object window, py::object prefix_lens, bool causal) {
+        if (window.is_none() && prefix_lens.is_none() && !causal) return gpu::doc_mask(cu_doclens, S); // the plain mask: its launch, its tables
+        gpu::AttentionWindow w;
+        return gpu::doc_mask(cu_doclens, S, win("doc_mask", window, w), opt(prefix_lens), causal);
+    }, py::arg("cu_doclens"), py::arg("S"), py::arg("window") = py::none(), py::arg("prefix_lens") = py::none(), py::arg("causal") = false,
           "doc_mask(cu_doclens, S) -> DocMask. cu_doclens: Long [B, n_docs + 1] on the device, the cumulative document lengths of each packed row:\n"
           "cu[b, 0] = 0 and document j of row b holds the tokens cu[b, j] <= m < cu[b, j+1]; a row with fewer documents repeats its last value\n"
           "(a zero-length document owns no token); values are clamped to [0, S], rows must be nondecreasing. Tokens at or beyond cu[b, -1] are\n"
-          "in no document. One launch; the DocMask is reused by every layer, forward and backward.");
+          "in no document. One launch; the DocMask is reused by every layer, forward and backward.\n"
+          "doc_mask(cu_doclens, S, window=None, prefix_lens=None, causal=False): with any of the three the mask holds, inside each document, a\n"
+          "causal rule (causal=True), a bidirectional prefix per document (prefix_lens: Long [B, n_docs] on the device, clamped to the\n"
+          "document; needs causal=True) and a sliding window (window: attention's pair; with causal=True the right side is 0 or None, read as\n"
+          "0): query m of document j sees key n of the same document iff (not causal or n <= m or n < start_j + prefix_j) and\n"
+          "m - left <= n <= m + right. With prefixes the right side is the causal rule alone, so a token sees the keys of its prefix that its\n"
+          "left side reaches. One launch writes four tables: doc_start / doc_end (also key_lo / key_hi), the keys each query sees, and\n"
+          "query_lo / query_hi, the queries that see each key; the mask keeps its window and its causal. attention(..., causal=) must repeat\n"
+          "the mask's causal. The local layers of a packed batch share one such mask, the global layers a plain one.");
     auto doc = [](const char *op, const py::object &d) -> const gpu::DocMask * {
         if (d.is_none()) return nullptr;
         if (!py::isinstance<gpu::DocMask>(d)) throw py::value_error(std::string(op) + ": doc_mask is a DocMask (doc_mask(cu_doclens, S)) or None");
@@ -462,7 +487,8 @@ PYBIND11_MODULE(_C, m) {
           "doc_mask: None, or a DocMask (doc_mask(cu_doclens, S)) for packed rows: each row holds several documents end to end and query m sees\n"
           "key n iff both lie in the same document (causal=True: and n <= m). Self-attention only (Sq = Skv = S of the mask); doc_mask together\n"
           "with kv_len, prefix_len or window is refused, and so is a mask built for another B, S or device. A token in no document gives a\n"
-          "zero row.\n"
+          "zero row. A window or prefixes INSIDE documents belong to the mask: doc_mask(cu_doclens, S, window=..., prefix_lens=..., causal=...);\n"
+          "such a mask holds the causal rule itself, and causal= here must equal the mask's (a mismatch is refused).\n"
           "softcap: None, or a positive finite float: every visible score x = q.k / sqrt(D) becomes softcap * tanh(x / softcap) (logit\n"
           "soft-capping); zero, negative and non-finite values are refused. sinks: None, or a Float tensor [Hq] on q's device (attention\n"
           "sinks): exp(sinks[h]) joins the softmax denominator of every query of head h - a raw logit, neither scaled nor capped - and owns\n"

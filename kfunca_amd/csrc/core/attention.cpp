@@ -1,6 +1,6 @@
 // namespace gpu: the attention operators over the C ABI's attention entries - causal_attention, causal_attention_gqa and
 // causal_attention_qkv (ops.h; nn_ops.cpp:6-8 + the checks of causal_attention_kernel.cu:9-20), attention and attention_qkv (attn_full.h).
-// Six families of entries (the causal pair, full attention and its prefix-LM, sliding-window and document-masked forms), one host path: check, plan the padding, pad,
+// Seven families of entries (the causal pair, full attention and its prefix-LM, sliding-window and document-masked forms, the last also with a window and prefixes inside the documents), one host path: check, plan the padding, pad,
 // allocate, call, un-pad.
 #include <cmath>
 
@@ -26,8 +26,9 @@ enum class Family {
     Prefix,    // kf_attn_prefix_fwd / kf_attn_prefix_bwd: Full's operands and checks; causal beyond an optional per-batch prefix
     Window,    // kf_attn_window_fwd / kf_attn_window_bwd: Full's operands and checks; keys m - left .. m + right of query m
     Doc,       // kf_attn_doc_fwd / kf_attn_doc_bwd: Full's operands and checks, Sq = Skv; the keys of the query's own document
+    Span,      // kf_attn_span_fwd / kf_attn_span_bwd: Doc's, the mask's causal rule, prefixes and window baked into two pairs of tables
 };
-bool full_like(Family f) { return f == Family::Full || f == Family::Prefix || f == Family::Window || f == Family::Doc; }
+bool full_like(Family f) { return f == Family::Full || f == Family::Prefix || f == Family::Window || f == Family::Doc || f == Family::Span; }
 // the length arrays of attention / attention_qkv: undefined tensors for the other families; with them the window of Family::Window
 // (-1: unbounded on that side), which the backward keeps beside the lengths
 // and the tables of Family::Doc (a DocMask's, kv among them) with its causal flag
@@ -36,6 +37,8 @@ struct Lens {
     int64_t wl = -1, wr = -1;
     Tensor doc_start, doc_end;
     bool doc_causal = false;
+    // Family::Span: doc_start and doc_end are the mask's key_lo and key_hi, these its key-indexed pair (the causal rule is in the tables)
+    Tensor query_lo, query_hi;
     // the score modifiers of attention / attention_qkv (kf_attn_ext_*): the cap (0: off) and the sinks, Float [Hq] (undefined: none)
     float softcap = 0.f;
     Tensor sinks;
@@ -55,12 +58,18 @@ struct Call {
     // the score modifiers (full-like families only): with either one the call goes to kf_attn_ext_*, without them to the family's entries
     float softcap = 0.f;
     const float *sink = nullptr;
+    const int32_t *query_lo = nullptr, *query_hi = nullptr; // Family::Span: the tables the dK/dV kernels read (mask.doc_start / doc_end: key_lo / key_hi)
     bool modified() const { return softcap > 0.f || sink; }
 };
 
 void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o, float *lse) {
     void *st = dev::stream(c.device);
     const kf_attn_mask &m = c.mask;
+    if (c.family == Family::Span) { // one entry with and without modifiers
+        DEV_CALL(kf_attn_span_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, m.kv_len, m.doc_start, m.doc_end, c.softcap, c.sink, q, c.lx, k, c.lx, v, c.lx, o,
+                                  c.lo, lse, st));
+        return;
+    }
     if (c.modified()) {
         DEV_CALL(kf_attn_ext_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, &m, c.softcap, c.sink, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
         return;
@@ -83,6 +92,8 @@ void run_fwd(const Call &c, const void *q, const void *k, const void *v, void *o
     case Family::Window:
         DEV_CALL(kf_attn_window_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, m.kv_len, m.window_left, m.window_right, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, st));
         break;
+    case Family::Span: // (served above)
+        break;
     case Family::Doc:
         DEV_CALL(kf_attn_doc_fwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, m.causal, m.kv_len, m.doc_start, m.doc_end, q, c.lx, k, c.lx, v, c.lx, o, c.lo,
                                  lse, st));
@@ -94,6 +105,11 @@ void run_bwd(const Call &c, const void *q, const void *k, const void *v, const v
              void *ws, size_t bytes, float *dsink = nullptr) {
     void *st = dev::stream(c.device);
     const kf_attn_mask &m = c.mask;
+    if (c.family == Family::Span) {
+        DEV_CALL(kf_attn_span_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, m.kv_len, m.doc_start, m.doc_end, c.query_lo, c.query_hi, c.softcap, c.sink, q, c.lx,
+                                  k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq, c.lx, dk, c.lx, dv, c.lx, dsink, ws, bytes, st));
+        return;
+    }
     if (c.modified()) { // (the workspace is kf_attn_full_bwd_workspace_bytes': the two size queries agree)
         DEV_CALL(kf_attn_ext_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, &m, c.softcap, c.sink, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo, dq,
                                  c.lx, dk, c.lx, dv, c.lx, dsink, ws, bytes, st));
@@ -122,6 +138,8 @@ void run_bwd(const Call &c, const void *q, const void *k, const void *v, const v
     case Family::Window:
         DEV_CALL(kf_attn_window_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, c.scale, m.kv_len, m.window_left, m.window_right, q, c.lx, k, c.lx, v, c.lx, o, c.lo, lse, go, c.lo,
                                     dq, c.lx, dk, c.lx, dv, c.lx, ws, bytes, st));
+        break;
+    case Family::Span: // (served above)
         break;
     case Family::Doc:
         DEV_CALL(kf_attn_doc_bwd(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.D, c.scale, m.causal, m.kv_len, m.doc_start, m.doc_end, q, c.lx, k, c.lx, v, c.lx, o, c.lo,
@@ -159,6 +177,7 @@ DataPtr bwd_scratch(const Call &c, size_t &bytes) {
     case Family::Prefix:
     case Family::Window:
     case Family::Doc:
+    case Family::Span:
         DEV_CALL(kf_attn_full_bwd_workspace_bytes(c.dt, c.B, c.Hq, c.Hkv, c.Sq, c.Skv, c.D, &bytes));
         return DeviceAllocator::GetInstance()->allocate(bytes > 0 ? bytes : 1, c.device);
     }
@@ -192,7 +211,10 @@ Tensor check_len(const Tensor &kv_len, int64_t B, int device, const char *name =
     return kv_len.dense();
 }
 Lens check_lens(const Lens &l, int64_t B, int device) {
-    return {check_len(l.kv, B, device), check_len(l.prefix, B, device, "prefix_len"), l.wl, l.wr, l.doc_start, l.doc_end, l.doc_causal, l.softcap, l.sinks};
+    Lens r = l;
+    r.kv = check_len(l.kv, B, device);
+    r.prefix = check_len(l.prefix, B, device, "prefix_len");
+    return r;
 }
 // the sinks of attention / attention_qkv: Float [Hq], dense, on the operands' device (the tensor itself is kept: it receives the gradient)
 void check_modifiers(const char *op, const Lens &l, int64_t Hq, int device) {
@@ -219,6 +241,10 @@ kf_attn_mask call_mask(Family f, const Lens &len) {
         m.doc_start = tab_ptr(len.doc_start);
         m.doc_end = tab_ptr(len.doc_end);
         m.causal = len.doc_causal;
+    } else if (f == Family::Span) { // as kf_attn_span_* read it: the document tables without a causal rule of their own
+        m.kind = KF_ATTN_MASK_DOC;
+        m.doc_start = tab_ptr(len.doc_start);
+        m.doc_end = tab_ptr(len.doc_end);
     }
     return m;
 }
@@ -264,7 +290,7 @@ Call contiguous_call(Family f, const Tensor &q, const Tensor &k, const PadPlan &
     const bool padded = pp.Sq != q.shape(2) || pp.Skv != k.shape(2) || pp.D != q.shape(3);
     return {.family = f, .dt = code(q.dtype()), .device = q.device(), .B = q.shape(0), .Hq = q.shape(1), .Hkv = k.shape(1), .Sq = pp.Sq, .Skv = pp.Skv,
             .D = pp.D, .scale = 1.0f / std::sqrt((float)q.shape(3)), .mask = call_mask(f, len), .lx = nullptr, .lo = nullptr, .padded = padded,
-            .softcap = len.softcap, .sink = sink_ptr(len.sinks)};
+            .softcap = len.softcap, .sink = sink_ptr(len.sinks), .query_lo = tab_ptr(len.query_lo), .query_hi = tab_ptr(len.query_hi)};
 }
 
 std::tuple<Tensor, Tensor> attention_forward(Family f, const Tensor &q, const Tensor &k, const Tensor &v, const Lens &len) {
@@ -345,7 +371,7 @@ PackedLay packed_layouts(int64_t S, int64_t H, int64_t Hkv, int64_t D) {
 Call packed_call(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D, const PackedLay &L, const Lens &len) {
     return {.family = f, .dt = code(qkv.dtype()), .device = qkv.device(), .B = B, .Hq = H, .Hkv = Hkv, .Sq = S, .Skv = S, .D = D,
             .scale = 1.0f / std::sqrt((float)D), .mask = call_mask(f, len), .lx = &L.qkv, .lo = &L.flat, .padded = false,
-            .softcap = len.softcap, .sink = sink_ptr(len.sinks)};
+            .softcap = len.softcap, .sink = sink_ptr(len.sinks), .query_lo = tab_ptr(len.query_lo), .query_hi = tab_ptr(len.query_hi)};
 }
 
 class PackedAttentionGradFunction : public GradFunction {
@@ -383,7 +409,7 @@ private:
 };
 
 // f: CausalMha for causal_attention_qkv(qkv, B, S, H) (Hkv = H, the [B*S, 3*H*D] texts), CausalGqa for its kv_heads form, Full, Prefix,
-// Window and Doc for attention_qkv
+// Window, Doc and Span for attention_qkv
 Tensor packed_attention(Family f, const Tensor &qkv, int64_t B, int64_t S, int64_t H, int64_t Hkv, const Lens &lens) {
     const char *op = full_like(f) ? "attention_qkv" : "causal_attention_qkv";
     CHECK_FAIL(qkv.defined() && qkv.dim() == 2 && qkv.is_dense(), op,
@@ -432,14 +458,15 @@ std::tuple<Tensor, Tensor, Tensor> causal_attention_bwd(const Tensor &q, const T
 }
 Tensor causal_attention(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalMha, q, k, v, Lens()); }
 Tensor causal_attention_gqa(const Tensor &q, const Tensor &k, const Tensor &v) { return contiguous_attention(Family::CausalGqa, q, k, v, Lens()); }
-// A document mask is a family of its own: the mask carries its key lengths, so kv_len beside it - like a prefix or a window, masks
-// this package does not combine with it - is refused, and so is a mask built for another batch, length or device (B_, S_, device:
-// the operands'; Sq: the query length, Sq != Skv being cross-attention between packed rows).
+// A document mask is a family of its own: the mask carries its key lengths, so kv_len beside it is refused - like a prefix or a window
+// given to the call: inside documents those are built into the mask (doc_mask(..., window, prefix_lens, causal)) - and so is a mask
+// built for another batch, length or device (B_, S_, device: the operands'; Sq: the query length, Sq != Skv being cross-attention between
+// packed rows). A mask built with a window, prefixes or causal holds the causal rule in its tables: the call's flag must repeat it.
 static Family doc_family(const char *op, bool causal, const Tensor &prefix_len, const AttentionWindow *window, Lens &lens, const DocMask *doc, int64_t B_,
                          int64_t Sq, int64_t S_, int device) {
     CHECK_FAIL(!lens.kv.defined() && !prefix_len.defined() && !window, op,
-               ": doc_mask cannot be combined with kv_len, prefix_len or window (the mask carries the rows' lengths; a window or a prefix inside "
-               "documents is not supported)");
+               ": doc_mask cannot be combined with kv_len, prefix_len or window (the mask carries the rows' lengths; a window or prefixes inside "
+               "documents belong to the mask: doc_mask(cu_doclens, S, window=..., prefix_lens=..., causal=...))");
     CHECK_FAIL(doc->kv_len.defined() && doc->doc_start.defined() && doc->doc_end.defined(), op, ": doc_mask is empty (build it with doc_mask(cu_doclens, S))");
     CHECK_FAIL(Sq == S_, op, ": doc_mask needs self-attention, Sq = Skv (got Sq = ", Sq, ", Skv = ", S_, ")");
     CHECK_FAIL(doc->B == B_ && doc->S == S_, op, ": doc_mask was built for B = ", doc->B, ", S = ", doc->S, ", the operands have B = ", B_, ", S = ", S_);
@@ -447,6 +474,14 @@ static Family doc_family(const char *op, bool causal, const Tensor &prefix_len, 
     lens.kv = doc->kv_len;
     lens.doc_start = doc->doc_start;
     lens.doc_end = doc->doc_end;
+    if (doc->span) {
+        CHECK_FAIL(doc->query_lo.defined() && doc->query_hi.defined(), op, ": doc_mask is empty (build it with doc_mask(cu_doclens, S, ...))");
+        CHECK_FAIL(causal == doc->causal, op, ": causal = ", causal ? "true" : "false", " but doc_mask was built with causal = ", doc->causal ? "true" : "false",
+                   " (a mask with a window or prefixes holds the causal rule in its tables: pass the same value to both)");
+        lens.query_lo = doc->query_lo;
+        lens.query_hi = doc->query_hi;
+        return Family::Span;
+    }
     lens.doc_causal = causal;
     return Family::Doc;
 }
@@ -485,23 +520,67 @@ Tensor attention(const Tensor &q, const Tensor &k, const Tensor &v, const Tensor
     return contiguous_attention(f, q, k, v, lens);
 }
 
-// One launch (kf_attn_doc_table); the three tensors are dense and live on cu_doclens' device.
-DocMask doc_mask(const Tensor &cu_doclens, int64_t S) {
+// What both forms of doc_mask share: the checks of cu_doclens and S, the dense list (cu) and the mask's B, S and kv_len.
+static DocMask doc_mask_head(const Tensor &cu_doclens, int64_t S, Tensor &cu) {
     CHECK_FAIL(cu_doclens.defined() && cu_doclens.dim() == 2 && cu_doclens.dtype() == ScalarType::Long && cu_doclens.shape(1) >= 2,
                "doc_mask expects cu_doclens of type Long and shape [B, n_docs + 1] with n_docs >= 1");
     CHECK_FAIL(S >= 0 && S < (int64_t(1) << 31), "doc_mask: S ", S, " outside [0, 2^31)");
-    const Tensor cu = cu_doclens.dense();
-    const int64_t B = cu.shape(0), n = cu.shape(1) - 1;
-    const int device = cu.device();
+    cu = cu_doclens.dense();
     DocMask m;
-    m.B = B;
+    m.B = cu.shape(0);
     m.S = S;
-    m.kv_len = zeros({B}, ScalarType::Long, device); // (S = 0 launches nothing: every length is 0)
+    m.kv_len = zeros({m.B}, ScalarType::Long, cu.device()); // (S = 0 launches nothing: every length is 0)
+    return m;
+}
+// One launch (kf_attn_doc_table); the three tensors are dense and live on cu_doclens' device.
+DocMask doc_mask(const Tensor &cu_doclens, int64_t S) {
+    Tensor cu;
+    DocMask m = doc_mask_head(cu_doclens, S, cu);
+    const int64_t B = m.B, n = cu.shape(1) - 1;
+    const int device = cu.device();
     m.doc_start = empty({B, S}, ScalarType::Int, device);
     m.doc_end = empty({B, S}, ScalarType::Int, device);
     if (B > 0 && S > 0)
         DEV_CALL(kf_attn_doc_table(B, S, n, static_cast<const int64_t *>(cu.data_ptr()), static_cast<int64_t *>(m.kv_len.data_ptr()),
                                    static_cast<int32_t *>(m.doc_start.data_ptr()), static_cast<int32_t *>(m.doc_end.data_ptr()), dev::stream(device)));
+    return m;
+}
+// The mask with a window, per-document prefixes or the causal rule inside the documents: one launch (kf_attn_span_table) writes the keys
+// each query sees (doc_start, doc_end) and the queries that see each key (query_lo, query_hi). The window is attention's: a side is a
+// key count or -1; causal closes the right side (0, or -1 read as 0). Prefixes open it again - a token sees its whole prefix - so with
+// them the table is built without a right side: the causal rule alone bounds it.
+DocMask doc_mask(const Tensor &cu_doclens, int64_t S, const AttentionWindow *window, const Tensor &prefix_lens, bool causal) {
+    Tensor cu;
+    DocMask m = doc_mask_head(cu_doclens, S, cu);
+    const int64_t B = m.B, n = cu.shape(1) - 1;
+    const int device = cu.device();
+    int64_t wl = -1, wr = -1;
+    if (window) {
+        CHECK_FAIL(window->left >= -1 && window->right >= -1, "doc_mask: window sizes must be non-negative (-1 / None: unbounded on that side)");
+        CHECK_FAIL(!causal || window->right <= 0, "doc_mask: causal = true means window right = 0, got right = ", window->right);
+        wl = window->left;
+        wr = window->right;
+    }
+    if (causal) wr = 0;
+    Tensor prefix;
+    if (prefix_lens.defined()) {
+        CHECK_FAIL(causal, "doc_mask: prefix_lens needs causal = true (without the causal mask every key of the document is visible already)");
+        CHECK_FAIL(prefix_lens.dtype() == ScalarType::Long && prefix_lens.dim() == 2 && prefix_lens.shape(0) == B && prefix_lens.shape(1) == n,
+                   "doc_mask: prefix_lens must be of type Long and shape [B, n_docs] = [", B, ", ", n, "]");
+        CHECK_FAIL(prefix_lens.device() == device, "doc_mask: prefix_lens must be on cu_doclens' device");
+        prefix = prefix_lens.dense();
+    }
+    m.span = true;
+    m.causal = causal;
+    m.window_left = wl;
+    m.window_right = wr;
+    Tensor *tab[4] = {&m.doc_start, &m.doc_end, &m.query_lo, &m.query_hi};
+    for (Tensor *t : tab) *t = empty({B, S}, ScalarType::Int, device);
+    if (B > 0 && S > 0)
+        DEV_CALL(kf_attn_span_table(B, S, n, static_cast<const int64_t *>(cu.data_ptr()), len_ptr(prefix), causal, wl, prefix.defined() ? -1 : wr,
+                                    static_cast<int64_t *>(m.kv_len.data_ptr()), static_cast<int32_t *>(m.doc_start.data_ptr()),
+                                    static_cast<int32_t *>(m.doc_end.data_ptr()), static_cast<int32_t *>(m.query_lo.data_ptr()),
+                                    static_cast<int32_t *>(m.query_hi.data_ptr()), dev::stream(device)));
     return m;
 }
 

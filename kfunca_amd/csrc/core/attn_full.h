@@ -1,5 +1,5 @@
 // namespace gpu: full (non-causal) softmax attention with an optional per-batch key length (kf_attn_full_fwd, kf_attn_full_bwd) and its
-// prefix-LM / padded-causal form (kf_attn_prefix_fwd, kf_attn_prefix_bwd) and its sliding-window form (kf_attn_window_fwd, kf_attn_window_bwd) and its document-masked form for packed rows (kf_attn_doc_fwd, kf_attn_doc_bwd), with autograd. No reference counterpart: the self-attention of a vision / audio encoder (every token sees every token), cross-attention
+// prefix-LM / padded-causal form (kf_attn_prefix_fwd, kf_attn_prefix_bwd) and its sliding-window form (kf_attn_window_fwd, kf_attn_window_bwd) and its document-masked form for packed rows (kf_attn_doc_fwd, kf_attn_doc_bwd; with a window, a causal rule and prefixes inside the documents: kf_attn_span_fwd, kf_attn_span_bwd), with autograd. No reference counterpart: the self-attention of a vision / audio encoder (every token sees every token), cross-attention
 // (Sq text queries over Skv image keys, in either size order) and padded batches (keys beyond a sample's own length are invisible).
 #pragma once
 
@@ -28,6 +28,9 @@ namespace gpu {
 // one row of [B, H, S, D] holds several independent sequences end to end, and query m sees key n iff both lie in the same document
 // (and, with causal = true, n <= m). Self-attention only (Sq = Skv = S of the mask); beside kv_len, prefix_len or a window it is
 // refused. A token in no document (the padded tail of a row) gives a zero row and zero gradients.
+// A mask built with a window, prefixes or causal (doc_mask's second form; kf_attn_span_table, kf_attn_span_fwd, kf_attn_span_bwd) is the
+// way to a sliding window or a prefix-LM mask inside packed documents: the same kernels read its tables, and the call's causal must
+// equal the mask's (a mismatch is refused). kv_len, prefix_len and window beside any doc_mask stay refused.
 struct AttentionWindow { int64_t left, right; };
 // doc_mask(cu_doclens, S): cu_doclens Long [B, n + 1] on the device, the cumulative document lengths of each row (cu[b, 0] = 0; document
 // j holds tokens cu[b, j] <= m < cu[b, j + 1]; a shorter list is padded by repeating its last value; values are clamped to [0, S]).
@@ -37,8 +40,20 @@ struct AttentionWindow { int64_t left, right; };
 struct DocMask {
     Tensor kv_len, doc_start, doc_end;
     int64_t B = 0, S = 0;
+    // the second form only (span = true): doc_start and doc_end are then the keys lo <= n < hi each token sees as a query, query_lo and
+    // query_hi the queries that see it as a key, all with the mask's causal rule, prefixes and window (-1: unbounded) inside
+    Tensor query_lo, query_hi;
+    int64_t window_left = -1, window_right = -1;
+    bool causal = false, span = false;
 };
 DocMask doc_mask(const Tensor &cu_doclens, int64_t S);
+// doc_mask(cu_doclens, S, window, prefix_lens, causal): the document mask and, inside each document, an optional causal rule with a
+// bidirectional prefix and an optional sliding window. With P_j = cu[b, j] + clamp(prefix_lens[b, j], 0, length of document j) query m of
+// document j sees key n of the same document iff (not causal or n <= m or n < P_j) and m - left <= n <= m + right.
+// window: null or attention's {left, right} (-1: unbounded); with causal the right side is 0 (-1 is read as 0, anything else refused)
+// and, where a prefix is given, the causal rule alone: a token sees the keys of its prefix that its left side reaches.
+// prefix_lens: undefined or Long [B, n_docs] on cu_doclens' device; refused without causal. One launch, built once per batch and mask.
+DocMask doc_mask(const Tensor &cu_doclens, int64_t S, const AttentionWindow *window, const Tensor &prefix_lens, bool causal);
 // mods (kf_attn_ext_fwd, kf_attn_ext_bwd): null (the calls above, unchanged: their path and their bits) or the modifiers of the SCORES,
 // which compose with every mask: softcap (has_softcap; positive and finite, else refused) turns each visible score x = q.k / sqrt(D)
 // into softcap tanh(x / softcap) (Gemma-2, Grok); sinks (defined: Float [Hq], dense, on the operands' device, else refused) adds

@@ -1317,6 +1317,58 @@ static __global__ __launch_bounds__(NT) void attn_doc_table_kernel(const int64_t
 }
 
 // ==========================================================================================
+// span table (kf_attn_span_table): the document mask with a causal rule, per-document prefixes and a window baked into the intervals
+// ==========================================================================================
+// The search and the clamps of attn_doc_table_kernel; token m of document j = [cs, ce) with P = cs + clamp(prefix[b, j], 0, ce - cs)
+// (P = cs without prefixes) gets the keys it sees as a query and the queries that see it as a key, each one interval (DESIGN.md section
+// 4.9.6). wl and wr arrive as -1 or clamped to [0, S] (the host), so m - wl and m + wr + 1 stay far inside 64 bits; every value written
+// lies in [cs, ce], hence in [0, S], with lo <= hi.
+static __global__ __launch_bounds__(NT) void attn_span_table_kernel(const int64_t *cu, const int64_t *prefix, int64_t B, int64_t S, int64_t n_docs, int causal,
+                                                             int64_t wl, int64_t wr, int64_t *kv_len, int32_t *key_lo, int32_t *key_hi, int32_t *query_lo,
+                                                             int32_t *query_hi) {
+    const int64_t idx = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (idx >= B * S) return;
+    const int64_t b = idx / S, m = idx - b * S;
+    const int64_t *row = cu + b * (n_docs + 1);
+    auto c = [&](int64_t j) -> int64_t {
+        if (j == 0) return 0;
+        const int64_t x = row[j];
+        return x < 0 ? 0 : (x > S ? S : x);
+    };
+    auto lower = [](int64_t x, int64_t y) { return x < y ? x : y; };
+    auto upper = [](int64_t x, int64_t y) { return x > y ? x : y; };
+    const int64_t len = c(n_docs);
+    if (m == 0) kv_len[b] = len;
+    int64_t klo = len, khi = len, qlo = len, qhi = len;
+    if (m < len) {
+        int64_t lo = 0, hi = n_docs;
+        while (hi - lo > 1) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (c(mid) <= m) lo = mid;
+            else hi = mid;
+        }
+        const int64_t cs = c(lo), ce = c(hi);
+        int64_t P = cs;
+        if (prefix) {
+            const int64_t x = prefix[b * n_docs + lo];
+            P = cs + (x < 0 ? 0 : lower(x, ce - cs));
+        }
+        klo = wl < 0 ? cs : upper(cs, m - wl);
+        khi = causal ? lower(ce, upper(m + 1, P)) : ce;
+        if (wr >= 0) khi = lower(khi, m + wr + 1);
+        qlo = causal && m >= P ? upper(cs, m) : cs;
+        if (wr >= 0) qlo = upper(qlo, m - wr);
+        qhi = wl < 0 ? ce : lower(ce, m + wl + 1);
+        khi = upper(khi, klo);
+        qhi = upper(qhi, qlo);
+    }
+    key_lo[idx] = (int32_t)klo;
+    key_hi[idx] = (int32_t)khi;
+    query_lo[idx] = (int32_t)qlo;
+    query_hi[idx] = (int32_t)qhi;
+}
+
+// ==========================================================================================
 // sink gradient (kf_attn_ext_bwd): dsink[h] = - sum_{b, m < Sq} exp(sink[h] - lse[b,h,m]) delta[b,h,m]
 // ==========================================================================================
 // One workgroup per query head. Thread t adds the terms i = t, t + 256, ... of the head's B Sq rows (b-major) in ascending order, then
@@ -1449,7 +1501,11 @@ template <typename F> static inline int with_mode(Mode mode, F &&f) {
                                              : mode == M_WINDOW ? f(std::integral_constant<int, M_WINDOW>{}) : f(std::integral_constant<int, M_DOC>{});
 }
 struct Window { int64_t left, right; };
-struct DocTables { const int32_t *start, *end; int causal; }; // the document variant's tables ([B, S] on the device) and its causal flag
+// The document variant's tables ([B, S] on the device) and its causal flag. A partition is symmetric, so kf_attn_doc_* hands over one
+// pair that the dK/dV kernels read at the key index too (keyed = false, qstart and qend null). kf_attn_span_* bakes a causal rule, a
+// prefix and a window into the intervals, which are then no longer symmetric: keyed = true, and the dK/dV launches take (qstart, qend),
+// the queries that see each key, in place of (start, end), the keys each query sees.
+struct DocTables { const int32_t *start, *end; int causal; const int32_t *qstart, *qend; bool keyed; };
 struct MaskPlan {
     Mode mode;
     const int64_t *kv_len, *prefix_len; // [B] on the device, or null; prefix_len of KF_ATTN_MASK_PREFIX only
@@ -1472,7 +1528,7 @@ static int mask_check(const char *who, const kf_attn_mask *m, int64_t Sq, int64_
                (long long)m->window_right, m->kind);
     KF_REQUIRE(m->kind == KF_ATTN_MASK_DOC || (!m->doc_start && !m->doc_end && m->causal == 0), KF_ERR_INVALID,
                "%s: doc_start, doc_end and causal belong to KF_ATTN_MASK_DOC, the kind is %d", who, m->kind);
-    p = MaskPlan{(Mode)m->kind, m->kv_len, m->prefix_len, Window{-1, -1}, DocTables{nullptr, nullptr, 0}};
+    p = MaskPlan{(Mode)m->kind, m->kv_len, m->prefix_len, Window{-1, -1}, DocTables{nullptr, nullptr, 0, nullptr, nullptr, false}};
     if (m->kind == KF_ATTN_MASK_WINDOW) {
         KF_REQUIRE(m->window_left >= -1 && m->window_right >= -1, KF_ERR_INVALID, "%s: a window side is a key count >= 0 or -1 (unbounded), not (%lld, %lld)", who,
                    (long long)m->window_left, (long long)m->window_right);
@@ -1481,7 +1537,7 @@ static int mask_check(const char *who, const kf_attn_mask *m, int64_t Sq, int64_
     } else if (m->kind == KF_ATTN_MASK_DOC) {
         KF_REQUIRE(m->causal == 0 || m->causal == 1, KF_ERR_INVALID, "%s: causal is 0 or 1, not %d", who, m->causal);
         KF_REQUIRE(Sq == Skv, KF_ERR_INVALID, "%s: a document mask is self-attention, Sq %lld must equal Skv %lld", who, (long long)Sq, (long long)Skv);
-        p.doc = DocTables{m->doc_start, m->doc_end, m->causal};
+        p.doc = DocTables{m->doc_start, m->doc_end, m->causal, nullptr, nullptr, false};
     }
     return KF_OK;
 }
@@ -1496,7 +1552,8 @@ static int set_mask(const char *who, FullArgs &a, const MaskPlan &p) {
         a.wr = p.win.right < 0 || p.win.right > kNoEdge ? kNoEdge : p.win.right;
     }
     if (p.mode != M_DOC) return KF_OK;
-    KF_REQUIRE(p.doc.start && p.doc.end, KF_ERR_INVALID, "%s: null doc_start or doc_end (kf_attn_doc_table writes them)", who);
+    KF_REQUIRE(p.doc.start && p.doc.end, KF_ERR_INVALID, "%s: null %s writes them)", who,
+               p.doc.keyed ? "key_lo or key_hi (kf_attn_span_table" : "doc_start or doc_end (kf_attn_doc_table");
     KF_REQUIRE(a.Sq < (1ll << 31), KF_ERR_UNSUPPORTED, "%s: the document tables are 32-bit, S must be below 2^31", who);
     a.doc_start = p.doc.start;
     a.doc_end = p.doc.end;
@@ -1569,6 +1626,12 @@ static int full_bwd(const char *who, const char *size_query, const Problem &pr, 
     rc = set_mask(who, a, p);
     if (rc != KF_OK) return rc;
     a.softcap = mod.softcap;
+    FullArgs akv = a; // what the two dK/dV launches take: they read the tables at the key index, a keyed mask has a pair of its own for that
+    if (p.mode == M_DOC && p.doc.keyed) {
+        KF_REQUIRE(p.doc.qstart && p.doc.qend, KF_ERR_INVALID, "%s: null query_lo or query_hi (kf_attn_span_table writes them)", who);
+        akv.doc_start = p.doc.qstart;
+        akv.doc_end = p.doc.qend;
+    }
     hipStream_t st = as_stream(stream);
     const Mode mode = p.mode;
     const Labels &label = kLabels[CAP][mode];
@@ -1591,7 +1654,7 @@ static int full_bwd(const char *who, const char *size_query, const Problem &pr, 
         KF_PROF(label.dkv[d64], st);
         const unsigned grid = (unsigned)(B * Hkv * ((Skv + TQ - 1) / TQ));
         return with_mode(mode, [&](auto M) {
-            return with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dkv_kernel<BF, D64 ? 64 : 128, M, CAP>, grid, NT, KV_LDS, st, a); }, bf, d64);
+            return with_flags([&](auto BF, auto D64) { return launch(attn_full_bwd_dkv_kernel<BF, D64 ? 64 : 128, M, CAP>, grid, NT, KV_LDS, st, akv); }, bf, d64);
         });
     }
     return with_dtype(pr.dtype, [&](auto t) {
@@ -1607,7 +1670,7 @@ static int full_bwd(const char *who, const char *size_query, const Problem &pr, 
             if (rc != KF_OK) return rc;
         }
         KF_PROF(label.generic[2], st);
-        return with_mode(mode, [&](auto M) { return launch(attn_full_bwd_dkv_generic_kernel<T, M, CAP>, (unsigned)(B * Hkv * Skv), NT, 0, st, a); });
+        return with_mode(mode, [&](auto M) { return launch(attn_full_bwd_dkv_generic_kernel<T, M, CAP>, (unsigned)(B * Hkv * Skv), NT, 0, st, akv); });
     });
 }
 

@@ -60,7 +60,7 @@ EXPORTS = [
     "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
     "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa",
     "kf_attn_full_fwd", "kf_attn_full_bwd_workspace_bytes", "kf_attn_full_bwd", "kf_attn_prefix_fwd", "kf_attn_prefix_bwd", "kf_attn_window_fwd", "kf_attn_window_bwd", "kf_attn_doc_table", "kf_attn_doc_fwd", "kf_attn_doc_bwd",
-    "kf_attn_ext_fwd", "kf_attn_ext_bwd_workspace_bytes", "kf_attn_ext_bwd", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
+    "kf_attn_ext_fwd", "kf_attn_ext_bwd_workspace_bytes", "kf_attn_ext_bwd", "kf_attn_span_table", "kf_attn_span_fwd", "kf_attn_span_bwd", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
 ]
 
 
@@ -230,6 +230,10 @@ def lib():
         _lib.kf_attn_ext_bwd_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.POINTER(sz)]
         _lib.kf_attn_ext_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, mp, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp,
                                          vp, lp, vp, lp, vp, lp, vp, vp, sz, vp]
+        _lib.kf_attn_span_table.argtypes = [i64, i64, i64, vp, vp, C.c_int, i64, i64, vp, vp, vp, vp, vp, vp]
+        _lib.kf_attn_span_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, vp, vp, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
+        _lib.kf_attn_span_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, vp, vp, vp, vp, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp,
+                                          vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, sz, vp]
         _lib.kf_rope.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, vp, vp, lp, vp, lp, vp]
         _lib.kf_rope_table.argtypes = [C.c_double, i64, i64, vp, vp, vp]
         _lib.kf_glu_fwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp]
@@ -796,6 +800,34 @@ def attn_ext_bwd(dtype, B, Hq, Hkv, Sq, Skv, D, scale, q, k, v, o, lse, d_o, dq,
     L = _gqa_layouts(layouts, 8)
     check(lib().kf_attn_ext_bwd(dtype, B, Hq, Hkv, Sq, Skv, D, scale, None if mask is None else C.byref(mask), softcap, sink, q, L[0], k, L[1], v,
                                 L[2], o, L[3], lse, d_o, L[4], dq, L[5], dk, L[6], dv, L[7], dsink, workspace, workspace_bytes, stream))
+
+
+def attn_span_table(B, S, n_docs, cu_doclens, kv_len, key_lo, key_hi, query_lo, query_hi, doc_prefix=None, causal=False, window_left=-1,
+                    window_right=-1, stream=None):
+    """The per-token tables of a document mask with a causal rule, per-document prefixes and a window (kf_attn_span_table). cu_doclens:
+    device pointer to int64 [B, n_docs + 1]; doc_prefix: device pointer to int64 [B, n_docs] or None (requires causal); a window side of
+    -1 is unbounded. Written: kv_len int64 [B]; key_lo, key_hi (the keys a query sees) and query_lo, query_hi (the queries that see a
+    key), int32 [B, S] (device pointers)."""
+    check(lib().kf_attn_span_table(B, S, n_docs, cu_doclens, doc_prefix, int(causal), window_left, window_right, kv_len, key_lo, key_hi, query_lo,
+                                   query_hi, stream))
+
+
+def attn_span_fwd(dtype, B, Hq, Hkv, S, D, scale, q, k, v, o, lse=None, kv_len=None, key_lo=None, key_hi=None, softcap=0.0, sink=None, layouts=None,
+                  stream=None):
+    """Attention forward under the tables of attn_span_table (kf_attn_span_fwd), Sq = Skv = S: query m sees key n iff n < kv_len[b] and
+    key_lo[b, m] <= n < key_hi[b, m]. key_lo, key_hi: device pointers to int32 [B, S] (required); softcap and sink as attn_ext_fwd;
+    layouts as attn_full_fwd."""
+    L = _gqa_layouts(layouts, 4)
+    check(lib().kf_attn_span_fwd(dtype, B, Hq, Hkv, S, D, scale, kv_len, key_lo, key_hi, softcap, sink, q, L[0], k, L[1], v, L[2], o, L[3], lse, stream))
+
+
+def attn_span_bwd(dtype, B, Hq, Hkv, S, D, scale, q, k, v, o, lse, d_o, dq, dk, dv, workspace, workspace_bytes, kv_len=None, key_lo=None, key_hi=None,
+                  query_lo=None, query_hi=None, softcap=0.0, sink=None, dsink=None, layouts=None, stream=None):
+    """Attention backward under the tables of attn_span_table (kf_attn_span_bwd): dQ reads (key_lo, key_hi), dK/dV read (query_lo,
+    query_hi). The workspace is attn_full_bwd_workspace_bytes(dtype, B, Hq, Hkv, S, S, D); dsink as attn_ext_bwd; layouts as attn_full_bwd."""
+    L = _gqa_layouts(layouts, 8)
+    check(lib().kf_attn_span_bwd(dtype, B, Hq, Hkv, S, D, scale, kv_len, key_lo, key_hi, query_lo, query_hi, softcap, sink, q, L[0], k, L[1], v, L[2],
+                                 o, L[3], lse, d_o, L[4], dq, L[5], dk, L[6], dv, L[7], dsink, workspace, workspace_bytes, stream))
 
 
 def rope(dtype, B, H, S, D, x, lx, y=None, ly=None, cos=None, sin=None, table_rows=None, rotary_dim=None, h_rot=None, positions=None,
