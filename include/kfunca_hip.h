@@ -260,6 +260,49 @@ int kf_cross_entropy_bwd(int dtype, int64_t rows, int64_t V, int64_t ld, const v
                          float label_smoothing, int reduction, const float *lse, const float *count, const float *grad, void *dlogits,
                          int64_t ldd, void *stream);
 
+/* ---- cross-entropy of a block of logits WITH its gradient (no reference counterpart: the row kernel of a chunked linear + loss) --- */
+/*
+ * kf_ce_fused_rows: one call turns a block of logits into its per-row loss and its gradient, so that a caller walking the tokens in
+ * chunks (kfunca.linear_cross_entropy) never holds more than one chunk of logits.
+ * logits: [rows, V] with row stride `ld` elements (ld >= V), in_dtype in {KF_F32, KF_BF16, KF_F16}; dlogits: [rows, V] with row stride
+ * ldd in out_dtype. Pairs: KF_F32 -> KF_BF16 / KF_F16 / KF_F32 (the f32 accumulators of a c_f32 GEMM -> the operands' dtype is the hot
+ * one) and a 16-bit type to itself. dlogits == logits (in place) is allowed when the dtypes and the strides are equal; any other overlap
+ * is refused. dlogits NULL: the loss only, in one pass over the logits. target: int64 [rows] on the device. Per row, with
+ * p = softmax(x), t = target[r], eps = label_smoothing in [0, 1], z = z_loss >= 0:
+ *     lse_r      = log(sum_v exp(x_rv))
+ *     rowloss_r  = (1 - eps) (lse_r - x_r,t) + eps (lse_r - mean_v x_rv) + z lse_r^2
+ *     dlogits_rv = p_rv (1 + 2 z lse_r) - (1 - eps) [v == t] - eps / V
+ * The gradient is UNSCALED (values in about [-1, 1]): no 1 / count and no upstream gradient is folded in, so f16 never sees a subnormal
+ * gradient and the kernel needs no count beforehand; kf_scale_cast applies both later, to the far smaller dX and dW.
+ * rowloss [rows] f32 is required; lse [rows] f32 may be NULL. A row whose target is ignore_index has loss 0 and a zero gradient row
+ * whatever its logits hold; a target outside [0, V) that is not ignore_index gives that row a NaN loss and a NaN gradient row and
+ * disturbs no other row. -inf logits are fine. The logits are read twice (state, then write), dlogits is written once, in 16-byte packs
+ * where the two rows' alignment allows (element by element otherwise); bytes past V in a strided row stay untouched.
+ * Regimes from (rows, V) only: V <= 4096 one wave per row; else rows >= 1024 one block per row (both ONE launch); else each row splits
+ * into chunks whose partial states go to the workspace of kf_ce_fused_rows_workspace_bytes() bytes (0 in the first two regimes; no
+ * initialisation needed) and are merged in chunk order. No atomics: the same call gives the same bits.
+ *
+ * kf_ce_fused_reduce: loss[0] = the f32 sum of rowloss[0..rows) in a fixed order (mean != 0: divided by the number of rows whose target
+ * is not ignore_index - NaN when every row is ignored, as torch's mean); count [1] f32 (may be NULL) receives that number. One launch
+ * over ALL rows of a chunked loss, after its last chunk.
+ *
+ * kf_scale_cast: out[i] = (out_dtype)(in[i] * s), s = g[0] / count[0] (count NULL: s = g[0]) formed once in f32; g and count are device
+ * f32 scalars, so an upstream gradient and a mean's divisor are applied without a host read. The same dtype pairs; in place (out == in)
+ * when the dtypes are equal, any other overlap is refused. n up to 2^38.
+ *
+ * None of the three synchronises or allocates: all can be captured with kf_graph_*. rows == 0 / n == 0 is KF_OK without a launch.
+ * Every argument is checked before any device call: KF_ERR_INVALID (null pointers, V < 1, ld < V, ldd < V, a dtype pair outside the
+ * list, label_smoothing outside [0, 1], a negative or non-finite z_loss, misaligned pointers, an overlap that is not in place, a
+ * workspace that is too small).
+ */
+int kf_ce_fused_rows_workspace_bytes(int64_t rows, int64_t V, size_t *bytes);
+int kf_ce_fused_rows(int in_dtype, int out_dtype, int64_t rows, int64_t V, int64_t ld, const void *logits, const int64_t *target,
+                     int64_t ignore_index, float label_smoothing, float z_loss, float *rowloss, float *lse, void *dlogits, int64_t ldd,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int kf_ce_fused_reduce(const float *rowloss, const int64_t *target, int64_t rows, int64_t ignore_index, int mean, float *loss, float *count,
+                       void *stream);
+int kf_scale_cast(int in_dtype, int out_dtype, int64_t n, const void *in, void *out, const float *g, const float *count, void *stream);
+
 /* ---- fused AdamW step over a list of tensors (no reference counterpart: the optimizer that applies a gradient to a weight) --- */
 typedef struct kf_adamw_tensor {
     int64_t numel;         /* elements of param, grad, master, exp_avg and exp_avg_sq (all contiguous, any size, 0 included) */

@@ -15,6 +15,7 @@
 #include "device_api.h"
 #include "expert_linear.h"
 #include "glu.h"
+#include "linear_ce.h"
 #include "moe.h"
 #include "softmax.h"
 #include "ops.h"
@@ -379,6 +380,21 @@ PYBIND11_MODULE(_C, m) {
         CHECK_FAIL(r >= 0, reduction, " is not a valid value for reduction");
         return gpu::cross_entropy(logits, target, ignore_index, r, label_smoothing);
     }, py::arg("logits"), py::arg("target"), py::arg("ignore_index") = -100, py::arg("reduction") = "mean", py::arg("label_smoothing") = 0.0);
+    // the LM head and its loss in chunks of chunk_rows tokens, never holding the [T, V] logits; weight is [V, d] (embedding's table layout)
+    m.def("linear_cross_entropy", [](const Tensor &x, const Tensor &weight, const Tensor &target, int64_t ignore_index, const std::string &reduction,
+                                     double label_smoothing, double z_loss, int64_t chunk_rows) {
+        int r = -1;
+        if (reduction == "none") r = KF_CE_NONE;
+        else if (reduction == "sum") r = KF_CE_SUM;
+        else if (reduction == "mean") r = KF_CE_MEAN;
+        CHECK_FAIL(r >= 0, reduction, " is not a valid value for reduction");
+        return gpu::linear_cross_entropy(x, weight, target, ignore_index, r, label_smoothing, z_loss, chunk_rows);
+    }, py::arg("x"), py::arg("weight"), py::arg("target"), py::arg("ignore_index") = -100, py::arg("reduction") = "mean",
+          py::arg("label_smoothing") = 0.0, py::arg("z_loss") = 0.0, py::arg("chunk_rows") = 0);
+    // NOT part of the operator surface (underscore, not in __all__): a hook for the CPU-only ABI test and tools/linear_ce_bench.py, which
+    // reach linear_cross_entropy's chunk_rows check and its default without a device. 0: the default; raises on anything but 0 or a
+    // positive multiple of 128.
+    m.def("_linear_ce_chunk_rows", &gpu::linear_ce_chunk_rows, py::arg("chunk_rows") = 0);
     m.def("gemm_fused", [](const Tensor &a, const Tensor &b, float alpha, py::object bias, py::object mul, py::object add) {
         auto opt = [](py::object o) { return o.is_none() ? Tensor() : o.cast<Tensor>(); };
         return gpu::gemm_fused(a, b, alpha, opt(bias), opt(mul), opt(add));

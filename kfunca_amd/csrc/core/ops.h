@@ -79,6 +79,12 @@ Tensor gemm_fused(const Tensor &a, const Tensor &b, float alpha, const Tensor &b
 //   logits.shape[:-1]; reduction KF_CE_NONE (loss shaped like target), KF_CE_SUM or KF_CE_MEAN ([1]); the loss is f32. A target
 //   outside [0, V) that is not ignore_index gives that row NaN (torch asserts instead).
 Tensor cross_entropy(const Tensor &logits, const Tensor &target, int64_t ignore_index, int reduction, double label_smoothing);
+//   linear_cross_entropy (linear_ce.h): cross_entropy(x weight^T, target) + z_loss * mean-or-sum of lse^2 WITHOUT the [T, V] logits - the tokens
+//   are walked in chunks of chunk_rows rows (0: the default; else a positive multiple of 128) and both gradients are formed in the
+//   forward. x [..., d] and weight [V, d] (the layout of embedding's table: a tied head is the same tensor) share a dtype in f32 / f16 /
+//   bf16, target is Long of x's shape without its last dim, reduction is KF_CE_SUM or KF_CE_MEAN (KF_CE_NONE is refused); the loss is f32 [1].
+Tensor linear_cross_entropy(const Tensor &x, const Tensor &weight, const Tensor &target, int64_t ignore_index, int reduction, double label_smoothing,
+                            double z_loss, int64_t chunk_rows);
 
 // extensions used by the backward passes (no reference counterpart)
 Tensor gemm_ex(const Tensor &a, bool trans_a, const Tensor &b, bool trans_b, float alpha);

@@ -48,6 +48,7 @@ EXPORTS = [
     "kf_reduce_moments_workspace_bytes", "kf_reduce_moments",
     "kf_norm_fwd", "kf_norm_bwd_workspace_bytes", "kf_norm_bwd",
     "kf_cross_entropy_workspace_bytes", "kf_cross_entropy_fwd", "kf_cross_entropy_bwd",
+    "kf_ce_fused_rows_workspace_bytes", "kf_ce_fused_rows", "kf_ce_fused_reduce", "kf_scale_cast",
     "kf_adamw_workspace_bytes", "kf_adamw_step",
     "kf_rope", "kf_rope_table",
     "kf_glu_fwd", "kf_glu_bwd",
@@ -182,6 +183,10 @@ def lib():
         _lib.kf_cross_entropy_workspace_bytes.argtypes = [C.c_int, i64, i64, C.c_int, C.POINTER(sz)]
         _lib.kf_cross_entropy_fwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_int, vp, vp, vp, vp, sz, vp]
         _lib.kf_cross_entropy_bwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_int, vp, vp, vp, vp, i64, vp]
+        _lib.kf_ce_fused_rows_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
+        _lib.kf_ce_fused_rows.argtypes = [C.c_int, C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp, i64, vp, sz, vp]
+        _lib.kf_ce_fused_reduce.argtypes = [vp, vp, i64, i64, C.c_int, vp, vp, vp]
+        _lib.kf_scale_cast.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp, vp]
         _lib.kf_adamw_workspace_bytes.argtypes = [i64, C.c_float, C.POINTER(sz)]
         _lib.kf_adamw_step.argtypes = [C.POINTER(AdamwTensor), i64, C.c_double, C.c_double, C.c_double, vp, C.c_float, C.c_float, vp, vp, sz, vp]
         _lib.kf_index_put.argtypes = [C.POINTER(IterDesc), C.c_int, C.POINTER(i64), C.POINTER(i64), vp]
@@ -555,6 +560,33 @@ def ce_bwd(dtype, rows, V, logits, target, lse, count, grad, dlogits, ignore_ind
     ld = V if ld is None else ld
     check(lib().kf_cross_entropy_bwd(dtype, rows, V, ld, logits, target, ignore_index, float(label_smoothing), reduction, lse, count, grad,
                                      dlogits, ld if ldd is None else ldd, stream))
+
+
+def ce_fused_rows_workspace_bytes(rows, V):
+    need = C.c_size_t(0)
+    check(lib().kf_ce_fused_rows_workspace_bytes(rows, V, C.byref(need)))
+    return need.value
+
+
+def ce_fused_rows(in_dtype, out_dtype, rows, V, logits, target, rowloss, lse=None, dlogits=None, ignore_index=-100, label_smoothing=0.0,
+                  z_loss=0.0, ld=None, ldd=None, stream=None):
+    """Loss and UNSCALED gradient of a block of logits in one call (kf_ce_fused_rows) with scratch of its own; dlogits None: the loss only.
+    Returns the scratch (keep it until the stream is synchronised)."""
+    need = ce_fused_rows_workspace_bytes(rows, V)
+    ws = DevBuf(need) if need else None
+    check(lib().kf_ce_fused_rows(in_dtype, out_dtype, rows, V, V if ld is None else ld, logits, target, ignore_index, float(label_smoothing),
+                                 float(z_loss), rowloss, lse, dlogits, V if ldd is None else ldd, ws.ptr if ws else None, need, stream))
+    return ws
+
+
+def ce_fused_reduce(rowloss, target, rows, loss, count=None, ignore_index=-100, mean=True, stream=None):
+    """The sum (mean: over the rows not ignored) of a chunked loss's row losses, and the count of those rows (kf_ce_fused_reduce)."""
+    check(lib().kf_ce_fused_reduce(rowloss, target, rows, ignore_index, int(bool(mean)), loss, count, stream))
+
+
+def scale_cast(in_dtype, out_dtype, n, src, dst, g, count=None, stream=None):
+    """dst[i] = (out_dtype)(src[i] * g[0] / count[0]) with device scalars g and count (kf_scale_cast); count None: no divisor."""
+    check(lib().kf_scale_cast(in_dtype, out_dtype, n, src, dst, g, count, stream))
 
 
 def adamw_workspace_bytes(n, max_grad_norm=0.0):
