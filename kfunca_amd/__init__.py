@@ -32,7 +32,7 @@ def _load():
     return _native
 
 
-_SUBMODULES = ("_build", "_C", "hip_abi", "parallel")
+_SUBMODULES = ("_abi_header", "_build", "_C", "hip_abi", "parallel")
 
 
 def __getattr__(name):

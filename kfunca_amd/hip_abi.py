@@ -14,55 +14,41 @@ import numpy as np
 
 import os
 
+from . import _abi_header, _build
+
 PKG = Path(__file__).resolve().parent
 # KF_HIP_LIB: load another build of the same library (A/B runs of two kernel variants on one box, tools/ only)
 LIB_PATH = Path(os.environ["KF_HIP_LIB"]) if os.environ.get("KF_HIP_LIB") else PKG / "libkfunca_hip.so"
 
-# dtype codes == reference ScalarType order (src/core/include/scalar_type.h:9-27)
-BOOL, U8, I8, I16, I32, I64, F16, BF16, F32, F64 = range(10)
-DTYPE_SIZE = {BOOL: 1, U8: 1, I8: 1, I16: 2, I32: 4, I64: 8, F16: 2, BF16: 2, F32: 4, F64: 8}
-EW_ADD, EW_SUB, EW_MUL, EW_DIV, EW_COPY, EW_FILL, EW_ADD_SCALAR, EW_SUB_SCALAR, EW_MUL_SCALAR, EW_DIV_SCALAR = range(10)
-RED_SUM, RED_MEAN = range(2)
-MOM_VAR, MOM_STD, MOM_INVSTD = range(3)
-EPI_NONE, EPI_BIAS_ROW = range(2)
-NORM_RMS, NORM_LAYER = range(2)
-CE_NONE, CE_SUM, CE_MEAN = range(3)
-ACT_SILU, ACT_GELU_TANH, ACT_GELU_ERF = range(3)
-SOFTMAX, LOG_SOFTMAX = range(2)
-MAX_DIMS, MAX_TENSORS = 12, 8
-KF_OK, KF_ERR_HIP, KF_ERR_INVALID, KF_ERR_UNSUPPORTED, KF_ERR_INDEX_RANGE, KF_ERR_WORKSPACE, KF_ERR_COMM, KF_ERR_OOM = range(8)
-COMM_ID_BYTES = 128
+HEADER = _abi_header.read((_build.INCLUDE / "kfunca_hip.h").read_text())   # include/kfunca_hip.h is the one statement of the ABI
 
+# The header's enumerators and integer defines under their names here: KF_ dropped, except from the status codes (KF_OK, KF_ERR_*).
+# A name the header lacks fails the import. dtype codes == reference ScalarType order (src/core/include/scalar_type.h:9-27)
+CONSTANTS = (
+    "BOOL", "U8", "I8", "I16", "I32", "I64", "F16", "BF16", "F32", "F64",
+    "EW_ADD", "EW_SUB", "EW_MUL", "EW_DIV", "EW_COPY", "EW_FILL", "EW_ADD_SCALAR", "EW_SUB_SCALAR", "EW_MUL_SCALAR", "EW_DIV_SCALAR",
+    "RED_SUM", "RED_MEAN",
+    "MOM_VAR", "MOM_STD", "MOM_INVSTD",
+    "EPI_NONE", "EPI_BIAS_ROW",
+    "NORM_RMS", "NORM_LAYER",
+    "CE_NONE", "CE_SUM", "CE_MEAN",
+    "ACT_SILU", "ACT_GELU_TANH", "ACT_GELU_ERF",
+    "SOFTMAX", "LOG_SOFTMAX",
+    "ATTN_MASK_FULL", "ATTN_MASK_PREFIX", "ATTN_MASK_WINDOW", "ATTN_MASK_DOC",
+    "MOE_SCORE_SOFTMAX", "MOE_SCORE_SIGMOID",
+    "MAX_DIMS", "MAX_TENSORS", "COMM_ID_BYTES",
+    "KF_OK", "KF_ERR_HIP", "KF_ERR_INVALID", "KF_ERR_UNSUPPORTED", "KF_ERR_INDEX_RANGE", "KF_ERR_WORKSPACE", "KF_ERR_COMM", "KF_ERR_OOM",
+)
+for _n in CONSTANTS:
+    globals()[_n] = HEADER.constants[_n if _n.startswith(("KF_OK", "KF_ERR_")) else "KF_" + _n]
+EXPORTS = HEADER.exports
+
+DTYPE_SIZE = {BOOL: 1, U8: 1, I8: 1, I16: 2, I32: 4, I64: 8, F16: 2, BF16: 2, F32: 4, F64: 8}
 NP2CODE = {np.dtype(np.bool_): BOOL, np.dtype(np.uint8): U8, np.dtype(np.int8): I8, np.dtype(np.int16): I16,
            np.dtype(np.int32): I32, np.dtype(np.int64): I64, np.dtype(np.float16): F16,
            np.dtype(np.float32): F32, np.dtype(np.float64): F64}
 CODE2NP = {BOOL: np.bool_, U8: np.uint8, I8: np.int8, I16: np.int16, I32: np.int32, I64: np.int64,
            F16: np.float16, BF16: np.uint16, F32: np.float32, F64: np.float64}
-
-EXPORTS = [
-    "kf_last_error", "kf_abi_version", "kf_build_source_sha", "kf_device_count", "kf_set_device", "kf_get_device", "kf_malloc", "kf_free",
-    "kf_memcpy_h2d", "kf_memcpy_d2h", "kf_memcpy_d2d", "kf_memset_zero", "kf_stream_create", "kf_stream_destroy",
-    "kf_stream_sync", "kf_stream_wait_event", "kf_device_sync", "kf_event_create", "kf_event_destroy", "kf_event_record", "kf_event_sync",
-    "kf_event_elapsed_ms", "kf_graph_begin_capture", "kf_graph_end_capture", "kf_graph_launch", "kf_graph_destroy", "kf_profile_enable", "kf_profile_reset", "kf_profile_count", "kf_profile_get", "kf_profile_samples", "kf_knobs_reload",
-    "kf_device_props_get", "kf_elementwise", "kf_reduce_workspace_bytes", "kf_reduce",
-    "kf_reduce_moments_workspace_bytes", "kf_reduce_moments",
-    "kf_norm_fwd", "kf_norm_bwd_workspace_bytes", "kf_norm_bwd",
-    "kf_cross_entropy_workspace_bytes", "kf_cross_entropy_fwd", "kf_cross_entropy_bwd",
-    "kf_ce_fused_rows_workspace_bytes", "kf_ce_fused_rows", "kf_ce_fused_reduce", "kf_scale_cast",
-    "kf_adamw_workspace_bytes", "kf_adamw_step",
-    "kf_rope", "kf_rope_table",
-    "kf_glu_fwd", "kf_glu_bwd",
-    "kf_softmax_fwd", "kf_softmax_bwd",
-    "kf_qk_norm_rope_fwd", "kf_qk_norm_rope_bwd_workspace_bytes", "kf_qk_norm_rope_bwd",
-    "kf_segment_offsets", "kf_gemm_segmented_workspace_bytes", "kf_gemm_segmented", "kf_gemm_segmented_wgrad",
-    "kf_moe_plan_workspace_bytes", "kf_moe_plan", "kf_moe_gate_fwd", "kf_moe_gate_bwd", "kf_moe_dispatch", "kf_moe_combine", "kf_moe_combine_bwd",
-    "kf_moe_router_fwd", "kf_moe_router_bwd", "kf_moe_aux_loss_workspace_bytes", "kf_moe_aux_loss_fwd", "kf_moe_aux_loss_bwd",
-    "kf_index_put", "kf_index_get", "kf_index_add_workspace_bytes", "kf_index_add", "kf_sort_workspace_bytes", "kf_sort", "kf_gemm_workspace_bytes", "kf_gemm", "kf_gemm_ex", "kf_gemm_grouped", "kf_gemm_grouped_single_grid", "kf_attn_fwd", "kf_attn_fwd_scaled", "kf_attn_bwd_workspace_bytes",
-    "kf_attn_bwd", "kf_attn_bwd_scaled", "kf_attn_fwd_strided", "kf_attn_bwd_strided",
-    "kf_attn_fwd_gqa", "kf_attn_bwd_gqa_workspace_bytes", "kf_attn_bwd_gqa",
-    "kf_attn_full_fwd", "kf_attn_full_bwd_workspace_bytes", "kf_attn_full_bwd", "kf_attn_prefix_fwd", "kf_attn_prefix_bwd", "kf_attn_window_fwd", "kf_attn_window_bwd", "kf_attn_doc_table", "kf_attn_doc_fwd", "kf_attn_doc_bwd",
-    "kf_attn_ext_fwd", "kf_attn_ext_bwd_workspace_bytes", "kf_attn_ext_bwd", "kf_attn_span_table", "kf_attn_span_fwd", "kf_attn_span_bwd", "kf_comm_unique_id", "kf_comm_init", "kf_comm_destroy", "kf_allreduce_sum", "kf_allreduce_sum_multi",
-]
 
 
 class KfError(RuntimeError):
@@ -71,44 +57,28 @@ class KfError(RuntimeError):
         self.code = code
 
 
-class IterDesc(C.Structure):
+class IterDesc(HEADER.structs["kf_iter_desc"]):
     """kf_iter_desc: post-build() TensorIterator state as a POD."""
-    _fields_ = [("ndim", C.c_int32), ("ntensors", C.c_int32), ("noutputs", C.c_int32), ("reserved", C.c_int32),
-                ("dtype", C.c_int32 * MAX_TENSORS), ("shape", C.c_int64 * MAX_DIMS),
-                ("stride_bytes", (C.c_int64 * MAX_DIMS) * MAX_TENSORS), ("data", C.c_void_p * MAX_TENSORS)]
 
 
-class AdamwTensor(C.Structure):
+class AdamwTensor(HEADER.structs["kf_adamw_tensor"]):
     """kf_adamw_tensor: one tensor of a fused AdamW step (param, grad, optional f32 master, f32 exp_avg / exp_avg_sq, f32 step on the device)."""
-    _fields_ = [("numel", C.c_int64), ("param_dtype", C.c_int), ("grad_dtype", C.c_int), ("param", C.c_void_p), ("grad", C.c_void_p),
-                ("master", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p), ("weight_decay", C.c_float)]
 
 
-class GemmEpilogue(C.Structure):
+class GemmEpilogue(HEADER.structs["kf_gemm_epilogue"]):
     """kf_gemm_epilogue: C = (alpha AB + beta C + bias) o mul + add, aux = the value in brackets."""
-    _fields_ = [("bias", C.c_void_p), ("mul", C.c_void_p), ("ldmul", C.c_int64), ("add", C.c_void_p), ("ldadd", C.c_int64),
-                ("aux", C.c_void_p), ("ldaux", C.c_int64), ("c_f32", C.c_int32)]
 
 
-class GemmProblem(C.Structure):
+class GemmProblem(HEADER.structs["kf_gemm_problem"]):
     """kf_gemm_problem: one product of a kf_gemm_grouped call."""
-    _fields_ = [("trans_a", C.c_int32), ("trans_b", C.c_int32), ("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64), ("alpha", C.c_float),
-                ("beta", C.c_float), ("A", C.c_void_p), ("lda", C.c_int64), ("B", C.c_void_p), ("ldb", C.c_int64), ("C", C.c_void_p), ("ldc", C.c_int64),
-                ("c_f32", C.c_int32)]
 
 
-class AttnLayout(C.Structure):
+class AttnLayout(HEADER.structs["kf_attn_layout"]):
     """kf_attn_layout: element strides of the batch, head and row dims of one attention operand."""
-    _fields_ = [("batch", C.c_int64), ("head", C.c_int64), ("row", C.c_int64)]
 
 
-ATTN_MASK_FULL, ATTN_MASK_PREFIX, ATTN_MASK_WINDOW, ATTN_MASK_DOC = 0, 1, 2, 3
-
-
-class AttnMask(C.Structure):
+class AttnMask(HEADER.structs["kf_attn_mask"]):
     """kf_attn_mask: the mask of kf_attn_ext_*. kind is ATTN_MASK_*; a field of another kind keeps its neutral value (None, -1, 0)."""
-    _fields_ = [("kind", C.c_int), ("kv_len", C.c_void_p), ("prefix_len", C.c_void_p), ("window_left", C.c_int64), ("window_right", C.c_int64),
-                ("doc_start", C.c_void_p), ("doc_end", C.c_void_p), ("causal", C.c_int)]
 
 
 def attn_mask(kind=ATTN_MASK_FULL, kv_len=None, prefix_len=None, window_left=-1, window_right=-1, doc_start=None, doc_end=None, causal=0) -> AttnMask:
@@ -116,11 +86,8 @@ def attn_mask(kind=ATTN_MASK_FULL, kv_len=None, prefix_len=None, window_left=-1,
     return AttnMask(kind, kv_len, prefix_len, window_left, window_right, doc_start, doc_end, int(causal))
 
 
-class DeviceProps(C.Structure):
-    _fields_ = [("name", C.c_char * 256), ("arch", C.c_char * 64), ("compute_units", C.c_int32),
-                ("wavefront_size", C.c_int32), ("max_threads_per_block", C.c_int32), ("clock_khz", C.c_int32),
-                ("memory_clock_khz", C.c_int32), ("memory_bus_bits", C.c_int32), ("lds_per_block", C.c_int64),
-                ("l2_bytes", C.c_int64), ("total_mem", C.c_uint64), ("free_mem", C.c_uint64)]
+class DeviceProps(HEADER.structs["kf_device_props"]):
+    """kf_device_props: what kf_device_props_get reports."""
 
 
 _lib = None
@@ -132,6 +99,16 @@ def build_source_sha() -> str:
     return l.kf_build_source_sha().decode() if hasattr(l, "kf_build_source_sha") else "unstamped"
 
 
+def bind(cdll):
+    """Give every entry of include/kfunca_hip.h that `cdll` exports the restype and argtypes the header declares, and return cdll.
+    libkfunca_hip.so exports all of them; a variant build of some device sources (the mutation library of the tests) exports a subset."""
+    for name, (restype, argtypes) in HEADER.prototypes.items():
+        if hasattr(cdll, name):
+            fn = getattr(cdll, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return cdll
+
+
 def lib():
     """Load libkfunca_hip.so; raises if it has not been built (python -m kfunca_amd._build)."""
     global _lib
@@ -139,137 +116,15 @@ def lib():
         if not LIB_PATH.exists():
             raise ImportError(f"{LIB_PATH} is missing: build it with `python -m kfunca_amd._build` "
                               "(there is no CPU fallback)")
-        _lib = C.CDLL(str(LIB_PATH))
-        _lib.kf_last_error.restype = C.c_char_p
-        if hasattr(_lib, "kf_build_source_sha"):   # (a diagnostic variant library under KF_HIP_LIB is linked without the stamp)
-            _lib.kf_build_source_sha.restype = C.c_char_p
-            # a library that was NOT built from the sources beside it must not pass for them (a failed rebuild leaves the old .so behind):
-            # refuse it unless told otherwise (KF_ALLOW_STALE_LIB=1)
-            from . import _build
-            if (_build.CSRC / "device").exists() and not os.environ.get("KF_ALLOW_STALE_LIB"):
-                built, tree = _lib.kf_build_source_sha().decode(), _build.device_src_sha()
-                if built != tree:
-                    _lib = None
-                    raise ImportError(f"{LIB_PATH} was built from device sources {built}, the tree is {tree}: rebuild it (python -m kfunca_amd._build); "
-                                      "KF_ALLOW_STALE_LIB=1 loads it anyway")
-        vp, i64, sz = C.c_void_p, C.c_int64, C.c_size_t
-        _lib.kf_malloc.argtypes = [C.POINTER(vp), sz]
-        _lib.kf_free.argtypes = [vp]
-        for n in ("kf_memcpy_h2d", "kf_memcpy_d2h", "kf_memcpy_d2d"):
-            getattr(_lib, n).argtypes = [vp, vp, sz, vp]
-        _lib.kf_memset_zero.argtypes = [vp, sz, vp]
-        _lib.kf_stream_create.argtypes = [C.POINTER(vp)]
-        _lib.kf_stream_destroy.argtypes = [vp]
-        _lib.kf_stream_sync.argtypes = [vp]
-        _lib.kf_stream_wait_event.argtypes = [vp, vp]
-        _lib.kf_event_create.argtypes = [C.POINTER(vp)]
-        _lib.kf_event_destroy.argtypes = [vp]
-        _lib.kf_event_record.argtypes = [vp, vp]
-        _lib.kf_event_sync.argtypes = [vp]
-        _lib.kf_event_elapsed_ms.argtypes = [vp, vp, C.POINTER(C.c_float)]
-        _lib.kf_graph_begin_capture.argtypes = [vp]
-        _lib.kf_graph_end_capture.argtypes = [vp, C.POINTER(vp)]
-        _lib.kf_graph_launch.argtypes = [vp, vp]
-        _lib.kf_graph_destroy.argtypes = [vp]
-        _lib.kf_device_props_get.argtypes = [C.c_int, C.POINTER(DeviceProps)]
-        _lib.kf_elementwise.argtypes = [C.c_int, C.POINTER(IterDesc), C.c_int, C.c_double, vp]
-        _lib.kf_reduce_workspace_bytes.argtypes = [C.POINTER(IterDesc), C.POINTER(sz)]
-        _lib.kf_reduce.argtypes = [C.c_int, C.POINTER(IterDesc), vp, sz, vp]
-        _lib.kf_reduce_moments_workspace_bytes.argtypes = [C.POINTER(IterDesc), C.POINTER(sz)]
-        _lib.kf_reduce_moments.argtypes = [C.c_int, C.POINTER(IterDesc), C.c_double, C.c_double, vp, sz, vp]
-        _lib.kf_norm_fwd.argtypes = [C.c_int, C.c_int, i64, i64, i64, vp, vp, vp, C.c_double, vp, vp, vp, vp]
-        _lib.kf_norm_bwd_workspace_bytes.argtypes = [C.c_int, C.c_int, i64, i64, i64, C.POINTER(sz)]
-        _lib.kf_norm_bwd.argtypes = [C.c_int, C.c_int, i64, i64, i64] + [vp] * 9 + [sz, vp]
-        _lib.kf_cross_entropy_workspace_bytes.argtypes = [C.c_int, i64, i64, C.c_int, C.POINTER(sz)]
-        _lib.kf_cross_entropy_fwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_int, vp, vp, vp, vp, sz, vp]
-        _lib.kf_cross_entropy_bwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_int, vp, vp, vp, vp, i64, vp]
-        _lib.kf_ce_fused_rows_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
-        _lib.kf_ce_fused_rows.argtypes = [C.c_int, C.c_int, i64, i64, i64, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp, i64, vp, sz, vp]
-        _lib.kf_ce_fused_reduce.argtypes = [vp, vp, i64, i64, C.c_int, vp, vp, vp]
-        _lib.kf_scale_cast.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp, vp]
-        _lib.kf_adamw_workspace_bytes.argtypes = [i64, C.c_float, C.POINTER(sz)]
-        _lib.kf_adamw_step.argtypes = [C.POINTER(AdamwTensor), i64, C.c_double, C.c_double, C.c_double, vp, C.c_float, C.c_float, vp, vp, sz, vp]
-        _lib.kf_index_put.argtypes = [C.POINTER(IterDesc), C.c_int, C.POINTER(i64), C.POINTER(i64), vp]
-        _lib.kf_index_get.argtypes = [vp, i64, i64, vp, i64, vp, vp]
-        _lib.kf_index_add_workspace_bytes.argtypes = [i64]
-        _lib.kf_index_add_workspace_bytes.restype = sz
-        _lib.kf_index_add.argtypes = [C.c_int, vp, i64, vp, i64, i64, vp, vp, sz, vp]
-        _lib.kf_sort_workspace_bytes.argtypes = [C.c_int, i64, i64]
-        _lib.kf_sort_workspace_bytes.restype = sz
-        _lib.kf_sort.argtypes = [C.c_int, vp, vp, vp, i64, i64, C.c_int, vp, sz, vp]
-        _lib.kf_gemm_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64, i64, C.POINTER(sz)]
-        _lib.kf_gemm.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64, i64, C.c_float, vp, i64, vp, i64, C.c_float,
-                                 vp, i64, C.c_int, vp, vp, sz, vp]
-        _lib.kf_gemm_ex.argtypes = [C.c_int, C.c_int, C.c_int, i64, i64, i64, C.c_float, vp, i64, vp, i64, C.c_float, vp, i64,
-                                    C.POINTER(GemmEpilogue), vp]
-        _lib.kf_gemm_grouped.argtypes = [C.c_int, C.c_int, C.POINTER(GemmProblem), vp]
-        _lib.kf_attn_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp]
-        _lib.kf_attn_bwd_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.POINTER(sz)]
-        _lib.kf_attn_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64] + [vp] * 10 + [sz, vp]
-        _lib.kf_attn_fwd_scaled.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, vp, vp, vp, vp, vp]
-        _lib.kf_attn_bwd_scaled.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float] + [vp] * 10 + [sz, vp]
-        lp = C.POINTER(AttnLayout)
-        _lib.kf_attn_fwd_strided.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
-        _lib.kf_attn_bwd_strided.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp, vp, lp, vp, lp,
-                                             vp, lp, vp, sz, vp]
-        _lib.kf_attn_fwd_gqa.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
-        _lib.kf_attn_bwd_gqa_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.POINTER(sz), C.POINTER(sz)]
-        _lib.kf_attn_bwd_gqa.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp, vp, lp, vp, lp,
-                                         vp, lp, vp, sz, vp]
-        _lib.kf_attn_full_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
-        _lib.kf_attn_full_bwd_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.POINTER(sz)]
-        _lib.kf_attn_full_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp, vp, lp,
-                                          vp, lp, vp, lp, vp, sz, vp]
-        _lib.kf_attn_prefix_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
-        _lib.kf_attn_prefix_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp, vp, lp,
-                                            vp, lp, vp, lp, vp, sz, vp]
-        _lib.kf_attn_window_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, i64, i64, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
-        _lib.kf_attn_window_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, vp, i64, i64, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp,
-                                            vp, lp, vp, lp, vp, lp, vp, sz, vp]
-        _lib.kf_attn_doc_table.argtypes = [i64, i64, i64, vp, vp, vp, vp, vp]
-        _lib.kf_attn_doc_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, C.c_int, vp, vp, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
-        _lib.kf_attn_doc_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, C.c_int, vp, vp, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp,
-                                         vp, lp, vp, lp, vp, lp, vp, sz, vp]
-        mp = C.POINTER(AttnMask)
-        _lib.kf_attn_ext_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, mp, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
-        _lib.kf_attn_ext_bwd_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.POINTER(sz)]
-        _lib.kf_attn_ext_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_float, mp, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, lp,
-                                         vp, lp, vp, lp, vp, lp, vp, vp, sz, vp]
-        _lib.kf_attn_span_table.argtypes = [i64, i64, i64, vp, vp, C.c_int, i64, i64, vp, vp, vp, vp, vp, vp]
-        _lib.kf_attn_span_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, vp, vp, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp, vp]
-        _lib.kf_attn_span_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, C.c_float, vp, vp, vp, vp, vp, C.c_float, vp, vp, lp, vp, lp, vp, lp, vp, lp, vp,
-                                          vp, lp, vp, lp, vp, lp, vp, lp, vp, vp, sz, vp]
-        _lib.kf_rope.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, vp, vp, lp, vp, lp, vp]
-        _lib.kf_rope_table.argtypes = [C.c_double, i64, i64, vp, vp, vp]
-        _lib.kf_glu_fwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp]
-        _lib.kf_glu_bwd.argtypes = [C.c_int, C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
-        _lib.kf_softmax_fwd.argtypes = [C.c_int, C.c_int, i64, i64, C.c_float, vp, i64, vp, i64, vp]
-        _lib.kf_softmax_bwd.argtypes = [C.c_int, C.c_int, i64, i64, C.c_float, vp, i64, vp, i64, vp, i64, vp]
-        _lib.kf_qk_norm_rope_fwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, i64, C.c_int, C.c_double, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64,
-                                             vp]
-        _lib.kf_qk_norm_rope_bwd_workspace_bytes.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, C.POINTER(sz)]
-        _lib.kf_qk_norm_rope_bwd.argtypes = [C.c_int, i64, i64, i64, i64, i64, i64, i64, C.c_int, C.c_double, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64,
-                                             vp, i64, vp, vp, vp, sz, vp]
-        _lib.kf_segment_offsets.argtypes = [vp, i64, i64, vp, vp]
-        _lib.kf_gemm_segmented_workspace_bytes.argtypes = [C.c_int, i64, i64, C.POINTER(sz)]
-        _lib.kf_gemm_segmented.argtypes = [C.c_int, C.c_int, i64, i64, i64, i64, vp, C.c_float, vp, i64, vp, i64, i64, C.c_float, vp, i64, vp, sz, vp]
-        _lib.kf_gemm_segmented_wgrad.argtypes = [C.c_int, i64, i64, i64, i64, vp, C.c_float, vp, i64, vp, i64, C.c_float, vp, i64, i64, vp, sz, vp]
-        _lib.kf_moe_plan_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
-        _lib.kf_moe_plan.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]
-        _lib.kf_moe_gate_fwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_int, vp, i64, vp]
-        _lib.kf_moe_gate_bwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, C.c_int, vp, i64, vp, i64, vp, i64, vp]
-        _lib.kf_moe_dispatch.argtypes = [C.c_int, i64, i64, i64, vp, vp, i64, vp, i64, vp]
-        _lib.kf_moe_combine.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp]
-        _lib.kf_moe_combine_bwd.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
-        _lib.kf_moe_router_fwd.argtypes = [C.c_int, i64, i64, i64, C.c_int, C.c_int, vp, i64, vp, vp, i64, vp]
-        _lib.kf_moe_router_bwd.argtypes = [C.c_int, i64, i64, i64, C.c_int, C.c_int, vp, i64, vp, vp, i64, vp, i64, vp]
-        _lib.kf_moe_aux_loss_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
-        _lib.kf_moe_aux_loss_fwd.argtypes = [C.c_int, i64, i64, i64, vp, i64, vp, C.c_float, C.c_float, vp, vp, vp, sz, vp]
-        _lib.kf_moe_aux_loss_bwd.argtypes = [C.c_int, i64, i64, i64, vp, i64, vp, C.c_float, C.c_float, vp, vp, i64, vp]
-        _lib.kf_comm_unique_id.argtypes = [C.c_char_p]
-        _lib.kf_comm_init.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int, C.c_int]
-        _lib.kf_comm_destroy.argtypes = [vp]
-        _lib.kf_allreduce_sum.argtypes = [vp, vp, sz, C.c_int, vp]
+        loaded = bind(C.CDLL(str(LIB_PATH)))
+        # a library that was NOT built from the sources beside it must not pass for them (a failed rebuild leaves the old .so behind):
+        # refuse it unless told otherwise (KF_ALLOW_STALE_LIB=1). (A diagnostic variant library under KF_HIP_LIB is linked without the stamp.)
+        if hasattr(loaded, "kf_build_source_sha") and (_build.CSRC / "device").exists() and not os.environ.get("KF_ALLOW_STALE_LIB"):
+            built, tree = loaded.kf_build_source_sha().decode(), _build.device_src_sha()
+            if built != tree:
+                raise ImportError(f"{LIB_PATH} was built from device sources {built}, the tree is {tree}: rebuild it (python -m kfunca_amd._build); "
+                                  "KF_ALLOW_STALE_LIB=1 loads it anyway")
+        _lib = loaded
     return _lib
 
 
@@ -1002,9 +857,6 @@ def moe_combine_bwd(dtype, T, k, cols, pair_row, n_valid, gate, ldg, ys, ldys, d
     """kf_moe_combine_bwd: dys[pair_row[t, j], :] = gate[t, j] dy[t, :] (+0 for a dropped pair) and dgate[t, j] = dy[t, :] . ys[row, :], in
     one pass; dgate None skips the dot products (ys may then be None)."""
     check(lib().kf_moe_combine_bwd(dtype, T, k, cols, pair_row, n_valid, gate, ldg, ys, ldys, dy, lddy, dys, lddys, dgate, lddg, stream))
-
-
-MOE_SCORE_SOFTMAX, MOE_SCORE_SIGMOID = range(2)
 
 
 def moe_router_fwd(dtype, T, E, k, score, normalize, logits, ldl, ids, gate, ldg, stream=None):

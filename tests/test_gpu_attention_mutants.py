@@ -25,10 +25,7 @@ MUT = _build.BUILD / "libkfunca_hip_mutant.so"
 def mut():
     if not MUT.exists():
         _build.build_mutant()
-    lib = C.CDLL(str(MUT))
-    lib.kf_attn_fwd.argtypes = [C.c_int] + [C.c_int64] * 5 + [C.c_void_p] * 6
-    lib.kf_attn_bwd.argtypes = [C.c_int] + [C.c_int64] * 5 + [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p]
-    lib.kf_attn_bwd_workspace_bytes.argtypes = [C.c_int] + [C.c_int64] * 5 + [C.POINTER(C.c_size_t)]
+    lib = H.bind(C.CDLL(str(MUT)))
     yield lib
     lib.kfmut_select(0)
 
