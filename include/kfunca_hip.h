@@ -1070,6 +1070,43 @@ int kf_moe_aux_loss_bwd(int dtype, int64_t T, int64_t E, int64_t k, const void *
                         float balance_coef, float z_coef, const float *dloss /* device, [1] */, void *dlogits, int64_t lddl,
                         void *stream);
 
+/* ---- per-tensor scaled FP8 on the block-scaled matrix pipe (no reference counterpart: the Transformer-Engine recipe with current
+ *      scaling). FP8 data are bytes in the OCP encodings gfx950 uses: e4m3fn (largest value 448, no infinity, NaN =
+ *      0x7f / 0xff) and e5m2 (largest finite value 57344). ---- */
+/*
+ *     fp8_amax      *amax = max |x| over the row-pitched [rows, cols] matrix x (KF_F32, KF_F16 or KF_BF16; ld in elements, >= cols). The
+ *                   entry zeroes *amax on the stream (a one-lane launch) and the kernel combines per-wave partials with an integer atomic max
+ *                   on the bits of |float(x)|: the result does not depend on block order. Any NaN in x gives the quiet NaN 0x7fc00000
+ *                   (its bits lie above every number's). rows * cols == 0 gives 0.
+ *     fp8_quantize  scale = 2^e, e the largest integer with amax * 2^e <= fmt_max (448 = 0.875 * 2^9, 57344 = 0.875 * 2^16: e follows
+ *                   from frexp(amax) and one compare of its mantissa with 0.875), clamped to [-126, 126]; e = 0 when *amax is 0,
+ *                   infinite or NaN. *scale_inv = 2^-e, exactly. q[r, c] = cvt_rne(clamp(float(x[r, c]) * scale, -fmt_max, fmt_max)):
+ *                   the product by a power of two is exact, the clamp is explicit (no mode register decides saturation), and a NaN
+ *                   becomes 0x7f with x's sign bit. q is [rows, cols] bytes with pitch ldq >= cols. qt (may be NULL) is the transposed
+ *                   image [cols, rows] of the same bytes with pitch ldqt >= ceil16(rows); columns rows .. ceil16(rows) - 1 of each of
+ *                   its rows are written as zero bytes, so a product may contract over ceil16(rows). q and qt come from ONE read of x.
+ *                   No other byte of q or qt is written. amax is read on the device (kf_fp8_amax's result, or any caller's bound).
+ *     gemm_fp8      C[M, N] = (*scale_inv_a * *scale_inv_b) A[M, K] B[N, K]^T: both operands K-contiguous bytes (the only layout; the
+ *                   transposed copies of fp8_quantize supply the other products), f32 accumulation on
+ *                   v_mfma_scale_f32_16x16x128_f8f6f4 with every block scale 1.0, one rounding to out_dtype (KF_F32, KF_BF16, KF_F16).
+ *                   The two scales are read on the device. All four format pairs. M, N >= 0 (0: KF_OK without a launch); K a positive
+ *                   multiple of 16; lda, ldb multiples of 16, >= K and at most 2^24; A and B 16-byte aligned, C aligned to its element;
+ *                   ldc >= N. A K tail short of 128 and ragged M / N edges are handled in the kernel by range-checked loads (bytes
+ *                   outside [rows, K] are never read into a result) and guarded stores. No workspace, no padded copies, no split-K:
+ *                   two runs give the same bits.
+ * Nothing synchronises, allocates or reads a value back: every entry can be captured with kf_graph_*. Profile labels fp8_amax,
+ * fp8_quantize, gemm_fp8. Every argument is checked before any device call, with the entry's name in kf_last_error(): KF_ERR_INVALID for
+ * a dtype, format or out_dtype outside the lists, negative extents, a leading dimension below its extent (ldqt < ceil16(rows)) or not a
+ * multiple of 16 where that is required, K not a positive multiple of 16, null or misaligned pointers.
+ */
+enum { KF_FP8_E4M3 = 0, KF_FP8_E5M2 = 1 };
+int kf_fp8_amax(int dtype, int64_t rows, int64_t cols, int64_t ld, const void *x, float *amax /* device, [1] */, void *stream);
+int kf_fp8_quantize(int dtype, int fmt, int64_t rows, int64_t cols, int64_t ld, const void *x, const float *amax /* device, [1] */,
+                    void *q, int64_t ldq, void *qt /* or NULL */, int64_t ldqt, float *scale_inv /* device, [1] */, void *stream);
+int kf_gemm_fp8(int fmt_a, int fmt_b, int out_dtype, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda, const void *B,
+                int64_t ldb, const float *scale_inv_a /* device, [1] */, const float *scale_inv_b /* device, [1] */, void *C,
+                int64_t ldc, void *stream);
+
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128
 int kf_comm_unique_id(char id[KF_COMM_ID_BYTES]);

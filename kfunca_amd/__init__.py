@@ -16,7 +16,7 @@ import importlib
 __all__ = ["device_info", "memstat", "dtype", "empty", "empty_like", "from_numpy", "to_numpy", "zeros",
            "causal_attention", "gemm", "cat", "tensor",
            # extensions over the reference surface
-           "rms_norm", "layer_norm", "embedding", "cross_entropy", "linear_cross_entropy", "AdamW", "rope_table", "rope", "rope_qkv", "qk_norm_rope", "swiglu", "geglu", "silu", "gelu", "softmax", "log_softmax", "segment_offsets", "expert_linear", "moe_plan", "MoePlan", "moe_gate", "moe_dispatch", "moe_combine", "moe_route", "moe_aux_loss", "causal_attention_qkv", "causal_attention_gqa", "attention", "attention_qkv", "doc_mask", "DocMask", "gemm_fused", "qkv_linear", "from_numpy_bf16", "device_count", "synchronize", "memstat_dict", "graph_begin", "graph_end", "graph_launch", "graph_destroy"]
+           "rms_norm", "layer_norm", "embedding", "cross_entropy", "linear_cross_entropy", "fp8_quantize", "gemm_fp8", "linear_fp8", "AdamW", "rope_table", "rope", "rope_qkv", "qk_norm_rope", "swiglu", "geglu", "silu", "gelu", "softmax", "log_softmax", "segment_offsets", "expert_linear", "moe_plan", "MoePlan", "moe_gate", "moe_dispatch", "moe_combine", "moe_route", "moe_aux_loss", "causal_attention_qkv", "causal_attention_gqa", "attention", "attention_qkv", "doc_mask", "DocMask", "gemm_fused", "qkv_linear", "from_numpy_bf16", "device_count", "synchronize", "memstat_dict", "graph_begin", "graph_end", "graph_launch", "graph_destroy"]
 
 _native = None
 

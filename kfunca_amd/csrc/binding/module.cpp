@@ -14,6 +14,7 @@
 #include "comm.h"
 #include "device_api.h"
 #include "expert_linear.h"
+#include "fp8.h"
 #include "glu.h"
 #include "linear_ce.h"
 #include "moe.h"
@@ -395,6 +396,34 @@ PYBIND11_MODULE(_C, m) {
     // reach linear_cross_entropy's chunk_rows check and its default without a device. 0: the default; raises on anything but 0 or a
     // positive multiple of 128.
     m.def("_linear_ce_chunk_rows", &gpu::linear_ce_chunk_rows, py::arg("chunk_rows") = 0);
+    // per-tensor scaled FP8 (fp8.h): FP8 codes travel as Byte tensors, the format as "e4m3" / "e5m2"
+    auto fp8_fmt = [](const std::string &fmt) {
+        CHECK_FAIL(fmt == "e4m3" || fmt == "e5m2", fmt, " is not an FP8 format: e4m3 or e5m2");
+        return fmt == "e4m3" ? KF_FP8_E4M3 : KF_FP8_E5M2;
+    };
+    m.def("fp8_quantize", [fp8_fmt](const Tensor &x, const std::string &fmt, bool transpose) {
+        const gpu::Fp8Quantized r = gpu::fp8_quantize(x, fp8_fmt(fmt), transpose);
+        return py::make_tuple(r.q, transpose ? py::cast(r.qt) : py::object(py::none()), r.scale_inv);
+    }, py::arg("x"), py::arg("fmt") = "e4m3", py::arg("transpose") = false,
+          "fp8_quantize(x [..., cols], fmt='e4m3', transpose=False) -> (q, qt or None, scale_inv): q Byte [rows, cols] = the FP8 codes of x * 2^e, "
+          "e the largest integer with max|x| * 2^e <= the format's maximum (448 / 57344); qt Byte [cols, ceil16(rows)] = the transposed codes "
+          "with zero bytes in the pad columns; scale_inv Float [1] = 2^-e on the device. float, half or bfloat16; x may be row-pitched. "
+          "Nothing is read back to the host.");
+    m.def("gemm_fp8", [fp8_fmt](const Tensor &a_q, const Tensor &b_q, const Tensor &scale_inv_a, const Tensor &scale_inv_b, const std::string &fmt_a,
+                                const std::string &fmt_b, ScalarType out_dtype) {
+        return gpu::gemm_fp8(a_q, b_q, scale_inv_a, scale_inv_b, fp8_fmt(fmt_a), fp8_fmt(fmt_b), out_dtype);
+    }, py::arg("a_q"), py::arg("b_q"), py::arg("scale_inv_a"), py::arg("scale_inv_b"), py::arg("fmt_a") = "e4m3", py::arg("fmt_b") = "e4m3",
+          py::arg("out_dtype") = ScalarType::BFloat16,
+          "gemm_fp8(a_q [M, K], b_q [N, K], scale_inv_a, scale_inv_b, fmt_a='e4m3', fmt_b='e4m3', out_dtype=bfloat16) -> [M, N] = "
+          "scale_inv_a * scale_inv_b * a_q b_q^T, f32 accumulation on the block-scaled matrix pipe. Byte operands with unit stride along K; K "
+          "and the row strides are multiples of 16.");
+    m.def("linear_fp8", &gpu::linear_fp8, py::arg("x"), py::arg("weight"),
+          "linear_fp8(x [..., K], weight [N, K]) -> [..., N] in x's dtype (float, half, bfloat16): both operands quantised to e4m3 with "
+          "per-tensor power-of-two scales. Differentiable in x and weight: the backward quantises dy to e5m2 and keeps only the transposed FP8 "
+          "copies of x and weight and the two scales. K and N must be multiples of 16. No host synchronisation: forward and backward capture "
+          "into a graph.");
+    // NOT part of the operator surface: linear_fp8's shape rule without a device, for the CPU-only ABI test
+    m.def("_linear_fp8_check_dims", &gpu::linear_fp8_check_dims, py::arg("K"), py::arg("N"));
     m.def("gemm_fused", [](const Tensor &a, const Tensor &b, float alpha, py::object bias, py::object mul, py::object add) {
         auto opt = [](py::object o) { return o.is_none() ? Tensor() : o.cast<Tensor>(); };
         return gpu::gemm_fused(a, b, alpha, opt(bias), opt(mul), opt(add));

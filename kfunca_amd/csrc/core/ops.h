@@ -86,6 +86,13 @@ Tensor cross_entropy(const Tensor &logits, const Tensor &target, int64_t ignore_
 Tensor linear_cross_entropy(const Tensor &x, const Tensor &weight, const Tensor &target, int64_t ignore_index, int reduction, double label_smoothing,
                             double z_loss, int64_t chunk_rows);
 
+//   fp8_quantize, gemm_fp8, linear_fp8 (fp8.h): per-tensor scaled FP8 on the block-scaled matrix pipe - x [..., K] weight [N, K]^T with both
+//   operands quantised to e4m3 and dy to e5m2, power-of-two scales from the device-side amax, FP8 copies kept for the backward
+struct Fp8Quantized;
+Fp8Quantized fp8_quantize(const Tensor &x, int fmt, bool transpose);
+Tensor gemm_fp8(const Tensor &a_q, const Tensor &b_q, const Tensor &scale_inv_a, const Tensor &scale_inv_b, int fmt_a, int fmt_b, ScalarType out_dtype);
+Tensor linear_fp8(const Tensor &x, const Tensor &weight);
+
 // extensions used by the backward passes (no reference counterpart)
 Tensor gemm_ex(const Tensor &a, bool trans_a, const Tensor &b, bool trans_b, float alpha);
 std::tuple<Tensor, Tensor> causal_attention_fwd(const Tensor &q, const Tensor &k, const Tensor &v); // (out, lse)

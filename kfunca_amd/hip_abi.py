@@ -36,6 +36,7 @@ CONSTANTS = (
     "SOFTMAX", "LOG_SOFTMAX",
     "ATTN_MASK_FULL", "ATTN_MASK_PREFIX", "ATTN_MASK_WINDOW", "ATTN_MASK_DOC",
     "MOE_SCORE_SOFTMAX", "MOE_SCORE_SIGMOID",
+    "FP8_E4M3", "FP8_E5M2",
     "MAX_DIMS", "MAX_TENSORS", "COMM_ID_BYTES",
     "KF_OK", "KF_ERR_HIP", "KF_ERR_INVALID", "KF_ERR_UNSUPPORTED", "KF_ERR_INDEX_RANGE", "KF_ERR_WORKSPACE", "KF_ERR_COMM", "KF_ERR_OOM",
 )
@@ -816,6 +817,22 @@ def gemm_segmented_wgrad(dtype, T, M, N, E, offsets, alpha, A, lda, B, ldb, beta
     """kf_gemm_segmented_wgrad: dW_e = alpha A[seg_e, :]^T B[seg_e, :] + beta dW_e with A [T, M], B [T, N], dW_e = dW + e dw_stride."""
     check(lib().kf_gemm_segmented_wgrad(dtype, T, M, N, E, offsets, alpha, A, lda, B, ldb, beta, dW, lddw, dw_stride, workspace, workspace_bytes,
                                         stream))
+
+
+def fp8_amax(dtype, rows, cols, ld, x, amax, stream=None):
+    """kf_fp8_amax: *amax (device f32) = max |x| over the row-pitched [rows, cols] matrix; a NaN in x gives NaN; 0 for an empty matrix."""
+    check(lib().kf_fp8_amax(dtype, rows, cols, ld, x, amax, stream))
+
+
+def fp8_quantize(dtype, fmt, rows, cols, ld, x, amax, q, ldq, scale_inv, qt=None, ldqt=0, stream=None):
+    """kf_fp8_quantize: q [rows, cols] (and qt [cols, ceil16(rows)], zero-padded, when given) = the FP8 codes of x * 2^e, e the largest
+    integer with *amax * 2^e <= the format's maximum; *scale_inv = 2^-e. amax and scale_inv are device pointers."""
+    check(lib().kf_fp8_quantize(dtype, fmt, rows, cols, ld, x, amax, q, ldq, qt, ldqt, scale_inv, stream))
+
+
+def gemm_fp8(fmt_a, fmt_b, out_dtype, M, N, K, A, lda, B, ldb, scale_inv_a, scale_inv_b, Cp, ldc, stream=None):
+    """kf_gemm_fp8: C [M, N] (out_dtype) = *scale_inv_a * *scale_inv_b * A [M, K] B [N, K]^T over FP8 bytes, both K-contiguous."""
+    check(lib().kf_gemm_fp8(fmt_a, fmt_b, out_dtype, M, N, K, A, lda, B, ldb, scale_inv_a, scale_inv_b, Cp, ldc, stream))
 
 
 def moe_plan_workspace_bytes(T, k, E) -> int:
