@@ -24,23 +24,16 @@
 LDS waits are COUNTED and inserted by the generator (`finish_waits`): before an instruction that reads the destination of a pending LDS
 read, s_waitcnt lgkmcnt(N) with N = the reads issued after that one."""
 import argparse
+import functools
 import os
 import re
 import sys
 from pathlib import Path
 
+import asm_stream
+from asm_stream import A, Ins, V, ar, m0_write, render, sr, vr  # noqa: F401
+
 ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT / "tools"))
-from gen_attn_fwd import A, Ins, V, ar, render, vr  # noqa: E402
-
-
-def sr(i, n=1):
-    """s-register text; a read-only input operand ("%[name]") passes through."""
-    if isinstance(i, str):
-        return i
-    return f"s{i}" if n == 1 else f"s[{i}:{i + n - 1}]"
-
-
 OUT = ROOT / "kfunca_amd" / "csrc" / "device" / "attn_dkv_w4.inc"
 
 # ------------------------------------------------------------------ register map
@@ -96,7 +89,7 @@ LDS_BYTES = STAGE0 + 4 * 64 * STAGE_ROW
 DS_TILE = 2048
 
 
-class Gen:
+class Gen(asm_stream.Emitter):
     # non-temporal: measured same-box against write-through (sc0 sc1), sc1 and plain stores (tools/scratch/ab_dkv.sh): this kernel's time is the same
     # under all four (1.99 - 2.04 ms on that box), the dQ kernel that streams the dS back runs 3 - 4 % faster behind nt stores (0.95 - 0.97 vs 1.00 ms)
     store_policy = "nt"
@@ -107,8 +100,8 @@ class Gen:
         # the k-steps and half the column blocks - 32 MFMAs per slice in four slots of 8 (slice64), the same per-score VALU work, so the
         # slice is VALU-issue bound where D = 128 is matrix bound. The LDS images keep their 256-byte rows with only the first 128 used: every
         # address formula, swizzle and read instruction is the D = 128 one, a tile's 8-row group is ONE 1-KiB DMA piece instead of two.
-        assert D in (64, 128) and not (scaled and D == 64)
-        self.D, self.NKK, self.NDB = D, D // 16, D // 32
+        super().__init__(f16, mutant, ablate, stamps, scaled, D)
+        self.ds = ds
         # early (D = 128): the scalar bookkeeping of a slice - ring step + source offsets of the next request (10 s_*), dS tile addresses (11 s_*) - runs in
         # slot S of the slice that USES it (gaps 10, 12) instead of slot dK of the slice before (gaps 50, 62): slot dK is the full one (DMA pieces, dS stores,
         # ring toggles, the next slice's head reads). The prologue then leaves both one step behind.
@@ -130,37 +123,11 @@ class Gen:
         # accumulator is the exponent (no multiply per score: -32 VALU per slice, no scaling pass in the prologue... and a score error of
         # eps scale sum|q k| that grows with the logits; KF_ATTN_SCALED_OPERANDS). Default: exact f32 scores - K as it is, the row
         # constant is -lse / scale, one multiply by %[scale] (= scale log2(e) then) per score in front of its exp2.
-        self.scaled = scaled
-        self.stamps = stamps   # diagnostic build (tools/attn_dkv_w4_timeline.py, -DKF_DKV_W4_STAMPS): s_memtime sums per wave and block pass
-        self.mfma = "v_mfma_f32_32x32x16_f16" if f16 else "v_mfma_f32_32x32x16_bf16"
-        self.cvt = "v_cvt_pk_f16_f32" if f16 else "v_cvt_pk_bf16_f32"
-        self.f16, self.mutant, self.ds, self.ablate = f16, mutant, ds, set(ablate)
-        self.out = []
-
-    # -------------------------------------------------------------- emit helpers
-    def raw(self, t): self.out.append(Ins(t, "raw"))
-    def label(self, n): self.out.append(Ins(f"{n}:", "label"))
-    def salu(self, t): self.out.append(Ins(t, "salu"))
-    def valu(self, t, reads=(), writes=(), trans=False): self.out.append(Ins(t, "trans" if trans else "valu", reads, writes))
-
-    def stamp_take(self):
-        """Diagnostic build: request the clock; the value is used by stamp_add() BEHIND a wait the stream has anyway (the slice barrier's
-        lgkmcnt(0)), so the stamps do not drain the LDS reads in flight - the schedule measured is the product's."""
-        if self.stamps: self.salu("s_memtime s[80:81]")
-
-    def stamp_add(self, bucket):
-        if not self.stamps: return
-        self.salu("s_sub_u32 s83, s80, s82")
-        self.salu(f"s_add_u32 s{84 + bucket}, s{84 + bucket}, s83")
-        self.salu("s_mov_b32 s82, s80")
-
-    def stamp(self, bucket):
-        """A whole stamp where nothing is in flight (prologue, epilogue): buckets 0 block start -> head reads, 1 steady / 2 diag1 / 3 diag0 /
-        4 idle slices (barrier to barrier, booked one slice late), 5 last booked barrier -> epilogue, 6 epilogue, 7 the number of steady slices."""
-        if not self.stamps: return
-        self.stamp_take()
-        self.out.append(Ins("s_waitcnt lgkmcnt(0)", "wait", tag="lgkm"))
-        self.stamp_add(bucket)
+        # stamps (tools/attn_dkv_w4_timeline.py, -DKF_DKV_W4_STAMPS): s_memtime sums per wave and block pass. A whole stamp() stands where nothing is
+        # in flight (prologue, epilogue); in the loop stamp_take() requests the clock and stamp_add() uses it BEHIND a wait the stream has anyway (the slice
+        # barrier's lgkmcnt(0)), so the stamps do not drain the LDS reads in flight - the schedule measured is the product's. Buckets: 0 block start -> head
+        # reads, 1 steady / 2 diag1 / 3 diag0 / 4 idle slices (barrier to barrier, booked one slice late), 5 last booked barrier -> epilogue, 6 epilogue,
+        # 7 the number of steady slices.
 
     def mm(self, d, dn, a, b, c=None, tag="", acc="v"):
         """D = A B + C on registers: d first of 16 (VGPR or AGPR by `acc`), a / b first of 4 VGPRs, C = D unless `c` names another tuple."""
@@ -195,50 +162,17 @@ class Gen:
         if "lds" in self.ablate: return
         self.out.append(Ins(f"ds_read_b128 {vr(dst + 4 * g, 4)}, {vr(LR)} offset:{off + 32 * g}", "lds", V(LR), V(dst + 4 * g, 4)))
 
-    def barrier(self):
-        if "barrier" in self.ablate and getattr(self, "in_loop", False): return   # (timing experiment: wrong results)
-        self.out.append(Ins("s_barrier", "barrier"))
-
-    def dma_piece(self, srd, voff, soff, m0_add, inst_off, dword=False, sep=None):
-        """One LDS-DMA request. A scalar write of M0 needs one wait state before the request that reads it: `sep` (an emitter of ONE
-        instruction that had to be issued anyway - round 6: the read-base toggles behind the slice barrier) takes the place of the s_nop."""
-        if "dma" in self.ablate and getattr(self, "in_loop", False):
-            if sep: sep()
-            return
-        self.salu(f"s_add_u32 m0, {sr(S_M0)}, {m0_add}" if m0_add else f"s_mov_b32 m0, {sr(S_M0)}")
-        if sep: sep()
-        else: self.salu("s_nop 0")
-        o = f" offset:{inst_off}" if inst_off else ""
-        op = "buffer_load_dword" if dword else "buffer_load_dwordx4"
-        self.out.append(Ins(f"{op} {vr(voff)}, {sr(srd, 4)}, {sr(soff)} offen{o} lds", "dma", V(voff)))
-
-    def dma_only(self, srd, voff, soff, inst_off, dword=False):
-        """The request alone (its M0 write stands at the head of the same gap): an s_nop only if nothing else of the gap came between."""
-        if "dma" in self.ablate and getattr(self, "in_loop", False): return
-        if self.out[-1].text.startswith(("s_add_u32 m0", "s_mov_b32 m0")):
-            self.salu("s_nop 0")
-        o = f" offset:{inst_off}" if inst_off else ""
-        op = "buffer_load_dword" if dword else "buffer_load_dwordx4"
-        self.out.append(Ins(f"{op} {vr(voff)}, {sr(srd, 4)}, {sr(soff)} offen{o} lds", "dma", V(voff)))
-
     def dma_slice(self, seps=()):
         """This wave's pieces of one slice: rows 8 w .. 8 w + 7 of the Q tile and of the dO tile (two 1-KiB pieces each), and the 64 row
         constants (every wave fetches them: identical bytes, uniform counts). seps: up to five one-instruction emitters that stand between an
         M0 write and its request instead of an s_nop (any left over are emitted behind the last request)."""
         seps = list(seps)
         nxt = lambda: seps.pop(0) if seps else None  # noqa: E731
-        self.dma_piece(Q_SRD, DMAQ, S_QOFF, 0, 0, sep=nxt())
-        if self.D == 128: self.dma_piece(Q_SRD, DMAQ, S_QOFF, 896, 128, sep=nxt())
-        self.dma_piece(DO_SRD, DMAD, S_DOOFF, SLICE_DO, 0, sep=nxt())
-        if self.D == 128: self.dma_piece(DO_SRD, DMAD, S_DOOFF, SLICE_DO + 896, 128, sep=nxt())
-        sep = nxt()
-        if not ("dma" in self.ablate and getattr(self, "in_loop", False)):
-            self.salu(f"s_mov_b32 m0, {sr(S_M0C)}")
-            if sep: sep()
-            else: self.salu("s_nop 0")
-            self.out.append(Ins(f"buffer_load_dword {vr(DMAC)}, {sr(C_SRD, 4)}, {sr(S_COFF)} offen lds", "dma", V(DMAC)))
-        elif sep:
-            sep()
+        self.dma(Q_SRD, DMAQ, S_QOFF, S_M0, 0, 0, sep=nxt())
+        if self.D == 128: self.dma(Q_SRD, DMAQ, S_QOFF, S_M0, 896, 128, sep=nxt())
+        self.dma(DO_SRD, DMAD, S_DOOFF, S_M0, SLICE_DO, 0, sep=nxt())
+        if self.D == 128: self.dma(DO_SRD, DMAD, S_DOOFF, S_M0, SLICE_DO + 896, 128, sep=nxt())
+        self.dma(C_SRD, DMAC, S_COFF, S_M0C, dword=True, sep=nxt())
         for f in seps:
             f()
 
@@ -362,10 +296,10 @@ class Gen:
             if not nop_sep: put(48, (-3, 0), after_barrier)
             pieces = [(Q_SRD, DMAQ, S_QOFF, 0, 0), (Q_SRD, DMAQ, S_QOFF, 896, 128), (DO_SRD, DMAD, S_DOOFF, SLICE_DO, 0), (DO_SRD, DMAD, S_DOOFF, SLICE_DO + 896, 128)]
             for pc, g in zip(pieces, dma_gaps[:4]):
-                put(g, (-9, 0), lambda pc=pc: self.salu(f"s_add_u32 m0, {sr(S_M0)}, {pc[3]}" if pc[3] else f"s_mov_b32 m0, {sr(S_M0)}"))
-                put(g, (9, 0), lambda pc=pc: self.dma_only(pc[0], pc[1], pc[2], pc[4]))
-            put(dma_gaps[4], (-9, 0), lambda: self.salu(f"s_mov_b32 m0, {sr(S_M0C)}"))
-            put(dma_gaps[4], (9, 0), lambda: self.dma_only(C_SRD, DMAC, S_COFF, 0, dword=True))
+                put(g, (-9, 0), lambda pc=pc: self.salu(m0_write(S_M0, pc[3])))      # (M0 at the head of the gap - in a "dma" ablation too -, the request at its end)
+                put(g, (9, 0), lambda pc=pc: self.dma_load(pc[0], pc[1], pc[2], pc[4]))
+            put(dma_gaps[4], (-9, 0), lambda: self.salu(m0_write(S_M0C)))
+            put(dma_gaps[4], (9, 0), lambda: self.dma_load(C_SRD, DMAC, S_COFF, dword=True))
         else:
             put(49, (3, 0), dma_guarded if self.skip_tail_dma else (self.dma_slice if nop_sep else (lambda: self.dma_slice(toggles))))
         def book():
@@ -399,9 +333,9 @@ class Gen:
                 # (what may still be in flight: the previous slice's stores - and, when this slice's own requests stand in front of the barrier, those five)
                 n_vm = prev_stores + (5 if dma_gaps and not self.skip_tail_dma and max(dma_gaps) < 48 and "dma" not in self.ablate else 0)
                 if self.stamps:
-                    self.out.append(Ins(f"s_waitcnt vmcnt({n_vm}) lgkmcnt(0)", "wait", tag="vmlgkm"))
+                    self.wait(vm=n_vm, lgkm=0)
                 else:
-                    self.out.append(Ins(f"s_waitcnt vmcnt({n_vm})", "wait", tag="vm"))
+                    self.wait(vm=n_vm)
                 self.barrier()
                 # diagnostic build: the clock requested behind the PREVIOUS barrier has long returned (the wait above covers it): the period
                 # that ended there is booked now - one slice late, so a kind's bucket holds its predecessor's period at every change of
@@ -549,7 +483,7 @@ class Gen:
         for g in range(NG):
             slot, j = g // 8, g % 8
             if g == BAR:
-                self.out.append(Ins(f"s_waitcnt vmcnt({vm_ok})", "wait", tag="vm"))
+                self.wait(vm=vm_ok)
                 self.barrier()
             ksb, i = j >> 2, j & 3
             if slot < 2:
@@ -593,12 +527,7 @@ class Gen:
     # -------------------------------------------------------------- block pass
     def prologue(self):
         e = self
-        if self.stamps:
-            for i in list(range(84, 92)) + [100, 101]:
-                e.salu(f"s_mov_b32 s{i}, 0")
-            e.salu("s_memtime s[80:81]")
-            e.salu("s_waitcnt lgkmcnt(0)")
-            e.salu("s_mov_b32 s82, s80")
+        self.stamp_init(list(range(84, 92)) + [100, 101])
         # num_records (round 6: ragged sequence lengths): gfx950 range-checks voffset + soffset + the instruction offset against it
         # (tools/scratch/buffer_bounds.hip): a Q / dO row beyond the last query and a K / V row beyond the last key arrive in LDS as ZEROS, a
         # dK / dV row beyond the last key is not stored - no instruction in the loop. Zero rows contribute nothing: P of a zero query row is
@@ -694,9 +623,7 @@ class Gen:
             for g in range(8):                                                     # row groups 0..7 of the wave's 64 keys
                 for half in range(2 if self.D == 128 else 1):           # (D = 64: a row group's 8 x 128 B are ONE piece, the first half of the image)
                     e.salu(f"s_add_u32 m0, {sr(S_M0)}, {base + 2048 * g + 1024 * half - 128 * half}")
-                    e.salu("s_nop 0")
-                    o = " offset:128" if half else ""
-                    e.out.append(Ins(f"buffer_load_dwordx4 {vr(kvo if g & 1 else kve)}, {sr(srd, 4)}, {sr(S_TMP)} offen{o} lds", "dma", V(kvo if g & 1 else kve)))
+                    e.dma_load(srd, kvo if g & 1 else kve, S_TMP, 128 * half)
                 e.salu(f"s_add_u32 {sr(S_TMP)}, {sr(S_TMP)}, {sr(S_X1)}")
                 if g == 3:
                     e.salu(f"s_add_u32 {sr(S_TMP)}, {sr(S_TMP)}, {sr(S_IT)}")   # on to sub-block B's rows
@@ -760,7 +687,7 @@ class Gen:
         e.salu(f"s_lshl_b32 {sr(S_TMP2)}, {sr(S_WID)}, 14")
         for i in range(2):
             e.valu(f"v_add_u32 {vr(rbk[i])}, {sr(S_TMP2)}, {vr(RB[i])}")
-        e.out.append(Ins(f"s_waitcnt vmcnt({2 * self.NKK})", "wait", tag="vm"))       # the V pieces may still be in flight
+        e.wait(vm=2 * self.NKK)       # the V pieces may still be in flight
         for ksb in range(2):
             for kk in range(self.NKK):
                 e.out.append(Ins(f"ds_read_b128 {vr(self.KFR(ksb, kk), 4)}, {vr(rbk[kk & 1])} offset:{8192 * ksb + 512 * (kk >> 1)}", "lds", V(rbk[kk & 1]), V(self.KFR(ksb, kk), 4)))
@@ -768,11 +695,11 @@ class Gen:
         rbv = (S(0, 4), S(0, 5))
         for i in range(2):
             e.valu(f"v_add_u32 {vr(rbv[i])}, {sr(S_TMP2)}, {vr(RB[i])}")
-        e.out.append(Ins("s_waitcnt vmcnt(0)", "wait", tag="vm"))
+        e.wait(vm=0)
         for ksb in range(2):
             for kk in range(self.NKK):
                 e.out.append(Ins(f"ds_read_b128 {vr(self.VFR(ksb, kk), 4)}, {vr(rbv[kk & 1])} offset:{8192 * ksb + 512 * (kk >> 1)}", "lds", V(rbv[kk & 1]), V(self.VFR(ksb, kk), 4)))
-        e.out.append(Ins("s_waitcnt lgkmcnt(0)", "wait", tag="lgkm"))
+        e.wait(lgkm=0)
         e.barrier()     # every wave has its K fragments out of the ring
         if self.f16:
             e.salu(f"s_mov_b32 {sr(S_PSH)}, 0x{(127 + P_SHIFT) << 23:08x}")          # 2^14 (the V descriptor's registers are free from here on)
@@ -809,9 +736,8 @@ class Gen:
                 e.valu(f"v_mul_f32 {vr(t0)}, {vr(t0)}, {vr(t2)}")
                 e.valu(f"v_mul_f32 {vr(t1)}, {vr(t1)}, {vr(t2)}")
                 e.valu(f"{self.cvt} {vr(x)}, {vr(t0)}, {vr(t1)}")
-        self.in_loop = False
         # ---- slice s0 has landed for everyone (slice s0 + 1's 5 pieces may still be in flight); the first slice's head state
-        e.out.append(Ins(f"s_waitcnt vmcnt({5 if self.D == 128 else 6})", "wait", tag="vm"))    # (D = 128: slice s0 + 1's 5 pieces may be in flight; D = 64: two slices of 3)
+        e.wait(vm=5 if self.D == 128 else 6)    # (D = 128: slice s0 + 1's 5 pieces may be in flight; D = 64: two slices of 3)
         e.barrier()
         self.stamp(0)
         # (in the ORDER every slice's tail issues them: the loop's counted waits assume it)
@@ -871,13 +797,13 @@ class Gen:
         #  they have LANDED before the barrier at the epilogue's end lets the next pass's K tiles into the ring: a counted wait in front of that
         #  barrier - everything but the epilogue's own stores - instead of vmcnt(0) here. KF_GEN_EPI_VMWAIT=1 restores the old form: same-box A/B.)
         self.epi_late_wait = not self.skip_tail_dma and not os.environ.get("KF_GEN_EPI_VMWAIT") and not self.stamps
-        e.out.append(Ins("s_waitcnt lgkmcnt(0)" if (self.skip_tail_dma or self.epi_late_wait) else "s_waitcnt vmcnt(0) lgkmcnt(0)", "wait", tag="vmlgkm"))
+        e.wait(vm=None if (self.skip_tail_dma or self.epi_late_wait) else 0, lgkm=0)
         if self.skip_tail_dma:
             # (a pass WITHOUT slices - a key block beyond the last query - comes here straight from the prologue, whose second request is
             #  still in flight: it must have landed before the barrier below lets the next pass's K tiles into the ring)
             e.salu(f"s_cmp_lg_u32 {sr(S_NS)}, 0")
             e.salu("s_cbranch_scc1 L_epi_go_%=")
-            e.out.append(Ins("s_waitcnt vmcnt(0)", "wait", tag="vm"))
+            e.wait(vm=0)
             e.label("L_epi_go_%=")
         self.stamp(5)
         e.salu("s_nop 15")
@@ -914,7 +840,7 @@ class Gen:
                         e.valu(f"{self.cvt} {vr(x[0])}, {vr(x[0])}, {vr(x[1])}")
                         e.valu(f"{self.cvt} {vr(x[1])}, {vr(x[2])}, {vr(x[3])}")
                         e.out.append(Ins(f"ds_write_b64 {vr(st)}, {vr(x[0], 2)} offset:{32 * ksb * STAGE_ROW + 64 * db + 16 * gq}", "ldsw"))
-            e.out.append(Ins("s_waitcnt lgkmcnt(0)", "wait", tag="lgkm"))
+            e.wait(lgkm=0)
             e.salu(f"s_mov_b64 {sr(O_SRD, 2)}, %[{ptr}]")
             e.salu(f"s_mov_b32 {sr(O_SRD + 2)}, %[on]")                        # rows beyond the last key are not stored
             e.salu(f"s_lshl_b32 {sr(S_TMP)}, {sr(S_D0)}, 5")
@@ -928,7 +854,7 @@ class Gen:
                 d = 32 + 4 * (j % 8)    # v[32..63]: the dP registers are free now
                 e.out.append(Ins(f"ds_read_b128 {vr(d, 4)}, {vr(rd)} offset:{rows_per * j * STAGE_ROW}", "ldsw"))
                 if j % 8 == 7:
-                    e.out.append(Ins("s_waitcnt lgkmcnt(0)", "wait", tag="lgkm"))
+                    e.wait(lgkm=0)
                     for i in range(8):
                         e.out.append(Ins(f"buffer_store_dwordx4 {vr(32 + 4 * i, 4)}, {vr(oo)}, {sr(O_SRD, 4)}, {sr(S_X0)} offen", "vmem"))
                         e.salu(f"s_add_u32 {sr(S_X0)}, {sr(S_X0)}, {sr(S_X1)}")
@@ -952,10 +878,10 @@ class Gen:
             e.out.append(Ins(f"global_store_dwordx4 {vr(T[0])}, {vr(36, 4)}, %[dbg] offset:16", "vmem"))
             e.out.append(Ins(f"global_store_dwordx4 {vr(T[0])}, {vr(40, 4)}, %[dbg] offset:32", "vmem"))
             e.salu("s_mov_b64 exec, -1")
-            e.out.append(Ins("s_waitcnt vmcnt(0)", "wait", tag="vm"))
+            e.wait(vm=0)
         if self.epi_late_wait:
             n_st = 2 * (64 // (4 if self.D == 128 else 8))     # this epilogue's own dV + dK row stores: the only memory operations that may still be in flight
-            e.out.append(Ins(f"s_waitcnt vmcnt({n_st})", "wait", tag="vm"))
+            e.wait(vm=n_st)
         e.barrier()   # the next block's DMA reuses the slice buffers: every wave is past its last reads (they are, since the last slice's barrier) and every wave's requests of this pass have landed
 
     def build(self):
@@ -986,7 +912,7 @@ class Gen:
             sl("drop", "drop", vm["drop"])
             self.next_iter()
         self.epilogue()
-        finish_waits(self.out)
+        asm_stream.finish_waits(self.out, VARIANTS, WAIT_BATCH_AGE)
         return self
 
 
@@ -999,163 +925,17 @@ VARIANTS = r"L_(steady|diag1|diag0|idle|half|drop)_%=:"
 WAIT_BATCH_AGE = int(os.environ.get("KF_GEN_DKV_WAIT_AGE", "5"))
 
 
-def finish_waits(ins):
-    """Inserts `s_waitcnt lgkmcnt(N)` in front of every instruction that reads (or rewrites) the destination of an LDS read still in
-    flight, N = the LDS reads issued after it. Each variant's body is walked with the reads its predecessor's tail left pending (every
-    variant ends with the same 16 reads: the next slice's -lse constants and Q rows), the prologue and the epilogue linearly.
-    WAIT_BATCH_AGE (round 6): an s_waitcnt is an instruction of the wave's stream like any other (4 issue cycles in a gap that is
-    already full); with N > 0 a wait that has to be there anyway is widened over the younger reads that are at least N gaps old - they have
-    landed - so their own first uses need none. A wider wait is only ever stricter: correctness does not depend on N."""
-    # the tail every variant leaves behind (with how many MFMA gaps lie between each read and the variant's end)
-    tail, gaps_after = [], []
-    on = False
-    for x in ins:
-        if x.kind == "label" and re.match(VARIANTS, x.text):
-            on = x.text.startswith("L_steady")
-            if on: tail, gaps_after = [], []
-        elif on and x.kind == "lds":
-            tail.append(x)
-            gaps_after.append(0)
-        elif on and x.kind == "wait" and "lgkm" in x.tag:
-            tail, gaps_after = [], []
-        elif on and x.kind in ("mfma", "nomfma"):
-            gaps_after = [g + 1 for g in gaps_after]
-        elif on and x.kind == "label" and x.text.startswith("L_loop"):
-            on = False
-    # (never more than 15 in flight: the walk below retires the oldest before a 16th is issued, in every variant and in the prologue - so only
-    #  the LAST 15 reads of the tail can still be pending where a variant starts; the counter's field is 4 bits wide)
-    out, pending, born = [], [], []     # pending: destination registers of the reads in flight; born: the gap counter when each was issued
-    gap = 0
-    for x in ins:
-        if x.kind == "label" and (re.match(VARIANTS, x.text) or x.text.startswith("L_epilogue")):
-            pending = [t.writes for t in tail][-15:]
-            gap = 0
-            born = [-g for g in gaps_after][-15:]
-        if x.kind in ("mfma", "nomfma"):
-            gap += 1
-        if x.kind == "wait" and "lgkm" in x.tag:
-            pending, born = [], []
-        touched = set(x.reads) | set(x.writes)
-        need = -1
-        for i, w in enumerate(pending):
-            if touched & set(w):
-                need = i
-        if need >= 0:
-            if WAIT_BATCH_AGE > 0:
-                while need + 1 < len(pending) and gap - born[need + 1] >= WAIT_BATCH_AGE:
-                    need += 1
-            n = len(pending) - 1 - need
-            out.append(Ins(f"s_waitcnt lgkmcnt({n})", "wait", tag="auto"))
-            pending, born = pending[need + 1:], born[need + 1:]
-        if x.kind == "lds":
-            if len(pending) >= 15:   # the counter saturates at 15: retire the oldest first (it is 15 reads old)
-                out.append(Ins("s_waitcnt lgkmcnt(14)", "wait", tag="auto"))
-                pending, born = pending[len(pending) - 14:], born[len(born) - 14:]
-            pending.append(x.writes)
-            born.append(gap)
-        out.append(x)
-    ins[:] = out
-
-
-def check(ins):
-    """Distances the hardware does not interlock, per variant (walked twice): an MFMA's VGPR / AGPR result is read or overwritten by
-    anything but its own accumulate chain only >= 2 MFMAs or >= 22 wait states later; a VALU result feeds an MFMA operand only with >= 4
-    instructions in between; a transcendental's result is never read by the very next instruction."""
-    problems = []
-    cur, variants = None, {}
-    for i in ins:
-        if i.kind == "label" and re.match(VARIANTS, i.text):
-            cur = i.text[2:-4]
-            variants[cur] = []
-        elif i.kind == "label" and i.text.startswith("L_epilogue"):
-            cur = None
-        elif cur is not None:
-            variants[cur].append(i)
-    for name, body in variants.items():
-        seq = [x for x in body if x.kind not in ("raw", "label", "nomfma")] * 2
-        lm, lv = {}, {}
-        n_mfma = n_ins = 0
-        prev, tws = None, 0
-        for x in seq:
-            # a transcendental's result: >= 2 wait states (or any real instruction) before its reader - gfx950 does not interlock one (gen_attn_fwd.py)
-            if x.kind == "salu" and x.text.startswith("s_nop") and prev is not None:
-                tws += int(x.text.split()[1]) + 1
-            elif prev is not None and x.kind in ("valu", "trans") and set(prev.writes) & set(x.reads) and tws < 2:
-                problems.append(f"{name}: '{x.text}' reads the result of the transcendental '{prev.text}' {tws} wait state(s) behind it (needs 2)")
-            if not (x.kind == "salu" and x.text.startswith("s_nop")):
-                prev, tws = (x, 0) if x.kind == "trans" else (None, 0)
-            n_ins += 1
-            if x.kind == "mfma":
-                n_mfma += 1
-            if x.kind == "salu" and x.text.startswith("s_nop"):
-                n_ins += int(x.text.split()[1])
-            for reg in x.reads:
-                if reg in lm:
-                    m, tag, at = lm[reg]
-                    chain = x.kind == "mfma" and reg in x.writes
-                    if not chain and n_mfma - m < 2 and n_ins - at < 22:
-                        problems.append(f"{name}: '{x.text}' reads {reg} {n_mfma - m} MFMA(s) / {n_ins - at} wait states after '{tag}'")
-                if x.kind == "mfma" and reg in lv and n_ins - lv[reg] < 4:
-                    problems.append(f"{name}: '{x.text}' reads {reg} {n_ins - lv[reg]} instruction(s) after a VALU wrote it")
-            for reg in x.writes:
-                if x.kind != "mfma" and reg in lm and n_mfma - lm[reg][0] < 2 and n_ins - lm[reg][2] < 22:
-                    problems.append(f"{name}: '{x.text}' overwrites {reg} right behind '{lm[reg][1]}'")
-                if x.kind == "mfma":
-                    lm[reg] = (n_mfma, x.tag, n_ins)
-                    lv.pop(reg, None)
-                else:
-                    lm.pop(reg, None)
-                    if x.kind != "lds":
-                        lv[reg] = n_ins
-    return problems
+check = functools.partial(asm_stream.check, variants=VARIANTS)   # (the rules: asm_stream.check)
 
 
 def selftest():
     """The 32-row tile image: what this wave's DMA pieces write, what the row reads deliver as the A operand of S / dP (lane (r, h):
     A[row r][k = 16 kk + 8 h + j]) and what the transposed reads deliver as the A operand of dV / dK in the k order of a score
     accumulator used as the B operand (element j of half h <-> query 16 s + 8 (j >> 2) + 4 h + (j & 3))."""
-    srb = 256 + 96
-    lds = {}
-    for w in range(4):
-        for hp in range(2):
-            base = 2048 * w + 1024 * hp
-            for L in range(64):
-                row7, sub32, slot, b4 = (L >> 2) & 7, L >> 5, L & 3, (L >> 4) & 1
-                x = ((w & 1) << 1) | b4
-                src = 8 * w * srb + row7 * srb + 64 * sub32 + 16 * (slot ^ x) + 128 * hp
-                row, colbyte = src // srb, src % srb
-                for byte in range(0, 16, 2):
-                    lds[base + 16 * L + byte] = (row, (colbyte + byte) // 2)
-    assert len(lds) == 32 * 128
-    for kk in range(8):
-        for lane in range(64):
-            r, h = lane & 31, lane >> 5
-            b0 = 2048 * (r >> 3) + 64 * (r & 7) + 16 * (h ^ ((r >> 2) & 3))
-            addr = (b0 ^ (32 if kk & 1 else 0)) + 512 * (kk >> 1)
-            for j in range(8):
-                assert lds[addr + 2 * j] == (r, 16 * kk + 8 * h + j), ("row", kk, lane, j)
-    for s in range(2):
-        for db in range(4):
-            for sec in range(2):
-                imm = 2048 * (2 * s + sec) + 512 * db
-                got = {}
-                for grp in range(4):
-                    blk = {}
-                    for i in range(16):
-                        lane = 16 * grp + i
-                        h, q, p, g1 = lane >> 5, i >> 2, i & 3, grp & 1
-                        t0 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ h) + 8 * (p & 1)
-                        addr = (t0 ^ (32 if sec else 0)) + imm
-                        for c in range(4):
-                            blk[(q, 4 * p + c)] = lds[addr + 2 * c]
-                    for i in range(16):
-                        got[16 * grp + i] = [blk[(qq, i)] for qq in range(4)]
-                for lane in range(64):
-                    r, h = lane & 31, lane >> 5
-                    for e in range(4):
-                        j = 4 * sec + e
-                        qrow = 16 * s + 8 * (j >> 2) + 4 * h + (j & 3)
-                        assert got[lane][e] == (qrow, 32 * db + r), ("tr", s, db, sec, lane, e, got[lane][e])
+    pieces = [(2048 * w + 1024 * hp, w, hp) for w in range(4) for hp in range(2)]   # wave w: row group w of the slice's tile
+    lds = asm_stream.tile_image(pieces, 256 + 96)   # (a row stride that is not the tile's own)
+    asm_stream.row_reads_agree(lds, 1)
+    asm_stream.transposed_reads_agree(lds, 2)
     return True
 
 
@@ -1192,42 +972,21 @@ def main():
         return 1
     if args.check_only:
         return 0
-    texts = {}
-    for f16 in (False, True):
-        for mut in (False, True):
-            for ds in (True, False):
-                for sq in (False, True):
-                    gg = Gen(f16, mut, ds, ablate=abl, stamps=args.stamps, scaled=sq).build()
-                    assert abl or not check(gg.out), check(gg.out)[:5]
-                    texts[(f16, mut, ds, sq)] = render(gg.out).replace(chr(10), " " + chr(92) + chr(10))
-    texts64 = {}
-    for f16 in (False, True):
-        for mut in (False, True):
-            for ds in (True, False):
-                gg = Gen(f16, mut, ds, ablate=abl, D=64).build()
-                assert abl or not check(gg.out), check(gg.out)[:5]
-                texts64[(f16, mut, ds)] = render(gg.out).replace(chr(10), " " + chr(92) + chr(10))
+    def stream(name, *a, **kw):
+        gg = Gen(*a, ablate=abl, **kw).build()
+        assert abl or not check(gg.out), check(gg.out)[:5]
+        return name, gg.out
+    def streams(mut):
+        kinds = [(f16, ds, f"{'F16' if f16 else 'BF16'}_{'DS' if ds else 'NODS'}") for f16 in (False, True) for ds in (True, False)]
+        return [stream(f"KF_DKV_W4_ASM_{nm}{'_SQ' if sq else ''}", f16, mut, ds, stamps=args.stamps, scaled=sq) for f16, ds, nm in kinds for sq in (False, True)] + \
+               [stream(f"KF_DKV_W4_D64_ASM_{nm}", f16, mut, ds, D=64) for f16, ds, nm in kinds]
     n_ins = sum(1 for i in g.out if i.kind not in ("raw", "label", "nomfma"))
-    def four(mut):
-        return "\n".join([f"#define KF_DKV_W4_ASM_{'F16' if f16 else 'BF16'}_{'DS' if ds else 'NODS'}{'_SQ' if sq else ''} \\\n{texts[(f16, mut, ds, sq)]}"
-                          for f16 in (False, True) for ds in (True, False) for sq in (False, True)] +
-                         [f"#define KF_DKV_W4_D64_ASM_{'F16' if f16 else 'BF16'}_{'DS' if ds else 'NODS'} \\\n{texts64[(f16, mut, ds)]}"
-                          for f16 in (False, True) for ds in (True, False)])
-    text = f"""// GENERATED by tools/gen_attn_dkv.py - do not edit; edit the generator and run it again.
+    asm_stream.write_inc(args.out, f"""// GENERATED by tools/gen_attn_dkv.py - do not edit; edit the generator and run it again.
 // The 16-bit causal-attention dK / dV pass of one 256-key block as ONE instruction stream ({n_ins} instructions): 4 waves x 64 keys,
 // one wave per SIMD, all 512 registers asm-owned; see the generator's header for the structure.
 // Two forms: exact f32 scores (default: %[scale] = scale log2 e, row constant -lse / scale), and _SQ = K scaled and rounded once per block
-// (KF_ATTN_SCALED_OPERANDS: %[scale] = the softmax scale, row constant -lse log2 e). _D64_ = head size 64 (exact form only): 32 MFMAs per slice.
-#pragma once
-#define KF_DKV_W4_LDS_BYTES {LDS_BYTES}
-#define KF_DKV_W4_CLOBBERS {", ".join('"' + c + '"' for c in CLOBBERS + ([f"s{i}" for i in range(80, 102)] if args.stamps else []))}
-#ifdef KF_MUTANT
-{four(True)}
-#else
-{four(False)}
-#endif
-"""
-    Path(args.out).write_text(text)
+// (KF_ATTN_SCALED_OPERANDS: %[scale] = the softmax scale, row constant -lse log2 e). _D64_ = head size 64 (exact form only): 32 MFMAs per slice.""",
+                        ("KF_DKV_W4_LDS_BYTES", LDS_BYTES), ("KF_DKV_W4_CLOBBERS", CLOBBERS + ([f"s{i}" for i in range(80, 102)] if args.stamps else [])), streams)
     print(f"wrote {args.out} ({n_ins} instructions)")
     return 0
 

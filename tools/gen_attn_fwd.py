@@ -25,10 +25,14 @@ Structure (cdna_hip_programming.md, "4-wave, one-wave-per-SIMD, persistent struc
 
 The file written is a C++ header with one string literal per element type (bf16 / f16) and the clobber list."""
 import argparse
+import functools
 import os
 import re
 import sys
 from pathlib import Path
+
+import asm_stream
+from asm_stream import A, Ins, V, ar, render, sr, vr  # noqa: F401
 
 ROOT = Path(__file__).resolve().parent.parent
 OUT = ROOT / "kfunca_amd" / "csrc" / "device" / "attn_fwd_w4.inc"
@@ -77,55 +81,26 @@ STAGE_ROW = 272
 LDS_BYTES = STAGE0 + 4 * 64 * STAGE_ROW
 
 
-def vr(i, n=1): return f"v{i}" if n == 1 else f"v[{i}:{i + n - 1}]"
-def ar(i, n=1): return f"a{i}" if n == 1 else f"a[{i}:{i + n - 1}]"
-def sr(i, n=1): return f"s{i}" if n == 1 else f"s[{i}:{i + n - 1}]"
-
-
-class Ins:
-    """One instruction with what the checker needs to know about it."""
-    def __init__(self, text, kind, reads=(), writes=(), tag=""):
-        self.text, self.kind, self.reads, self.writes, self.tag = text, kind, tuple(reads), tuple(writes), tag
-
-
-def V(i, n=1): return [("v", j) for j in range(i, i + n)]
-def A(i, n=1): return [("a", j) for j in range(i, i + n)]
-
-
-class Gen:
+class Gen(asm_stream.Emitter):
     def __init__(self, f16=False, mutant=False, ablate=(), stamps=False, scaled=False, D=128):
         # D = 64 (round 5, VERDICT round 4 #4; the reference's second fast head size, causal_attention_kernel.cu:40-52): half the k-steps and half
         # the column blocks - a 64-key tile is 32 MFMAs in four slots of 8 - with the SAME softmax work per tile, so the tile is VALU-issue bound
         # (three scores per gap in the exponent chain). LDS images keep their 256-byte rows with the first 128 bytes used: every address formula
         # is the D = 128 one, a row group of a tile is ONE 1-KiB DMA piece instead of two. Exact scores only.
-        assert D in (64, 128) and not (scaled and D == 64)
-        self.D, self.NKK, self.NDB = D, D // 16, D // 32
+        super().__init__(f16, mutant, ablate, stamps, scaled, D)
         self.SL = 2 * self.NKK               # MFMAs per slot (S of a block: 2 sub-tiles x NKK k-steps; P V: 4 k-steps x NDB column blocks)
         self.NG = 4 * self.SL                # gaps per tile iteration
         self.VF = lambda ks, db: 96 + 4 * self.NDB * ks + 4 * db        # V^T fragment (4 VGPRs)
         self.OA = lambda b, db: 16 * self.NDB * b + 16 * db             # AGPRs
         self.QF = lambda b, kk: 128 + 4 * self.NKK * b + 4 * kk
         self.KF = lambda sub, kk: 192 + 4 * self.NKK * sub + 4 * kk
-        self.mutant = mutant
         # scaled: the query is multiplied by scale log2(e) and ROUNDED to the element type once per pass, the score chains start from -max and
         # deliver exponents (no multiply per score: -64 VALU per tile, ~4 % of the kernel) - at the price of a score error of eps scale sum|q k|,
         # which grows with the logits (KF_ATTN_SCALED_OPERANDS; DESIGN.md 4.1). Default: exact f32 scores, one fma per score.
-        self.scaled = scaled
-        self.stamps = stamps        # diagnostic build (tools/attn_fwd_w4_timeline.py): s_memtime at the slot boundaries, eight sums per wave and block
-        self.ablate = set(ablate)   # timing experiments only (tools/scratch/fwd_w4_ablate.sh): parts of the tile body left out - WRONG results
-        self.f16 = f16
-        self.mfma = "v_mfma_f32_32x32x16_f16" if f16 else "v_mfma_f32_32x32x16_bf16"
-        self.cvt = "v_cvt_pk_f16_f32" if f16 else "v_cvt_pk_bf16_f32"
-        self.out = []   # list of Ins (and labels / comments as kind "raw")
+        # stamps (tools/attn_fwd_w4_timeline.py): s_memtime at the slot boundaries, eight sums per wave and block - buckets 0 prologue, 1..4 the steady
+        # tile's slots A..D, 5 the other variants' iterations, 6 epilogue, 7 two stamps back to back (what a stamp itself costs); s91 counts steady
+        # iterations. ablate: tools/scratch/fwd_w4_ablate.sh.
         self.uid = 0
-
-    # -------------------------------------------------------------- emit helpers
-    def raw(self, text): self.out.append(Ins(text, "raw"))
-    def label(self, name): self.out.append(Ins(f"{name}:", "label"))
-    def salu(self, text): self.out.append(Ins(text, "salu"))
-
-    def valu(self, text, reads=(), writes=(), trans=False):
-        self.out.append(Ins(text, "trans" if trans else "valu", reads, writes))
 
     def qk(self, b, sub, kk, first=False):
         """One MFMA of S^T = K (c Q)^T. The chain starts from -MC (sixteen equal registers per lane: a lane holds one query), so the
@@ -156,40 +131,6 @@ class Gen:
         imm = 2048 * (4 * sub + 2 * s + second) + 512 * db
         self.out.append(Ins(f"ds_read_b64_tr_b16 {vr(self.VF(ks, db) + 2 * second, 2)}, {vr(VB[second])} offset:{imm}", "lds",
                             V(VB[second]), V(self.VF(ks, db) + 2 * second, 2)))
-
-    def wait(self, vm=None, lgkm=None):
-        parts = ([f"vmcnt({vm})"] if vm is not None else []) + ([f"lgkmcnt({lgkm})"] if lgkm is not None else [])
-        self.out.append(Ins("s_waitcnt " + " ".join(parts), "wait", tag=f"{'vm' if vm is not None else ''}{'lgkm' if lgkm is not None else ''}"))
-
-    def barrier(self):
-        if "barrier" in self.ablate and getattr(self, "in_loop", False): return
-        self.out.append(Ins("s_barrier", "barrier"))
-
-    def dma_m0(self, m0_from, m0_add):
-        if "dma" in self.ablate and getattr(self, "in_loop", False): return
-        self.salu(f"s_add_u32 m0, {sr(m0_from)}, {m0_add}" if m0_add else f"s_mov_b32 m0, {sr(m0_from)}")
-
-    def dma_load(self, srd, voff, soff, inst_off):
-        if "dma" in self.ablate and getattr(self, "in_loop", False): return
-        if self.out[-1].text.startswith(("s_add_u32 m0", "s_mov_b32 m0")):
-            self.salu("s_nop 0")   # SALU write of M0 -> LDS-DMA: one wait state (in the tile loop a gap's other fillers stand between the two)
-        o = f" offset:{inst_off}" if inst_off else ""
-        self.out.append(Ins(f"buffer_load_dwordx4 {vr(voff)}, {sr(srd, 4)}, {sr(soff)} offen{o} lds", "dma", V(voff)))
-
-    def dma(self, srd, voff, soff, m0_from, m0_add, inst_off):
-        self.dma_m0(m0_from, m0_add)
-        self.dma_load(srd, voff, soff, inst_off)
-
-    def stamp(self, bucket):
-        """Diagnostic build only: the cycles since the previous stamp go to accumulator `bucket` (0 prologue, 1..4 the steady tile's slots
-        A..D, 5 the other variants' iterations, 6 epilogue; s91 counts steady iterations). The SMEM round trip of each stamp (~100 cycles)
-        lands in the bucket that FOLLOWS it: tools/attn_fwd_w4_timeline.py calibrates it with two stamps back to back (bucket 7)."""
-        if not self.stamps: return
-        self.salu("s_memtime s[80:81]")
-        self.salu("s_waitcnt lgkmcnt(0)")
-        self.salu("s_sub_u32 s83, s80, s82")
-        self.salu(f"s_add_u32 s{84 + bucket}, s{84 + bucket}, s83")
-        self.salu("s_mov_b32 s82, s80")
 
     # -------------------------------------------------------------- the filler streams of one iteration
     def softmax_ops(self, b, cur, masked, drop, first=False):
@@ -458,13 +399,8 @@ class Gen:
     # -------------------------------------------------------------- whole pass of one query block
     def prologue(self):
         e = self
-        if self.stamps:
-            for i in range(84, 92):
-                e.salu(f"s_mov_b32 s{i}, 0")
-            e.salu("s_memtime s[80:81]")
-            e.salu("s_waitcnt lgkmcnt(0)")
-            e.salu("s_mov_b32 s82, s80")
-            self.stamp(7)   # calibration: two stamps back to back
+        self.stamp_init(range(84, 92))
+        self.stamp(7)   # calibration: two stamps back to back
         e.raw("; ---- inputs into fixed registers")
         e.salu(f"s_mov_b64 {sr(K_SRD, 2)}, %[kp]")
         e.salu(f"s_mov_b64 {sr(V_SRD, 2)}, %[vp]")
@@ -562,9 +498,7 @@ class Gen:
         for g in range(8):                                                         # (into the wave's OWN slab, S_STAGE: a wave that is early must not write where a late one still reads its O rows)
             for half in range(2 if self.D == 128 else 1):
                 e.salu(f"s_add_u32 m0, {sr(S_STAGE)}, {2048 * g + 1024 * half - 128 * half}")
-                e.salu("s_nop 0")
-                o = " offset:128" if half else ""
-                e.out.append(Ins(f"buffer_load_dwordx4 {vr(qo if g & 1 else qe)}, {sr(Q_SRD, 4)}, {sr(S_X0)} offen{o} lds", "dma", V(qo if g & 1 else qe)))
+                e.dma_load(Q_SRD, qo if g & 1 else qe, S_X0, 128 * half)
             e.salu(f"s_add_u32 {sr(S_X0)}, {sr(S_X0)}, {sr(S_X1)}")
         # ---- tile 0 of K into slot 0
         e.raw("; ---- K(0) -> slot 0; then K(1) -> slot 1 and V(0) -> slot 0")
@@ -806,92 +740,11 @@ class Gen:
         self.fix_trans_use()
         return self
 
-    def fix_trans_use(self):
-        """gfx950 does not interlock a transcendental result against the VERY NEXT instruction reading it: the lanes with
-        (lane & 4) == 0 get the old register value (tools/scratch/trans_hazard.hip, profiles/r04_trans_hazard.txt). One wait state
-        is what the hardware needs (LLVM's hasTransForwardingHazard; hipcc inserts it for compiled code, never inside inline asm).
-        Behind an MFMA the stream never has the two as neighbours; where gaps hold no MFMA (drain, a first tile's empty slot,
-        prologue, epilogue, the rare rescale) they can be: `s_nop 1` (one more than needed) goes between them, and an `s_nop 0`
-        that is all that separates them is widened."""
-        out, prev, sep = [], None, 0
-        for x in self.out:
-            if x.kind in ("raw", "label", "nomfma"):
-                out.append(x)
-                if x.kind == "label": prev = None
-                continue
-            if prev is not None and x.kind == "salu" and x.text.startswith("s_nop") and sep == 0:
-                if int(x.text.split()[1]) < 1:
-                    x = Ins("s_nop 1", "salu")
-                out.append(x)
-                sep = 2
-                continue
-            if prev is not None and sep == 0 and x.kind in ("valu", "trans") and set(prev.writes) & set(x.reads):
-                out.append(Ins("s_nop 1", "salu"))
-            out.append(x)
-            prev, sep = (x, 0) if x.kind == "trans" else (None, 0)
-        self.out = out
+    def fix_trans_use(self): asm_stream.fix_trans_use(self.out)
 
 
-# ------------------------------------------------------------------ static checks on the emitted stream
-def check(ins):
-    """Walks each variant's stream twice (an iteration behind itself) and enforces:
-       * an MFMA result is read or overwritten by a non-MFMA instruction only >= 2 MFMAs later (and by an MFMA only as its own
-         accumulate chain or >= 2 MFMAs later);
-       * a VALU result feeds an MFMA's A / B / C only with >= 4 instructions in between;
-       * an LDS read's destination is used only behind an s_waitcnt lgkmcnt(0) that follows the read."""
-    problems = []
-    # split into variants
-    cur, variants = None, {}
-    for i in ins:
-        if i.kind == "label" and re.match(r"L_(steady|first|masked|firstmasked|drain|idle|steadydrop)_%=:", i.text):
-            cur = i.text[2:-4]
-            variants[cur] = []
-        elif i.kind == "label" and i.text.startswith("L_epilogue"):
-            cur = None
-        elif cur is not None:
-            variants[cur].append(i)
-    for name, body in variants.items():
-        seq = [x for x in body if x.kind not in ("raw", "label", "nomfma")] * 2
-        last_mfma_write, last_valu_write, pending_lds = {}, {}, {}
-        n_mfma, n_ins = 0, 0
-        prev, tws = None, 0
-        for x in seq:
-            if x.kind == "salu" and x.text.startswith("s_nop") and prev is not None:
-                tws += int(x.text.split()[1]) + 1
-            elif prev is not None and x.kind in ("valu", "trans") and set(prev.writes) & set(x.reads) and tws < 2:
-                problems.append(f"{name}: '{x.text}' reads the result of '{prev.text}' {tws} wait state(s) behind it (a transcendental needs 2)")
-            if not (x.kind == "salu" and x.text.startswith("s_nop")):
-                prev, tws = (x, 0) if x.kind == "trans" else (None, 0)
-            n_ins += 1
-            if x.kind == "mfma":
-                n_mfma += 1
-            if x.kind == "salu" and x.text.startswith("s_nop"):
-                n_ins += int(x.text.split()[1])
-            if x.kind == "wait" and "lgkm" in x.tag:
-                pending_lds.clear()
-            for reg in x.reads:
-                if reg in pending_lds:
-                    problems.append(f"{name}: '{x.text}' uses {reg} of an LDS read not yet waited for")
-                if reg in last_mfma_write:
-                    m, tag, at = last_mfma_write[reg]
-                    chain = x.kind == "mfma" and reg in x.writes and n_mfma - m == 1
-                    if not chain and n_mfma - m < 2 and n_ins - at < 22:
-                        problems.append(f"{name}: '{x.text}' reads {reg} {n_mfma - m} MFMA(s) / {n_ins - at} wait states after '{tag}' wrote it")
-                if x.kind == "mfma" and reg in last_valu_write and n_ins - last_valu_write[reg] < 4:
-                    problems.append(f"{name}: '{x.text}' reads {reg} {n_ins - last_valu_write[reg]} instruction(s) after a VALU wrote it")
-            for reg in x.writes:
-                if x.kind != "mfma" and reg in last_mfma_write and n_mfma - last_mfma_write[reg][0] < 2 and n_ins - last_mfma_write[reg][2] < 22:
-                    problems.append(f"{name}: '{x.text}' overwrites {reg} right behind '{last_mfma_write[reg][1]}'")
-                if x.kind == "mfma":
-                    last_mfma_write[reg] = (n_mfma, x.tag, n_ins)
-                    last_valu_write.pop(reg, None)
-                elif x.kind == "lds":
-                    pending_lds[reg] = n_ins
-                    last_mfma_write.pop(reg, None)
-                else:
-                    last_valu_write[reg] = n_ins
-                    last_mfma_write.pop(reg, None)
-    return problems
+VARIANTS = r"L_(steady|first|masked|firstmasked|drain|idle|steadydrop)_%=:"
+check = functools.partial(asm_stream.check, variants=VARIANTS)   # (the rules: asm_stream.check)
 
 
 def gap_table(ins, name="steady"):
@@ -920,75 +773,16 @@ def selftest():
     """The three views of one tile image must agree: what the DMA pieces write, what the K row reads deliver as the A operand of
     v_mfma_32x32x16 (lane (r, h): A[row r][k = 8 h + j]), and what the transposed reads deliver as the V^T operand in the k order of
     a score accumulator used as the B operand (element j of half h <-> key 16 ks + 8 (j >> 2) + 4 h + (j & 3))."""
-    sr_b = 256 + 64   # a row stride that is not the tile's own
-    lds = {}
-    for w in range(4):
-        for rgi, rg in enumerate((2 * w, 2 * w + 1)):
-            for hp in range(2):
-                base = 4096 * w + 2048 * rgi + 1024 * hp
-                for L in range(64):
-                    row7, sub32, slot, b4 = (L >> 2) & 7, L >> 5, L & 3, (L >> 4) & 1
-                    x = b4 if rg % 2 == 0 else (2 | b4)
-                    src = 8 * rg * sr_b + row7 * sr_b + 64 * sub32 + 16 * (slot ^ x) + 128 * hp   # soffset + voffset + inst offset
-                    row, colbyte = src // sr_b, src % sr_b
-                    for byte in range(0, 16, 2):
-                        lds[base + 16 * L + byte] = (row, (colbyte + byte) // 2)
-    assert len(lds) == 64 * 128
-    # K row reads
-    for sub in range(2):
-        for kk in range(8):
-            for lane in range(64):
-                r, h = lane & 31, lane >> 5
-                b0 = 2048 * (r >> 3) + 64 * (r & 7) + 16 * (h ^ ((r >> 2) & 3))
-                addr = (b0 ^ (32 if kk & 1 else 0)) + 8192 * sub + 512 * (kk >> 1)
-                for j in range(8):
-                    assert lds[addr + 2 * j] == (32 * sub + r, 16 * kk + 8 * h + j), ("K", sub, kk, lane, j, lds[addr + 2 * j])
-    # V transposed reads
-    for ks in range(4):
-        for db in range(4):
-            for sec in range(2):
-                sub, s = ks >> 1, ks & 1
-                imm = 2048 * (4 * sub + 2 * s + sec) + 512 * db
-                got = {}
-                for grp in range(4):
-                    blk = {}
-                    for i in range(16):
-                        lane = 16 * grp + i
-                        h, q, p, g1 = lane >> 5, i >> 2, i & 3, grp & 1
-                        t0 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ h) + 8 * (p & 1)
-                        addr = (t0 ^ (32 if sec else 0)) + imm
-                        for c in range(4):
-                            blk[(q, 4 * p + c)] = lds[addr + 2 * c]
-                    for i in range(16):
-                        got[16 * grp + i] = [blk[(qq, i)] for qq in range(4)]
-                for lane in range(64):
-                    r, h = lane & 31, lane >> 5
-                    for e in range(4):
-                        j = 4 * sec + e
-                        key = 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3)
-                        assert got[lane][e] == (key, 32 * db + r), ("V", ks, db, sec, lane, e, got[lane][e], (key, 32 * db + r))
+    pieces = [(4096 * w + 2048 * rgi + 1024 * hp, 2 * w + rgi, hp) for w in range(4) for rgi in range(2) for hp in range(2)]   # wave w: row groups 2 w, 2 w + 1
+    lds = asm_stream.tile_image(pieces, 256 + 64)   # (a row stride that is not the tile's own)
+    asm_stream.row_reads_agree(lds, 2)
+    asm_stream.transposed_reads_agree(lds, 4)
     return True
 
 
 # m0 is written by every DMA piece; exec is all ones on entry (a full 256-thread block, no divergence in the wrapper) and is restored to -1
 # wherever the stream narrows it (lse store): the block assumes and leaves exec == -1
 CLOBBERS = (["memory", "vcc", "scc", "m0"] + [f"s{i}" for i in range(36, 80)] + [f"v{i}" for i in range(N_VGPR)] + [f"a{i}" for i in range(256)])
-
-
-def render(ins):
-    lines = []
-    for i in ins:
-        if i.kind == "nomfma":
-            continue
-        if i.kind == "raw" and i.text.startswith("#"):
-            lines.append(i.text)
-        elif i.kind == "raw":
-            lines.append(f'    "{i.text}\\n"')
-        elif i.kind == "label":
-            lines.append(f'    "{i.text}\\n"')
-        else:
-            lines.append(f'    "\\t{i.text}\\n"')
-    return "\n".join(lines)
 
 
 def main():
@@ -1018,38 +812,21 @@ def main():
         return 1
     if args.check_only:
         return 0
-    texts = {}
-    for f16 in (False, True):
-        for mut in (False, True):
-            for sq in (False, True):
-                gg = Gen(f16, mut, ablate=abl, stamps=args.stamps, scaled=sq).build()
-                assert abl or not check(gg.out), check(gg.out)[:5]
-                texts[(f16, mut, sq)] = render(gg.out).replace(chr(10), " " + chr(92) + chr(10))
-    texts64 = {}
-    for f16 in (False, True):
-        for mut in (False, True):
-            gg = Gen(f16, mut, ablate=abl, D=64).build()
-            assert abl or not check(gg.out), check(gg.out)[:5]
-            texts64[(f16, mut)] = render(gg.out).replace(chr(10), " " + chr(92) + chr(10))
+    def stream(name, *a, **kw):
+        gg = Gen(*a, ablate=abl, **kw).build()
+        assert abl or not check(gg.out), check(gg.out)[:5]
+        return name, gg.out
+    def streams(mut):
+        return [stream(f"KF_FWD_W4_ASM_{'F16' if f16 else 'BF16'}{'_SQ' if sq else ''}", f16, mut, stamps=args.stamps, scaled=sq) for f16 in (False, True) for sq in (False, True)] + \
+               [stream(f"KF_FWD_W4_D64_ASM_{'F16' if f16 else 'BF16'}", f16, mut, D=64) for f16 in (False, True)]
     n_ins = sum(1 for i in g.out if i.kind not in ("raw", "label", "nomfma"))
-    def four(mut):
-        return "\n".join([f"#define KF_FWD_W4_ASM_{'F16' if f16 else 'BF16'}{'_SQ' if sq else ''} \\\n{texts[(f16, mut, sq)]}" for f16 in (False, True) for sq in (False, True)] +
-                         [f"#define KF_FWD_W4_D64_ASM_{'F16' if f16 else 'BF16'} \\\n{texts64[(f16, mut)]}" for f16 in (False, True)])
-    text = f"""// GENERATED by tools/gen_attn_fwd.py - do not edit; edit the generator and run it again.
+    asm_stream.write_inc(args.out, f"""// GENERATED by tools/gen_attn_fwd.py - do not edit; edit the generator and run it again.
 // The 16-bit causal-attention forward of one 256-row query block as ONE instruction stream per element type ({n_ins} instructions):
 // 4 waves x 64 query rows, one wave per SIMD, all 512 registers asm-owned; see the generator's header for the structure.
 // Two forms: exact f32 scores (default), and _SQ = the query scaled and rounded once per pass (KF_ATTN_SCALED_OPERANDS: faster, less exact).
-// _D64_ = head size 64 (exact form only): a 64-key tile is 32 MFMAs, the exponent chain runs three scores per gap.
-#pragma once
-#define KF_FWD_W4_LDS_BYTES {LDS_BYTES}
-#define KF_FWD_W4_CLOBBERS {", ".join('"' + c + '"' for c in CLOBBERS + ([f"s{i}" for i in range(80, 92)] if args.stamps else []))}
-#ifdef KF_MUTANT  // + one more variant of the tile body: the probabilities of tile %[mut] are dropped (tests/test_gpu_attention_mutants.py)
-{four(True)}
-#else
-{four(False)}
-#endif
-"""
-    Path(args.out).write_text(text)
+// _D64_ = head size 64 (exact form only): a 64-key tile is 32 MFMAs, the exponent chain runs three scores per gap.""",
+                        ("KF_FWD_W4_LDS_BYTES", LDS_BYTES), ("KF_FWD_W4_CLOBBERS", CLOBBERS + ([f"s{i}" for i in range(80, 92)] if args.stamps else [])), streams,
+                        "  // + one more variant of the tile body: the probabilities of tile %[mut] are dropped (tests/test_gpu_attention_mutants.py)")
     print(f"wrote {args.out} ({n_ins} instructions per element type)")
     return 0
 
