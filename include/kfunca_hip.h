@@ -1093,7 +1093,11 @@ int kf_moe_aux_loss_bwd(int dtype, int64_t T, int64_t E, int64_t k, const void *
  *                   multiple of 16; lda, ldb multiples of 16, >= K and at most 2^24; A and B 16-byte aligned, C aligned to its element;
  *                   ldc >= N. A K tail short of 128 and ragged M / N edges are handled in the kernel by range-checked loads (bytes
  *                   outside [rows, K] are never read into a result) and guarded stores. No workspace, no padded copies, no split-K:
- *                   two runs give the same bits.
+ *                   two runs give the same bits. Special codes go through the instruction as IEEE values: a NaN code (e4m3 0x7f / 0xff,
+ *                   e5m2 0x7d .. 0x7f with either sign) in A makes every output of its row of C NaN (in B: of its column), against
+ *                   zero codes too; an e5m2 +infinity in A against a strictly positive column of B makes its row of C +infinity. Every
+ *                   other output keeps the bits it has without that byte, wherever the byte sits (first K block, K tail, last row of a
+ *                   ragged edge tile): tests/test_gpu_fp8_edges.py.
  * Nothing synchronises, allocates or reads a value back: every entry can be captured with kf_graph_*. Profile labels fp8_amax,
  * fp8_quantize, gemm_fp8. Every argument is checked before any device call, with the entry's name in kf_last_error(): KF_ERR_INVALID for
  * a dtype, format or out_dtype outside the lists, negative extents, a leading dimension below its extent (ldqt < ceil16(rows)) or not a

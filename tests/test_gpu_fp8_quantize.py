@@ -22,20 +22,24 @@ def device_image(nbytes):
     return buf
 
 
-def run(x, dt, fmt, transpose=True, ld=None, ldq=None, ldqt=None):
-    """x: stored elements [rows, cols]. Returns (amax bits, scale_inv, the whole q allocation as [rows, ldq] + guard, the same for qt)."""
+def run(x, dt, fmt, transpose=True, ld=None, ldq=None, ldqt=None, amax=None):
+    """x: stored elements [rows, cols]. Returns (amax bits, scale_inv, the whole q allocation as [rows, ldq] + guard, the same for qt).
+    amax: None for kf_fp8_amax's result, else the caller's bound (an f32), uploaded in its place."""
     rows, cols = x.shape
     rows16 = (rows + 15) // 16 * 16
     ld, ldq, ldqt = ld or cols, ldq or cols, ldqt or rows16
     host = np.full((rows, ld), GAP[dt], dtype=R.STORE[dt])
     host[:, :cols] = x
     bx = H.DevBuf.from_numpy(host)
-    amax, sinv = H.DevBuf(4), H.DevBuf(4)
+    given, amax, sinv = amax, H.DevBuf(4), H.DevBuf(4)
     P.fill(amax.ptr, 4, 0xFF)
     P.fill(sinv.ptr, 4, 0xFF)
     nq, nqt = rows * ldq, cols * ldqt
     bq, bqt = device_image(nq), device_image(nqt) if transpose else None
-    H.fp8_amax(CODE[dt], rows, cols, ld, bx.ptr, amax.ptr)
+    if given is None:
+        H.fp8_amax(CODE[dt], rows, cols, ld, bx.ptr, amax.ptr)
+    else:
+        amax = H.DevBuf.from_numpy(np.array([given], dtype=np.float32))
     H.fp8_quantize(CODE[dt], fmt, rows, cols, ld, bx.ptr, amax.ptr, bq.ptr, ldq, sinv.ptr, bqt.ptr if transpose else None, ldqt if transpose else 0)
     H.device_sync()
     q_all = bq.to_numpy(nq + P.GUARD, np.uint8)
@@ -43,9 +47,9 @@ def run(x, dt, fmt, transpose=True, ld=None, ldq=None, ldqt=None):
     return int(amax.to_numpy(1, np.uint32)[0]), sinv.to_numpy(1, np.float32)[0], q_all, qt_all
 
 
-def expected_images(x, dt, fmt, ldq=None, ldqt=None):
+def expected_images(x, dt, fmt, ldq=None, ldqt=None, amax=None):
     rows, cols = x.shape
-    q, qt, sinv, bits = R.quantize(R.to_f32(x, dt), fmt)
+    q, qt, sinv, bits = R.quantize(R.to_f32(x, dt), fmt, amax)
     ldq, ldqt = ldq or cols, ldqt or qt.shape[1]
     q_all = np.full(rows * ldq + P.GUARD, FILL, dtype=np.uint8)
     q_all[:rows * ldq].reshape(rows, ldq)[:, :cols] = q
@@ -54,9 +58,9 @@ def expected_images(x, dt, fmt, ldq=None, ldqt=None):
     return bits, sinv, q_all, qt_all
 
 
-def check(x, dt, fmt, transpose=True, ld=None, ldq=None, ldqt=None, what=""):
-    got = run(x, dt, fmt, transpose, ld, ldq, ldqt)
-    want = expected_images(x, dt, fmt, ldq, ldqt)
+def check(x, dt, fmt, transpose=True, ld=None, ldq=None, ldqt=None, what="", amax=None):
+    got = run(x, dt, fmt, transpose, ld, ldq, ldqt, amax)
+    want = expected_images(x, dt, fmt, ldq, ldqt, amax)
     assert got[0] == want[0], f"{what}: amax bits {got[0]:#x}, expected {want[0]:#x}"
     assert got[1].view(np.uint32) == want[1].view(np.uint32), f"{what}: scale_inv {got[1]}, expected {want[1]}"
     bad = np.flatnonzero(got[2] != want[2])

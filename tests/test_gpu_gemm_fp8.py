@@ -38,24 +38,31 @@ def scale(v):
     return H.DevBuf.from_numpy(np.array([v], dtype=np.float32))
 
 
+def launch(ba, lda, bb, ldb, bsa, bsb, fa, fb, out, M, N, K, ldc):
+    """One kf_gemm_fp8 on operands that are on the device already. Returns the stored [M, N] window and asserts that the rest of the C
+    allocation (pitch gaps and guard band) kept its poison."""
+    code, store = OUT[out]
+    nbytes = M * ldc * np.dtype(store).itemsize
+    bc = H.DevBuf(nbytes + P.GUARD)
+    P.fill(bc.ptr, nbytes + P.GUARD, FILL)
+    H.gemm_fp8(fa, fb, code, M, N, K, ba.ptr, lda, bb.ptr, ldb, bsa.ptr, bsb.ptr, bc.ptr, ldc)
+    H.device_sync()
+    raw = bc.to_numpy(nbytes + P.GUARD, np.uint8)
+    img = raw[:nbytes].view(store).reshape(M, ldc)
+    assert (img[:, N:].view(np.uint8) == FILL).all() and (raw[nbytes:] == FILL).all(), "bytes outside C[M, N] were written"
+    return np.ascontiguousarray(img[:, :N])
+
+
+def default_ldc(N):
+    return N + 8 if N % 2 == 0 else N + 5    # rows of C that keep and that lose 16-byte alignment
+
+
 def run(a, fa, b, fb, out, sa=1.0, sb=1.0, lda=None, ldb=None, ldc=None, repeat=1):
     """a [M, K], b [N, K] codes. Returns the decoded [M, N] window as f64 and asserts that the rest of the C allocation kept its poison."""
     (M, K), N = a.shape, b.shape[0]
-    lda, ldb, ldc = lda or K + 16, ldb or K + 32, ldc or (N + 8 if N % 2 == 0 else N + 5)   # rows of C that keep and that lose 16-byte alignment
-    code, store = OUT[out]
-    es = np.dtype(store).itemsize
+    lda, ldb, ldc = lda or K + 16, ldb or K + 32, ldc or default_ldc(N)
     ba, bb, bsa, bsb = operand(a, lda), operand(b, ldb), scale(sa), scale(sb)
-    nbytes = M * ldc * es
-    results = []
-    for _ in range(repeat):
-        bc = H.DevBuf(nbytes + P.GUARD)
-        P.fill(bc.ptr, nbytes + P.GUARD, FILL)
-        H.gemm_fp8(fa, fb, code, M, N, K, ba.ptr, lda, bb.ptr, ldb, bsa.ptr, bsb.ptr, bc.ptr, ldc)
-        H.device_sync()
-        raw = bc.to_numpy(nbytes + P.GUARD, np.uint8)
-        img = raw[:nbytes].view(store).reshape(M, ldc)
-        assert (img[:, N:].view(np.uint8) == FILL).all() and (raw[nbytes:] == FILL).all(), "bytes outside C[M, N] were written"
-        results.append(np.ascontiguousarray(img[:, :N]))
+    results = [launch(ba, lda, bb, ldb, bsa, bsb, fa, fb, out, M, N, K, ldc) for _ in range(repeat)]
     for r in results[1:]:
         assert np.array_equal(r.view(np.uint8), results[0].view(np.uint8)), "two runs differ"
     return R.to_f32(results[0], out).astype(np.float64)
