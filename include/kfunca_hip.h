@@ -1111,6 +1111,37 @@ int kf_gemm_fp8(int fmt_a, int fmt_b, int out_dtype, int64_t M, int64_t N, int64
                 int64_t ldb, const float *scale_inv_a /* device, [1] */, const float *scale_inv_b /* device, [1] */, void *C,
                 int64_t ldc, void *stream);
 
+/* ---- symmetric product and the Muon optimizer's device steps (no reference counterpart) ---------------------------------------------
+ *     gemm_sym      C[M, M] = alpha X X^T + beta D + gamma I. X is [M, K] row-major (ldx >= K); D (NULL: no beta term; never read when
+ *                   beta == 0) is a symmetric [M, M] matrix (ldd >= M) of which only the values at and below the diagonal are used; C has
+ *                   ldc >= M and overlaps neither X nor D. dtype KF_F32, KF_BF16 or KF_F16 for all three; f32 accumulation, one rounding.
+ *                   Only the tiles on and below the diagonal are computed and each is stored to both places, so C is BITWISE symmetric;
+ *                   every element is written by exactly one workgroup, no atomics, no workspace: two runs give the same bits. 16-bit
+ *                   operands with M % 128 == 0, K % 64 == 0, K >= 64, leading dimensions multiples of 8 and 16-byte-aligned bases run on
+ *                   the matrix cores (profile labels gemm_sym_bf16_mfma / gemm_sym_f16_mfma); everything else takes one plain kernel
+ *                   (gemm_sym_generic) with the same semantics. M == 0 is KF_OK without a launch; K == 0 gives beta D + gamma I.
+ *     muon_prepare  g = grad * grad_scale over the dense [rows, cols] grad (KF_F32, KF_BF16 or KF_F16); momentum = mu momentum + g
+ *                   (dense f32 [rows, cols]; NULL with mu == 0: no state); u = g + mu momentum (nesterov) or momentum;
+ *                   X = bf16(u / (|u|_F + 1e-7)) in the WIDE orientation [min(rows, cols), max(rows, cols)] - transposed when
+ *                   rows > cols - inside a bf16 matrix [xm, xn] with pitch ldx, whose elements outside the wide matrix are written as +0
+ *                   (whole tiles for the products that follow). The norm is formed on the device from per-block partial sums in the
+ *                   workspace (kf_muon_prepare_workspace_bytes; 4-byte aligned, no initialisation), folded in one fixed order.
+ *     muon_apply    p = p (1 - lr wd) - lr scale O over the dense [rows, cols] param (KF_F32; KF_BF16 or KF_F16 with an optional dense
+ *                   f32 master: the update then runs on the master and the param is rewritten from it, round to nearest even). O is the
+ *                   bf16 wide matrix (pitch ldo), read transposed when rows > cols; lr is a device float [1].
+ * Nothing synchronises, allocates, uses atomics or reads a value back: every entry can be captured with kf_graph_*, and two calls give
+ * the same bits. Profile labels muon_prepare, muon_apply. Every argument is checked before any device call, with the entry's name in
+ * kf_last_error(): KF_ERR_INVALID for a dtype outside the list, negative extents, a short leading dimension, null or misaligned
+ * pointers, C overlapping X or D, mu outside [0, 1), a master for an f32 param, a workspace that is too small.
+ */
+int kf_gemm_sym(int dtype, int64_t M, int64_t K, float alpha, const void *X, int64_t ldx, float beta, const void *D /* or NULL */, int64_t ldd,
+                float gamma, void *C, int64_t ldc, void *stream);
+int kf_muon_prepare_workspace_bytes(int64_t rows, int64_t cols, size_t *bytes);
+int kf_muon_prepare(int grad_dtype, int64_t rows, int64_t cols, const void *grad, float *momentum /* or NULL */, float mu, int nesterov,
+                    float grad_scale, void *X, int64_t xm, int64_t xn, int64_t ldx, void *workspace, size_t workspace_bytes, void *stream);
+int kf_muon_apply(int param_dtype, int64_t rows, int64_t cols, void *param, float *master /* or NULL */, const void *O, int64_t ldo,
+                  const float *lr /* device, [1] */, float weight_decay, float scale, void *stream);
+
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128
 int kf_comm_unique_id(char id[KF_COMM_ID_BYTES]);

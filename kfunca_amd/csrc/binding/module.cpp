@@ -339,6 +339,30 @@ PYBIND11_MODULE(_C, m) {
             return py::make_tuple(m, v, s, ms.defined() ? py::cast(ms) : py::none());
         }, py::arg("param"))
         .def("__len__", &gpu::AdamW::size);
+    m.def("gemm_sym", [](const Tensor &x, float alpha, py::object d, float beta, float gamma) {
+        return gpu::gemm_sym(x, alpha, d.is_none() ? Tensor() : d.cast<Tensor>(), beta, gamma);
+    }, py::arg("x"), py::arg("alpha") = 1.0f, py::arg("d") = py::none(), py::arg("beta") = 0.0f, py::arg("gamma") = 0.0f);
+    m.def("newton_schulz", [](const Tensor &x, int64_t steps, std::tuple<double, double, double> coeffs) {
+        return gpu::newton_schulz(x, steps, std::get<0>(coeffs), std::get<1>(coeffs), std::get<2>(coeffs));
+    }, py::arg("x"), py::arg("steps") = 5, py::arg("coeffs") = std::make_tuple(3.4445, -4.7750, 2.0315));
+    py::class_<gpu::Muon, std::shared_ptr<gpu::Muon>>(m, "Muon", py::module_local())
+        .def(py::init([](const std::vector<Tensor> &params, double lr, double momentum, bool nesterov, int64_t ns_steps, double weight_decay,
+                         const std::string &adjust, double grad_scale, bool master_weights) {
+                 if (adjust != "spectral" && adjust != "rms") throw py::value_error("Muon: adjust '" + adjust + "' is not 'spectral' or 'rms'");
+                 return std::make_shared<gpu::Muon>(params, lr, momentum, nesterov, ns_steps, weight_decay,
+                                                    adjust == "rms" ? gpu::Muon::Adjust::Rms : gpu::Muon::Adjust::Spectral, grad_scale, master_weights);
+             }),
+             py::arg("params"), py::arg("lr"), py::arg("momentum") = 0.95, py::arg("nesterov") = true, py::arg("ns_steps") = 5, py::arg("weight_decay") = 0.0,
+             py::arg("adjust") = "spectral", py::arg("grad_scale") = 1.0, py::arg("master_weights") = true)
+        .def("step", &gpu::Muon::step)
+        .def("zero_grad", &gpu::Muon::zero_grad)
+        .def("set_lr", &gpu::Muon::set_lr, py::arg("lr"))
+        .def_property_readonly("lr", &gpu::Muon::lr)
+        .def("state", [](const gpu::Muon &o, const Tensor &p) -> py::tuple {
+            auto [buf, ms] = o.state(p);
+            return py::make_tuple(buf, ms.defined() ? py::cast(ms) : py::none());
+        }, py::arg("param"))
+        .def("__len__", &gpu::Muon::size);
     py::class_<gpu::GradBucket, std::shared_ptr<gpu::GradBucket>>(m, "GradBucket", py::module_local())
         .def(py::init([](const std::vector<Tensor> &params, double cap_mb, bool accum_f32) {
                  return gpu::GradBucket::create(params, (int64_t)(cap_mb * 1048576.0), accum_f32);

@@ -44,4 +44,40 @@ private:
     int device_ = 0;
 };
 
+// C [M, M] = alpha x x^T + beta d + gamma I on kf_gemm_sym (x [M, K], d an optional symmetric [M, M] of x's dtype): bitwise symmetric.
+// No autograd.
+Tensor gemm_sym(const Tensor &x, float alpha, const Tensor &d, float beta, float gamma);
+
+// The Newton-Schulz orthogonalisation Muon applies to a momentum: X = x / (|x|_F + 1e-7) in bf16, then `steps` times
+// A = X X^T, X <- (a I + b A + c A A) X. x is 2-D float, half or bfloat16; the bfloat16 result has x's shape.
+Tensor newton_schulz(const Tensor &x, int64_t steps, double a, double b, double c);
+
+// Muon over 2-D params: p = p (1 - lr wd) - lr scale NS(momentum), one param after the other through shared scratch.
+class Muon {
+public:
+    enum class Adjust { Spectral, Rms }; // scale = sqrt(max(1, rows / cols)) or 0.2 sqrt(max(rows, cols))
+    // All state and scratch live on the device and are allocated here: the f32 momentum buffers (zero), the f32 masters of 16-bit params
+    // (master_weights), the iteration's four matrices sized for the largest param, the partial sums, the product scratch and lr.
+    // step() allocates nothing and reads nothing back: it can be captured in a graph from the first call.
+    Muon(const std::vector<Tensor> &params, double lr, double momentum, bool nesterov, int64_t ns_steps, double weight_decay, Adjust adjust,
+         double grad_scale, bool master_weights);
+    void step();                          // the params whose grad() is defined; the others and their state are left alone
+    void zero_grad();
+    void set_lr(double lr);               // the device scalar, written in stream order; refused while a graph capture is open
+    double lr() const { return lr_value_; }
+    std::tuple<Tensor, Tensor> state(const Tensor &param) const; // (momentum buffer, master or undefined)
+    int64_t size() const { return (int64_t)params_.size(); }
+
+private:
+    std::vector<Tensor> params_, momentum_, master_;
+    std::unordered_map<TensorImpl *, int> index_;
+    Tensor x_[2], a_, b_, partial_, gemm_scratch_, lr_;
+    double lr_value_;
+    float mu_, weight_decay_, grad_scale_;
+    bool nesterov_;
+    int64_t ns_steps_;
+    Adjust adjust_;
+    int device_ = 0;
+};
+
 } // namespace gpu

@@ -474,6 +474,36 @@ def adamw_step(tensors, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, ma
     return ws
 
 
+def gemm_sym(dtype, M, K, alpha, X, ldx, Cp, ldc, beta=0.0, D=None, ldd=0, gamma=0.0, stream=None):
+    """kf_gemm_sym: C [M, M] = alpha X X^T + beta D + gamma I (X [M, K]; D symmetric or None); C comes out bitwise symmetric."""
+    check(lib().kf_gemm_sym(dtype, M, K, alpha, X, ldx, beta, D, ldd, gamma, Cp, ldc, stream))
+
+
+def muon_prepare_workspace_bytes(rows, cols) -> int:
+    need = C.c_size_t(0)
+    check(lib().kf_muon_prepare_workspace_bytes(rows, cols, C.byref(need)))
+    return need.value
+
+
+def muon_prepare(grad_dtype, rows, cols, grad, momentum, mu, nesterov, X, xm, xn, ldx, grad_scale=1.0, workspace=None, workspace_bytes=None, stream=None):
+    """kf_muon_prepare: momentum = mu momentum + grad * grad_scale (momentum None: no state, mu 0), X (bf16 [xm, xn]) = u / (|u|_F + 1e-7)
+    in the wide orientation, zero outside it. Without a workspace, one of the queried size is made here and returned (keep it until the
+    stream is synchronised)."""
+    ws = None
+    if workspace is None:
+        workspace_bytes = muon_prepare_workspace_bytes(rows, cols)
+        ws = DevBuf(workspace_bytes)
+        workspace = ws.ptr
+    check(lib().kf_muon_prepare(grad_dtype, rows, cols, grad, momentum, mu, int(bool(nesterov)), grad_scale, X, xm, xn, ldx, workspace, workspace_bytes,
+                                stream))
+    return ws
+
+
+def muon_apply(param_dtype, rows, cols, param, master, O, ldo, lr, weight_decay=0.0, scale=1.0, stream=None):
+    """kf_muon_apply: param = param (1 - lr wd) - lr scale O with O the bf16 wide matrix; lr: a device f32 [1]; master: f32 or None."""
+    check(lib().kf_muon_apply(param_dtype, rows, cols, param, master, O, ldo, lr, weight_decay, scale, stream))
+
+
 def index_put(desc: IterDesc, sizes, strides_bytes, stream=None):
     n = len(sizes)
     a = (C.c_int64 * n)(*sizes)
