@@ -1142,6 +1142,25 @@ int kf_muon_prepare(int grad_dtype, int64_t rows, int64_t cols, const void *grad
 int kf_muon_apply(int param_dtype, int64_t rows, int64_t cols, void *param, float *master /* or NULL */, const void *O, int64_t ldo,
                   const float *lr /* device, [1] */, float weight_decay, float scale, void *stream);
 
+/* ---- chunked linear attention with a scalar per-step decay ----
+ *   S_t = exp(g_t) S_{t-1} + k_t v_t^T,  o_t = scale q_t S_t,  that is  O = scale ((Q K^T) . A) V  with  A[t, s] = exp(G_t - G_s) for s <= t
+ *   (else 0) and G the inclusive prefix sum of g. q, k [B, H, S, Dk] and v, o, d_o [B, H, S, Dv] contiguous, KF_BF16 or KF_F16; g, dg
+ *   [B, H, S] float with g <= 0; Dk == Dv in {64, 128}; any S >= 1 (a last chunk of fewer than 64 steps is handled inside the kernels: no
+ *   padded copies, no store past the end). The forward takes no workspace. The backward writes dq, dk, dv and the exact
+ *   dg_r = sum_{t >= r} (q_t . dq_t - k_t . dk_t), summed in f32 in one fixed order; its workspace (kf_linear_attn_bwd_workspace_bytes,
+ *   16-byte aligned) needs no initialisation. Nothing synchronises, allocates, uses atomics or reads a value back: both entries can be
+ *   captured and two calls give the same bits. Profile labels linear_attn_fwd_{bf16,f16}, linear_attn_bwd_{bf16,f16}.
+ * Every argument is checked before any device call, with the entry's name in kf_last_error(): KF_ERR_INVALID for a null pointer, a
+ * non-positive extent, a scale that is zero or not finite, a base not aligned to 16 bytes; KF_ERR_UNSUPPORTED for another dtype,
+ * Dk != Dv or a head size outside {64, 128}; KF_ERR_WORKSPACE for a missing or short workspace.
+ */
+int kf_linear_attn_fwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                       const void *v, const float *g, void *o, void *stream);
+int kf_linear_attn_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, size_t *bytes);
+int kf_linear_attn_bwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                       const void *v, const float *g, const void *d_o, void *dq, void *dk, void *dv, float *dg, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128
 int kf_comm_unique_id(char id[KF_COMM_ID_BYTES]);

@@ -16,6 +16,7 @@
 #include "expert_linear.h"
 #include "fp8.h"
 #include "glu.h"
+#include "linear_attn.h"
 #include "linear_ce.h"
 #include "moe.h"
 #include "softmax.h"
@@ -339,6 +340,12 @@ PYBIND11_MODULE(_C, m) {
             return py::make_tuple(m, v, s, ms.defined() ? py::cast(ms) : py::none());
         }, py::arg("param"))
         .def("__len__", &gpu::AdamW::size);
+    m.def("linear_attention", [](const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &g, py::object scale) {
+        return gpu::linear_attention(q, k, v, g, scale.is_none() ? std::nullopt : std::optional<float>(scale.cast<float>()));
+    }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("g"), py::arg("scale") = py::none(),
+          "linear_attention(q, k, v, g, scale=None): S_t = exp(g_t) S_{t-1} + k_t v_t^T, o_t = scale q_t S_t in 64-step chunks on the matrix cores. "
+          "q, k, v [B, H, S, D] half or bfloat16 with D in {64, 128}; g [B, H, S] float, <= 0; scale defaults to D ** -0.5. Differentiable in "
+          "q, k, v and g (the exact gradient of g); forward and backward can be captured into a graph.");
     m.def("gemm_sym", [](const Tensor &x, float alpha, py::object d, float beta, float gamma) {
         return gpu::gemm_sym(x, alpha, d.is_none() ? Tensor() : d.cast<Tensor>(), beta, gamma);
     }, py::arg("x"), py::arg("alpha") = 1.0f, py::arg("d") = py::none(), py::arg("beta") = 0.0f, py::arg("gamma") = 0.0f);

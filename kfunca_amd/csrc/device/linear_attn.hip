@@ -1,0 +1,595 @@
+// Chunked linear attention with a scalar per-step decay for gfx950, forward and backward:
+//
+//   S_t = exp(g_t) S_{t-1} + k_t v_t^T,   o_t = scale q_t S_t        <=>   O = scale ((Q K^T) . A) V,  A[t, s] = exp(G_t - G_s) for s <= t
+//
+//   kf_linear_attn_fwd   one workgroup per (b, h, 64 columns of Dv) walks the head's 64-step chunks in order; the [Dk, 64] state stays in
+//                        f32 MFMA accumulators for the whole walk
+//   kf_linear_attn_bwd   an ascending walk (S recomputed; dQ and a_t = q_t . dq_t), a descending walk (dS carried; dK, dV and
+//                        b_t = k_t . dk_t), one workgroup per (b, h) each with the whole [Dk, Dv] state in accumulators, then
+//                        dg_r = sum_{t >= r} (a_t - b_t) in a fixed order
+//
+// Every decay factor is exp of a non-positive difference of in-chunk prefix sums (G_t - G_s for s <= t, G_t - G_start, G_end - G_s), so
+// nothing overflows and nothing is divided. The chunk's Q / K / V / dO tiles arrive by LDS-DMA through buffer descriptors that end with
+// the sequence: rows past it read as zeros, their g counts as 0, and their stores are dropped. All tiles are 64 rows of 16-bit values
+// with an XOR swizzle on the 16-byte chunk; a fragment whose contraction index runs along a tile's columns is one ds_read_b128, one
+// whose contraction index runs along the rows is two ds_read_b64_tr_b16 (l_frag_row / l_frag_col). No atomics, no workspace for the
+// forward, nothing read back: results are reproducible to the bit and the calls can be captured.
+#include <math.h>
+
+#include "common.h"
+
+namespace kf {
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 l_bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 l_f16x8;
+typedef __attribute__((ext_vector_type(16))) float l_f32x16;
+typedef __attribute__((ext_vector_type(4))) uint32_t l_u32x4;
+typedef __attribute__((ext_vector_type(2))) uint32_t l_u32x2;
+
+constexpr int L_C = 64;           // chunk length
+constexpr int L_PT = L_C * 128;   // bytes of a [64][64] 16-bit tile (P, M, a V slice)
+constexpr int L_G = 2 * 3 * L_C * 4; // two parities of {G, kd, qd}, 64 floats each
+
+struct LinArgs {
+    const char *q, *k, *v, *d_o;
+    const float *g;
+    char *o, *dq, *dk, *dv;
+    float *wa, *wb, *dg;
+    int64_t S;
+    float scale;
+};
+
+template <bool BF>
+__device__ __forceinline__ l_f32x16 l_mma(l_u32x4 a, l_u32x4 b, l_f32x16 c) {
+    if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(l_bf16x8, a), __builtin_bit_cast(l_bf16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(l_f16x8, a), __builtin_bit_cast(l_f16x8, b), c, 0, 0, 0);
+}
+template <bool BF> __device__ __forceinline__ uint32_t l_cvt16(float v) { return BF ? f32_to_bf16(v).x : f32_to_f16(v).x; }
+template <bool BF> __device__ __forceinline__ float l_f32(uint32_t h) { return BF ? bf16_to_f32(bf16_t{(uint16_t)h}) : f16_to_f32(f16_t{(uint16_t)h}); }
+
+// LDS image of a tile with RB-byte rows: the 16-B chunk ch of row r at chunk position ch ^ f(r) (gemm.hip's f for 128-B rows,
+// attention.hip's for 256-B rows: both conflict-free for row reads and for the 4-row x 16-column blocks of the transposed read)
+template <int RB> __device__ __forceinline__ int l_off(int row, int ch) {
+    if constexpr (RB == 128) return row * 128 + ((ch ^ ((row >> 1) & 7)) << 4);
+    else return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
+}
+// accumulator register e of lane half h <-> row of the 32 x 32 block (the column is lane & 31)
+__device__ __forceinline__ int l_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+
+// MFMA operand whose 32 rows are the tile's rows row0 .. row0 + 31 and whose 16 k are the tile's columns k0 .. k0 + 15
+template <int RB> __device__ __forceinline__ l_u32x4 l_frag_row(unsigned tile, int row0, int k0) {
+    const int lane = threadIdx.x & 63;
+    l_u32x4 r;
+    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(tile + (unsigned)l_off<RB>(row0 + (lane & 31), (k0 >> 3) + (lane >> 5))) : "memory");
+    return r;
+}
+// MFMA operand whose 32 rows are the tile's COLUMNS col0 .. col0 + 31 and whose 16 k are the tile's rows r0 .. r0 + 15. Each group of 16
+// lanes hands the transposed read a 4-row x 16-column block (lane i: row i >> 2, columns 4 (i & 3) ..) and lane i gets column i of it:
+// lane half h reads rows r0 + 8 h + 0..3, then + 4..7 - the k order of l_frag_row.
+template <int RB> __device__ __forceinline__ l_u32x4 l_frag_col(unsigned tile, int col0, int r0) {
+    const int lane = threadIdx.x & 63, g = lane >> 4, i = lane & 15;
+    const int row = r0 + 8 * (g >> 1) + (i >> 2), col = col0 + 16 * (g & 1) + 4 * (i & 3);
+    const unsigned a0 = tile + (unsigned)(l_off<RB>(row, col >> 3) + (col & 7) * 2), a1 = tile + (unsigned)(l_off<RB>(row + 4, col >> 3) + (col & 7) * 2);
+    l_u32x2 lo, hi;
+    asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(lo), "=&v"(hi) : "v"(a0), "v"(a1) : "memory");
+    return l_u32x4{lo[0], lo[1], hi[0], hi[1]};
+}
+// element j of the fragment times w[j], in f32, one rounding
+template <bool BF> __device__ __forceinline__ l_u32x4 l_scale_frag(l_u32x4 f, const float (&w)[8]) {
+    l_u32x4 r;
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+        r[p] = l_cvt16<BF>(l_f32<BF>(f[p] & 0xffffu) * w[2 * p]) | (l_cvt16<BF>(l_f32<BF>(f[p] >> 16) * w[2 * p + 1]) << 16);
+    return r;
+}
+
+// the descriptor of `bytes` bytes at base; its inputs through readfirstlane (gemm_fp8.hip): block-uniform to the compiler too
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t l_rsrc(const char *base, uint32_t bytes) {
+    const uint64_t p = (uint64_t)(uintptr_t)base;
+    const uint64_t u = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)p) |
+                       ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(p >> 32)) << 32);
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)u, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
+}
+// rows 0 .. 63 of a chunk (RB bytes of each, from byte cb of rows ld bytes apart) -> tile. One wave-instruction moves 1 KiB to consecutive
+// LDS bytes, so the swizzle is on the SOURCE chunk; a row at or past `valid` asks for the descriptor's end and gets 16 zero bytes.
+template <int RB> __device__ __forceinline__ void l_stage(const char *chunk, int valid, uint32_t ld, uint32_t cb, char *tile) {
+    const uint32_t end = (uint32_t)valid * ld;
+    const __amdgpu_buffer_rsrc_t rs = l_rsrc(chunk, end);
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int CPR = RB / 16, ROWS = 64 / CPR, OPW = RB / 64; // chunks per row, rows per instruction, instructions per wave
+#pragma unroll
+    for (int i = 0; i < OPW; ++i) {
+        const int row0 = (wid * OPW + i) * ROWS, row = row0 + lane / CPR, pos = lane % CPR;
+        const uint32_t src = (uint32_t)(l_off<RB>(row, pos) - row * RB); // the chunk that belongs at position pos: pos ^ f(row)
+        const uint32_t voff = row < valid ? (uint32_t)row * ld + cb + src : end;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)(tile + row0 * RB), 16, (int)voff, 0, 0, 0);
+    }
+}
+__device__ __forceinline__ void l_landed() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+// wave 0: the chunk's inclusive prefix sum of g in f32 (a wave scan over 64 values; steps past the sequence count as 0) and the two
+// decay vectors every product of the chunk takes: G[t] = G_t - G_start, kd[s] = exp(G_end - G_s), qd[t] = scale exp(G_t - G_start)
+__device__ __forceinline__ void l_scan(const float *g, int valid, float scale, float *out) {
+    if (threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    float x = lane < valid ? g[lane] : 0.f;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    const float total = __shfl(x, 63);
+    out[lane] = x;
+    out[64 + lane] = expf(total - x);
+    out[128 + lane] = scale * expf(x);
+}
+
+// acc (t, s) of block (tb, sb) -> scale acc exp(G_t - G_s) for s <= t, else 0 -> one rounding -> the [t][s] tile
+template <bool BF> __device__ __forceinline__ void l_mask_store(const l_f32x16 &acc, char *tile, int tb, int sb, const float (&gt)[16], float gs, float scale) {
+    const int lane = threadIdx.x & 63, xl = lane & 31, hl = lane >> 5, s = 32 * sb + xl;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int t = 32 * tb + l_row(e, hl);
+        const float v = s <= t ? acc[e] * scale * expf(gt[e] - gs) : 0.f;
+        *(uint16_t *)(tile + l_off<128>(t, s >> 3) + (s & 7) * 2) = (uint16_t)l_cvt16<BF>(v);
+    }
+}
+// a state block (rows d of block db in the registers, column dv = lane & 31 of block dvb) -> the 16-bit copy [dv][d], 8-byte stores
+template <bool BF, int RB> __device__ __forceinline__ void l_state_store(const l_f32x16 &s, char *tile, int db, int dvb) {
+    const int lane = threadIdx.x & 63, xl = lane & 31, hl = lane >> 5;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int d = 32 * db + 8 * q + 4 * hl;
+        uint2 w;
+        w.x = l_cvt16<BF>(s[4 * q]) | (l_cvt16<BF>(s[4 * q + 1]) << 16);
+        w.y = l_cvt16<BF>(s[4 * q + 2]) | (l_cvt16<BF>(s[4 * q + 3]) << 16);
+        *(uint2 *)(tile + l_off<RB>(32 * dvb + xl, d >> 3) + (d & 7) * 2) = w;
+    }
+}
+// state <- decay state + (rows of tile A)^T (diag(w) rows of tile B): blocks (db[i], dvb), k = the chunk's 64 steps. The 16-bit rounding
+// of w B is the one rounding an operand takes on its way into the state.
+template <bool BF, int RBA, int RBB, int N>
+__device__ __forceinline__ void l_state_update(l_f32x16 (&st)[N], unsigned tA, unsigned tB, const int (&db)[N], int dvb, float decay, const float (&w)[4][8]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) st[i][e] *= decay;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        const l_u32x4 b = l_scale_frag<BF>(l_frag_col<RBB>(tB, 32 * dvb, 16 * ks), w[ks]);
+#pragma unroll
+        for (int i = 0; i < N; ++i) st[i] = l_mma<BF>(l_frag_col<RBA>(tA, 32 * db[i], 16 * ks), b, st[i]);
+    }
+}
+// per lane: w[ks][j] = vec[16 ks + 8 h + j], the k order of a fragment
+__device__ __forceinline__ void l_kvec(const float *vec, float (&w)[4][8]) {
+    const int hl = (threadIdx.x & 63) >> 5;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w[ks][j] = vec[16 * ks + 8 * hl + j];
+}
+__device__ __forceinline__ void l_rows(const float *vec, int blk, float (&r)[16]) {
+    const int hl = (threadIdx.x & 63) >> 5;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) r[e] = vec[32 * blk + l_row(e, hl)];
+}
+// sum over the 32 lanes of a half wave (the 32 columns of a block), every lane gets it
+__device__ __forceinline__ float l_half_sum(float x) {
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------------------------
+// Wave w: the P block and the O block of query rows 32 (w >> 1) (key / Dv columns 32 (w & 1)), and the state blocks of Dv columns
+// 32 (w & 1), Dk rows 32 ((w >> 1) + 2 i). LDS: Q[2] K[2] V-slice[2] | P | state copy [64 dv][Dk] | G.
+template <int D> constexpr int l_fwd_lds() { return 2 * (2 * L_C * D * 2 + L_PT) + L_PT + 64 * D * 2 + L_G; }
+
+template <bool BF, int D>
+__global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int RB = D * 2, QT = L_C * RB, NS = D / 64, NST = D / 64;
+    constexpr int oQ = 0, oK = 2 * QT, oV = 4 * QT, oP = oV + 2 * L_PT, oS = oP + L_PT, oG = oS + 64 * RB;
+    const unsigned sm = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)smem;
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), xl = lane & 31, hl = lane >> 5;
+    const int tb = wid >> 1, cbk = wid & 1;
+    const int64_t bh = blockIdx.x / NS, S = a.S;
+    const int slice = blockIdx.x % NS;
+    const char *q = a.q + bh * S * RB, *k = a.k + bh * S * RB, *v = a.v + bh * S * RB;
+    char *o = a.o + bh * S * RB;
+    const float *g = a.g + bh * S;
+    float *gbuf = (float *)(smem + oG);
+    const int nc = (int)((S + L_C - 1) / L_C);
+    auto stage = [&](int c) __attribute__((always_inline)) {
+        const int valid = (int)(S - (int64_t)c * L_C < L_C ? S - (int64_t)c * L_C : L_C), p = c & 1;
+        l_stage<RB>(q + (int64_t)c * QT, valid, RB, 0, smem + oQ + p * QT);
+        l_stage<RB>(k + (int64_t)c * QT, valid, RB, 0, smem + oK + p * QT);
+        l_stage<128>(v + (int64_t)c * QT, valid, RB, slice * 128, smem + oV + p * L_PT);
+    };
+    l_f32x16 st[NST];
+    int db[NST];
+#pragma unroll
+    for (int i = 0; i < NST; ++i) {
+        db[i] = tb + 2 * i;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) st[i][e] = 0.f;
+    }
+    stage(0);
+    for (int c = 0; c < nc; ++c) {
+        const int p = c & 1, valid = (int)(S - (int64_t)c * L_C < L_C ? S - (int64_t)c * L_C : L_C);
+        float *G = gbuf + p * 192;
+        l_scan(g + (int64_t)c * L_C, valid, a.scale, G);
+        l_landed(); // chunk c and its G are there for everyone; nobody reads chunk c - 1 any more
+        float gt[16], qdt[16], kdv[4][8];
+        l_rows(G, tb, gt);
+        l_rows(G + 128, tb, qdt);
+        l_kvec(G + 64, kdv);
+        const float gs = G[32 * cbk + xl], dec = expf(G[63]);
+        if (c + 1 < nc) stage(c + 1);
+        const unsigned tQ = sm + oQ + p * QT, tK = sm + oK + p * QT, tV = sm + oV + p * L_PT, tP = sm + oP, tS = sm + oS;
+        l_f32x16 acc, out;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = out[e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < D / 16; ++ks) acc = l_mma<BF>(l_frag_row<RB>(tQ, 32 * tb, 16 * ks), l_frag_row<RB>(tK, 32 * cbk, 16 * ks), acc);
+        l_mask_store<BF>(acc, smem + oP, tb, cbk, gt, gs, a.scale);
+        if (c > 0) { // the carried state, through its 16-bit copy; the row scaling stays in f32
+#pragma unroll
+            for (int ks = 0; ks < D / 16; ++ks) out = l_mma<BF>(l_frag_row<RB>(tQ, 32 * tb, 16 * ks), l_frag_row<RB>(tS, 32 * cbk, 16 * ks), out);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) out[e] *= qdt[e];
+        }
+        __syncthreads(); // P is whole; nobody reads the state copy any more
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) out = l_mma<BF>(l_frag_row<128>(tP, 32 * tb, 16 * ks), l_frag_col<128>(tV, 32 * cbk, 16 * ks), out);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int t = 32 * tb + l_row(e, hl);
+            if (t < valid) *(uint16_t *)(o + ((int64_t)c * L_C + t) * RB + (slice * 64 + 32 * cbk + xl) * 2) = (uint16_t)l_cvt16<BF>(out[e]);
+        }
+        if (c + 1 < nc) {
+            l_state_update<BF, RB, 128, NST>(st, tK, tV, db, cbk, dec, kdv);
+#pragma unroll
+            for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], cbk);
+        }
+    }
+}
+
+// ---- backward, ascending: dQ and a_t ---------------------------------------------------------------------------------------------------
+// Wave w: the dP block (32 (w >> 1), 32 (w & 1)), the dQ blocks of rows 32 (w >> 1) and Dk columns 32 ((w & 1) D / 64 + i), the state
+// blocks of Dv columns 32 w and every Dk row block at D = 128 (Dv columns 32 (w & 1), Dk rows 32 (w >> 1) at D = 64).
+// LDS: K[2] V[2] dO[2] | M | state copy [Dv][Dk] | G | a_t halves.
+template <int D> constexpr int l_asc_lds() { return 6 * L_C * D * 2 + L_PT + D * D * 2 + L_G + 2 * L_C * 4; }
+
+template <bool BF, int D>
+__global__ __launch_bounds__(256) void lin_bwd_asc_kernel(const LinArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int RB = D * 2, QT = L_C * RB, NQ = D / 64, NST = D == 128 ? 4 : 1;
+    constexpr int oK = 0, oV = 2 * QT, oO = 4 * QT, oM = 6 * QT, oS = oM + L_PT, oG = oS + D * RB, oA = oG + L_G;
+    const unsigned sm = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)smem;
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), xl = lane & 31, hl = lane >> 5;
+    const int tb = wid >> 1, cbk = wid & 1;
+    const int64_t bh = blockIdx.x, S = a.S;
+    const char *q = a.q + bh * S * RB, *k = a.k + bh * S * RB, *v = a.v + bh * S * RB, *d_o = a.d_o + bh * S * RB;
+    char *dq = a.dq + bh * S * RB;
+    const float *g = a.g + bh * S;
+    float *gbuf = (float *)(smem + oG), *asum = (float *)(smem + oA);
+    const int nc = (int)((S + L_C - 1) / L_C);
+    auto stage = [&](int c) __attribute__((always_inline)) {
+        const int valid = (int)(S - (int64_t)c * L_C < L_C ? S - (int64_t)c * L_C : L_C), p = c & 1;
+        l_stage<RB>(k + (int64_t)c * QT, valid, RB, 0, smem + oK + p * QT);
+        l_stage<RB>(v + (int64_t)c * QT, valid, RB, 0, smem + oV + p * QT);
+        l_stage<RB>(d_o + (int64_t)c * QT, valid, RB, 0, smem + oO + p * QT);
+    };
+    l_f32x16 st[NST];
+    int db[NST], qb[NQ];
+    const int sdv = D == 128 ? wid : cbk;
+#pragma unroll
+    for (int i = 0; i < NST; ++i) {
+        db[i] = D == 128 ? i : tb;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) st[i][e] = 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) qb[i] = cbk * NQ + i;
+    stage(0);
+    for (int c = 0; c < nc; ++c) {
+        const int p = c & 1, valid = (int)(S - (int64_t)c * L_C < L_C ? S - (int64_t)c * L_C : L_C);
+        float *G = gbuf + p * 192;
+        l_scan(g + (int64_t)c * L_C, valid, a.scale, G);
+        l_landed();
+        float gt[16], qdt[16], kdv[4][8];
+        l_rows(G, tb, gt);
+        l_rows(G + 128, tb, qdt);
+        l_kvec(G + 64, kdv);
+        const float gs = G[32 * cbk + xl], dec = expf(G[63]);
+        if (c + 1 < nc) stage(c + 1);
+        const unsigned tK = sm + oK + p * QT, tV = sm + oV + p * QT, tO = sm + oO + p * QT, tM = sm + oM, tS = sm + oS;
+        l_f32x16 acc, out[NQ];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NQ; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) out[i][e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < D / 16; ++ks) acc = l_mma<BF>(l_frag_row<RB>(tO, 32 * tb, 16 * ks), l_frag_row<RB>(tV, 32 * cbk, 16 * ks), acc);
+        l_mask_store<BF>(acc, smem + oM, tb, cbk, gt, gs, a.scale);
+        if (c > 0) { // dO S_prev^T: k runs over Dv, the rows of the state copy
+#pragma unroll
+            for (int ks = 0; ks < D / 16; ++ks) {
+                const l_u32x4 fa = l_frag_row<RB>(tO, 32 * tb, 16 * ks);
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) out[i] = l_mma<BF>(fa, l_frag_col<RB>(tS, 32 * qb[i], 16 * ks), out[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < NQ; ++i)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) out[i][e] *= qdt[e];
+        }
+        __syncthreads(); // M is whole; nobody reads the state copy any more
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const l_u32x4 fa = l_frag_row<128>(tM, 32 * tb, 16 * ks);
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) out[i] = l_mma<BF>(fa, l_frag_col<RB>(tK, 32 * qb[i], 16 * ks), out[i]);
+        }
+        float part[16]; // q_t . dq_t over this wave's columns, from the f32 rows
+#pragma unroll
+        for (int e = 0; e < 16; ++e) part[e] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NQ; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int t = 32 * tb + l_row(e, hl);
+                if (t < valid) {
+                    const int64_t at = ((int64_t)c * L_C + t) * RB + (32 * qb[i] + xl) * 2;
+                    *(uint16_t *)(dq + at) = (uint16_t)l_cvt16<BF>(out[i][e]);
+                    part[e] += l_f32<BF>(*(const uint16_t *)(q + at)) * out[i][e];
+                }
+            }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float s = l_half_sum(part[e]);
+            if (xl == 0) asum[cbk * L_C + 32 * tb + l_row(e, hl)] = s;
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < valid) a.wa[bh * S + (int64_t)c * L_C + threadIdx.x] = asum[threadIdx.x] + asum[L_C + threadIdx.x];
+        if (c + 1 < nc) {
+            l_state_update<BF, RB, RB, NST>(st, tK, tV, db, sdv, dec, kdv);
+#pragma unroll
+            for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], sdv);
+        }
+    }
+}
+
+// ---- backward, descending: dK, dV and b_t ----------------------------------------------------------------------------------------------
+// The carried dS[d][dv] = sum over later t of scale exp(G_t - G_end of this chunk) q_t dO_t^T. Wave w: the P and M blocks
+// (32 (w >> 1), 32 (w & 1)), the dK and dV blocks of key rows 32 (w >> 1) and columns 32 ((w & 1) D / 64 + i), the dS blocks as the
+// ascending walk's state blocks. LDS: NBUF x (Q K V dO) | P | M | dS copy [Dv][Dk] | G | b_t halves; four 16 KiB tiles twice do not
+// fit beside the rest at D = 128, so there the next chunk is fetched after this one's last read (NBUF 1).
+template <int D> constexpr int l_desc_nbuf() { return D == 64 ? 2 : 1; }
+template <int D> constexpr int l_desc_lds() { return l_desc_nbuf<D>() * 4 * L_C * D * 2 + 2 * L_PT + D * D * 2 + L_G + 2 * L_C * 4; }
+
+template <bool BF, int D>
+__global__ __launch_bounds__(256) void lin_bwd_desc_kernel(const LinArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int RB = D * 2, QT = L_C * RB, NQ = D / 64, NST = D == 128 ? 4 : 1, NBUF = l_desc_nbuf<D>();
+    constexpr int oP = NBUF * 4 * QT, oM = oP + L_PT, oS = oM + L_PT, oG = oS + D * RB, oB = oG + L_G;
+    const unsigned sm = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)smem;
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), xl = lane & 31, hl = lane >> 5;
+    const int tb = wid >> 1, cbk = wid & 1;
+    const int64_t bh = blockIdx.x, S = a.S;
+    const char *q = a.q + bh * S * RB, *k = a.k + bh * S * RB, *v = a.v + bh * S * RB, *d_o = a.d_o + bh * S * RB;
+    char *dk = a.dk + bh * S * RB, *dv = a.dv + bh * S * RB;
+    const float *g = a.g + bh * S;
+    float *gbuf = (float *)(smem + oG), *bsum = (float *)(smem + oB);
+    const int nc = (int)((S + L_C - 1) / L_C);
+    auto stage = [&](int c, int buf) __attribute__((always_inline)) {
+        const int valid = (int)(S - (int64_t)c * L_C < L_C ? S - (int64_t)c * L_C : L_C);
+        char *base = smem + buf * 4 * QT;
+        l_stage<RB>(q + (int64_t)c * QT, valid, RB, 0, base);
+        l_stage<RB>(k + (int64_t)c * QT, valid, RB, 0, base + QT);
+        l_stage<RB>(v + (int64_t)c * QT, valid, RB, 0, base + 2 * QT);
+        l_stage<RB>(d_o + (int64_t)c * QT, valid, RB, 0, base + 3 * QT);
+    };
+    l_f32x16 st[NST];
+    int db[NST], cb[NQ];
+    const int sdv = D == 128 ? wid : cbk;
+#pragma unroll
+    for (int i = 0; i < NST; ++i) {
+        db[i] = D == 128 ? i : tb;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) st[i][e] = 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) cb[i] = cbk * NQ + i;
+    stage(nc - 1, 0);
+    for (int it = 0; it < nc; ++it) {
+        const int c = nc - 1 - it, buf = it % NBUF, valid = (int)(S - (int64_t)c * L_C < L_C ? S - (int64_t)c * L_C : L_C);
+        float *G = gbuf + (it & 1) * 192;
+        l_scan(g + (int64_t)c * L_C, valid, a.scale, G);
+        l_landed();
+        float gt[16];
+        l_rows(G, tb, gt);
+        const float gs = G[32 * cbk + xl], dec = expf(G[63]);
+        if (NBUF == 2 && c > 0) stage(c - 1, buf ^ 1);
+        const unsigned tQ = sm + buf * 4 * QT, tK = tQ + QT, tV = tQ + 2 * QT, tO = tQ + 3 * QT, tP = sm + oP, tM = sm + oM, tS = sm + oS;
+        l_f32x16 accp, accm, ok[NQ], ov[NQ];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) accp[e] = accm[e] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NQ; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) ok[i][e] = ov[i][e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < D / 16; ++ks) {
+            accp = l_mma<BF>(l_frag_row<RB>(tQ, 32 * tb, 16 * ks), l_frag_row<RB>(tK, 32 * cbk, 16 * ks), accp);
+            accm = l_mma<BF>(l_frag_row<RB>(tO, 32 * tb, 16 * ks), l_frag_row<RB>(tV, 32 * cbk, 16 * ks), accm);
+        }
+        l_mask_store<BF>(accp, smem + oP, tb, cbk, gt, gs, a.scale);
+        l_mask_store<BF>(accm, smem + oM, tb, cbk, gt, gs, a.scale);
+        if (it > 0) { // V dS^T (k over Dv, the copy's rows) and K dS (k over Dk, the copy's columns)
+#pragma unroll
+            for (int ks = 0; ks < D / 16; ++ks) {
+                const l_u32x4 fv = l_frag_row<RB>(tV, 32 * tb, 16 * ks), fk = l_frag_row<RB>(tK, 32 * tb, 16 * ks);
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) {
+                    ok[i] = l_mma<BF>(fv, l_frag_col<RB>(tS, 32 * cb[i], 16 * ks), ok[i]);
+                    ov[i] = l_mma<BF>(fk, l_frag_row<RB>(tS, 32 * cb[i], 16 * ks), ov[i]);
+                }
+            }
+            float kds[16]; // (read where they are used, like qdv below: the walk at D = 128 has no registers to hold them across the chunk)
+            l_rows(G + 64, tb, kds); // this wave's key rows are block w >> 1 too
+#pragma unroll
+            for (int i = 0; i < NQ; ++i)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    ok[i][e] *= kds[e];
+                    ov[i][e] *= kds[e];
+                }
+        }
+        __syncthreads(); // P and M are whole; nobody reads the dS copy any more
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) { // k runs over the chunk's query rows: M^T Q and P^T dO
+            const l_u32x4 fm = l_frag_col<128>(tM, 32 * tb, 16 * ks), fp = l_frag_col<128>(tP, 32 * tb, 16 * ks);
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) {
+                ok[i] = l_mma<BF>(fm, l_frag_col<RB>(tQ, 32 * cb[i], 16 * ks), ok[i]);
+                ov[i] = l_mma<BF>(fp, l_frag_col<RB>(tO, 32 * cb[i], 16 * ks), ov[i]);
+            }
+        }
+        float part[16]; // k_s . dk_s over this wave's columns, from the f32 rows
+#pragma unroll
+        for (int e = 0; e < 16; ++e) part[e] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NQ; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int s = 32 * tb + l_row(e, hl), col = 32 * cb[i] + xl;
+                if (s < valid) {
+                    const int64_t at = ((int64_t)c * L_C + s) * RB + col * 2;
+                    *(uint16_t *)(dk + at) = (uint16_t)l_cvt16<BF>(ok[i][e]);
+                    *(uint16_t *)(dv + at) = (uint16_t)l_cvt16<BF>(ov[i][e]);
+                    part[e] += l_f32<BF>(*(const uint16_t *)(smem + buf * 4 * QT + QT + l_off<RB>(s, col >> 3) + (col & 7) * 2)) * ok[i][e];
+                }
+            }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float s = l_half_sum(part[e]);
+            if (xl == 0) bsum[cbk * L_C + 32 * tb + l_row(e, hl)] = s;
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < valid) a.wb[bh * S + (int64_t)c * L_C + threadIdx.x] = bsum[threadIdx.x] + bsum[L_C + threadIdx.x];
+        if (c > 0) {
+            float qdv[4][8];
+            l_kvec(G + 128, qdv);
+            l_state_update<BF, RB, RB, NST>(st, tQ, tO, db, sdv, dec, qdv);
+#pragma unroll
+            for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], sdv);
+            if (NBUF == 1) {
+                __syncthreads(); // the last read of this chunk's tiles
+                stage(c - 1, 0);
+            }
+        }
+    }
+}
+
+// dg_r = sum_{t >= r} (a_t - b_t): one wave per (b, h) walks the sequence downwards in blocks of 64, a suffix scan inside the block
+__global__ __launch_bounds__(64) void lin_dg_kernel(const LinArgs a) {
+    const int64_t S = a.S, base = (int64_t)blockIdx.x * S;
+    const int lane = threadIdx.x;
+    float carry = 0.f;
+    for (int64_t blk = (S + 63) / 64 - 1; blk >= 0; --blk) {
+        const int64_t t = blk * 64 + lane;
+        float x = t < S ? a.wa[base + t] - a.wb[base + t] : 0.f;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float y = __shfl_down(x, o);
+            if (lane + o < 64) x += y;
+        }
+        if (t < S) a.dg[base + t] = x + carry;
+        carry += __shfl(x, 0);
+    }
+}
+
+int lin_check(const char *who, int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale) {
+    KF_REQUIRE(B > 0 && H > 0 && S > 0 && Dk > 0 && Dv > 0, KF_ERR_INVALID, "%s: bad extents B %lld H %lld S %lld Dk %lld Dv %lld", who, (long long)B,
+               (long long)H, (long long)S, (long long)Dk, (long long)Dv);
+    KF_REQUIRE(isfinite(scale) && scale != 0.f, KF_ERR_INVALID, "%s: scale must be finite and not zero", who);
+    KF_REQUIRE(dtype == KF_BF16 || dtype == KF_F16, KF_ERR_UNSUPPORTED, "%s: dtype %d not supported (half, bfloat16)", who, dtype);
+    KF_REQUIRE(Dk == Dv, KF_ERR_UNSUPPORTED, "%s: Dk %lld != Dv %lld is not supported", who, (long long)Dk, (long long)Dv);
+    KF_REQUIRE(Dk == 64 || Dk == 128, KF_ERR_UNSUPPORTED, "%s: head size %lld not supported (64, 128)", who, (long long)Dk);
+    KF_REQUIRE(B * H < (int64_t)1 << 30 && S < (int64_t)1 << 40, KF_ERR_UNSUPPORTED, "%s: B * H %lld or S %lld above one grid", who, (long long)(B * H), (long long)S);
+    return KF_OK;
+}
+bool al16(const void *p) { return p && ((uintptr_t)p & 15u) == 0; }
+size_t lin_ws_bytes(int64_t B, int64_t H, int64_t S) { return (size_t)((2 * B * H * S * 4 + 15) / 16 * 16); }
+
+} // namespace
+} // namespace kf
+
+using namespace kf;
+
+extern "C" int kf_linear_attn_fwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                                  const void *v, const float *g, void *o, void *stream) {
+    const char *who = "kf_linear_attn_fwd";
+    KF_REQUIRE(q && k && v && g && o, KF_ERR_INVALID, "%s: null operand", who);
+    const int rc = lin_check(who, dtype, B, H, S, Dk, Dv, scale);
+    if (rc != KF_OK) return rc;
+    KF_REQUIRE(al16(q) && al16(k) && al16(v) && al16(g) && al16(o), KF_ERR_INVALID, "%s: an operand is not aligned to 16 bytes", who);
+    hipStream_t st = as_stream(stream);
+    LinArgs a{};
+    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.g = g; a.o = (char *)o;
+    a.S = S; a.scale = scale;
+    const bool bf = dtype == KF_BF16, big = Dk == 128;
+    const dim3 grid((unsigned)(B * H * (Dv / 64)));
+    KF_PROF(bf ? "linear_attn_fwd_bf16" : "linear_attn_fwd_f16", st);
+    return with_flags([&](auto BF, auto BIG) {
+        constexpr int D = decltype(BIG)::value ? 128 : 64;
+        return launch(lin_fwd_kernel<decltype(BF)::value, D>, grid, dim3(256), (size_t)l_fwd_lds<D>(), st, a);
+    }, bf, big);
+}
+
+extern "C" int kf_linear_attn_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, size_t *bytes) {
+    const char *who = "kf_linear_attn_bwd_workspace_bytes";
+    KF_REQUIRE(bytes, KF_ERR_INVALID, "%s: null bytes", who);
+    const int rc = lin_check(who, dtype, B, H, S, Dk, Dv, 1.f);
+    if (rc != KF_OK) return rc;
+    *bytes = lin_ws_bytes(B, H, S);
+    return KF_OK;
+}
+
+extern "C" int kf_linear_attn_bwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                                  const void *v, const float *g, const void *d_o, void *dq, void *dk, void *dv, float *dg, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    const char *who = "kf_linear_attn_bwd";
+    KF_REQUIRE(q && k && v && g && d_o && dq && dk && dv && dg, KF_ERR_INVALID, "%s: null operand", who);
+    const int rc = lin_check(who, dtype, B, H, S, Dk, Dv, scale);
+    if (rc != KF_OK) return rc;
+    KF_REQUIRE(al16(q) && al16(k) && al16(v) && al16(g) && al16(d_o) && al16(dq) && al16(dk) && al16(dv) && al16(dg), KF_ERR_INVALID,
+               "%s: an operand is not aligned to 16 bytes", who);
+    KF_REQUIRE(workspace && workspace_bytes >= lin_ws_bytes(B, H, S), KF_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
+               workspace ? workspace_bytes : (size_t)0, lin_ws_bytes(B, H, S));
+    KF_REQUIRE(al16(workspace), KF_ERR_INVALID, "%s: workspace is not aligned to 16 bytes", who);
+    hipStream_t st = as_stream(stream);
+    LinArgs a{};
+    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.g = g; a.d_o = (const char *)d_o;
+    a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv; a.dg = dg;
+    a.wa = (float *)workspace; a.wb = a.wa + B * H * S;
+    a.S = S; a.scale = scale;
+    const bool bf = dtype == KF_BF16, big = Dk == 128;
+    const dim3 grid((unsigned)(B * H));
+    KF_PROF(bf ? "linear_attn_bwd_bf16" : "linear_attn_bwd_f16", st);
+    const int r2 = with_flags([&](auto BF, auto BIG) {
+        constexpr int D = decltype(BIG)::value ? 128 : 64;
+        const int r = launch(lin_bwd_asc_kernel<decltype(BF)::value, D>, grid, dim3(256), (size_t)l_asc_lds<D>(), st, a);
+        return r != KF_OK ? r : launch(lin_bwd_desc_kernel<decltype(BF)::value, D>, grid, dim3(256), (size_t)l_desc_lds<D>(), st, a);
+    }, bf, big);
+    return r2 != KF_OK ? r2 : launch(lin_dg_kernel, grid, dim3(64), 0, st, a);
+}

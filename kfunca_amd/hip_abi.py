@@ -504,6 +504,29 @@ def muon_apply(param_dtype, rows, cols, param, master, O, ldo, lr, weight_decay=
     check(lib().kf_muon_apply(param_dtype, rows, cols, param, master, O, ldo, lr, weight_decay, scale, stream))
 
 
+def linear_attn_fwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, o, stream=None):
+    """kf_linear_attn_fwd: o = scale ((q k^T) . A) v with A[t, s] = exp(G_t - G_s) for s <= t, G the prefix sum of g (f32, <= 0)."""
+    check(lib().kf_linear_attn_fwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, o, stream))
+
+
+def linear_attn_bwd_workspace_bytes(dtype, B, H, S, Dk, Dv) -> int:
+    need = C.c_size_t(0)
+    check(lib().kf_linear_attn_bwd_workspace_bytes(dtype, B, H, S, Dk, Dv, C.byref(need)))
+    return need.value
+
+
+def linear_attn_bwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, d_o, dq, dk, dv, dg, workspace=None, workspace_bytes=None, stream=None):
+    """kf_linear_attn_bwd: dq, dk, dv and the exact dg. Without a workspace, one of the queried size is made here and returned (keep it
+    until the stream is synchronised)."""
+    ws = None
+    if workspace is None:
+        workspace_bytes = linear_attn_bwd_workspace_bytes(dtype, B, H, S, Dk, Dv)
+        ws = DevBuf(workspace_bytes)
+        workspace = ws.ptr
+    check(lib().kf_linear_attn_bwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, d_o, dq, dk, dv, dg, workspace, workspace_bytes, stream))
+    return ws
+
+
 def index_put(desc: IterDesc, sizes, strides_bytes, stream=None):
     n = len(sizes)
     a = (C.c_int64 * n)(*sizes)
