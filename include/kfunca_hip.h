@@ -1160,6 +1160,29 @@ int kf_linear_attn_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t 
 int kf_linear_attn_bwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
                        const void *v, const float *g, const void *d_o, void *dq, void *dk, void *dv, float *dg, void *workspace,
                        size_t workspace_bytes, void *stream);
+/* The same with a carried state (h0, hT, d_hT, d_h0: dense [B, H, Dk, Dv] float, 16-byte aligned, each may be NULL; with all of them NULL
+ * the calls are the two above, bit for bit). With D_t = exp(G_t), kd_s = exp(G_T - G_s):
+ *   o_t = scale q_t (sum_{s <= t} A[t, s] k_s v_s^T + D_t h0),   hT = D_T h0 + sum_s kd_s k_s v_s^T
+ *   dq_t += scale D_t (h0 dO_t),  dk_s += kd_s (d_hT v_s),  dv_s += kd_s (d_hT^T k_s),  d_h0 = scale sum_t D_t q_t dO_t^T + D_T d_hT,
+ *   dg_r = sum_{t >= r} (q_t . dq_t - k_t . dk_t) + <d_hT, hT>
+ * so a sequence can be processed in segments chained through hT -> h0 (forward) and d_h0 -> d_hT (backward) with exact gradients
+ * across the cut. d_h0 needs h0 (KF_ERR_INVALID without). hT may alias h0 and d_h0 may alias d_hT: a workgroup reads its part before
+ * it writes it. The workspace (kf_linear_attn_state_bwd_workspace_bytes) holds B H floats more than the stateless one. Same checks
+ * and contract; profile labels linear_attn_state_fwd_{bf16,f16}, linear_attn_state_bwd_{bf16,f16}. */
+int kf_linear_attn_state_fwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                             const void *v, const float *g, const float *h0 /* or NULL */, void *o, float *hT /* or NULL */, void *stream);
+int kf_linear_attn_state_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, size_t *bytes);
+int kf_linear_attn_state_bwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                             const void *v, const float *g, const float *h0 /* or NULL */, const void *d_o, const float *d_hT /* or NULL */,
+                             void *dq, void *dk, void *dv, float *dg, float *d_h0 /* or NULL; needs h0 */, void *workspace,
+                             size_t workspace_bytes, void *stream);
+/* The recurrence token by token, for generation after a prefill that returned hT: for t = 0 .. T - 1
+ *   state <- exp(g_t) state + k_t v_t^T,  o_t = scale q_t state,
+ * q, k, v, o [B, H, T, D], g [B, H, T], state [B, H, Dk, Dv] float updated in place (read once and written once whatever T is; all in
+ * f32, o rounded once). Any T >= 1; meant for one to a handful of tokens - long T belongs to the chunk kernels. Same checks and
+ * contract; profile labels linear_attn_step_{bf16,f16}. */
+int kf_linear_attn_step(int dtype, int64_t B, int64_t H, int64_t T, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                        const void *v, const float *g, float *state, void *o, void *stream);
 
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128

@@ -340,12 +340,25 @@ PYBIND11_MODULE(_C, m) {
             return py::make_tuple(m, v, s, ms.defined() ? py::cast(ms) : py::none());
         }, py::arg("param"))
         .def("__len__", &gpu::AdamW::size);
-    m.def("linear_attention", [](const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &g, py::object scale) {
-        return gpu::linear_attention(q, k, v, g, scale.is_none() ? std::nullopt : std::optional<float>(scale.cast<float>()));
-    }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("g"), py::arg("scale") = py::none(),
-          "linear_attention(q, k, v, g, scale=None): S_t = exp(g_t) S_{t-1} + k_t v_t^T, o_t = scale q_t S_t in 64-step chunks on the matrix cores. "
-          "q, k, v [B, H, S, D] half or bfloat16 with D in {64, 128}; g [B, H, S] float, <= 0; scale defaults to D ** -0.5. Differentiable in "
-          "q, k, v and g (the exact gradient of g); forward and backward can be captured into a graph.");
+    m.def("linear_attention", [](const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &g, py::object scale, py::object initial_state,
+                                 bool return_state) -> py::object {
+        auto r = gpu::linear_attention(q, k, v, g, scale.is_none() ? std::nullopt : std::optional<float>(scale.cast<float>()),
+                                       initial_state.is_none() ? Tensor() : initial_state.cast<Tensor>(), return_state);
+        return return_state ? py::object(py::make_tuple(r.first, r.second)) : py::cast(r.first);
+    }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("g"), py::arg("scale") = py::none(), py::arg("initial_state") = py::none(),
+          py::arg("return_state") = false,
+          "linear_attention(q, k, v, g, scale=None, initial_state=None, return_state=False): S_t = exp(g_t) S_{t-1} + k_t v_t^T, o_t = scale q_t S_t "
+          "in 64-step chunks on the matrix cores. q, k, v [B, H, S, D] half or bfloat16 with D in {64, 128}; g [B, H, S] float, <= 0; scale "
+          "defaults to D ** -0.5. initial_state is S_0, float [B, H, D, D] (None: zero); with return_state the result is (o, S_T). Segments "
+          "chained through the state give the results and gradients of the whole sequence. Differentiable in q, k, v, g (the exact "
+          "gradient of g) and initial_state. A prefill with return_state=True followed by linear_attention_step calls is the inference path.");
+    m.def("linear_attention_step", [](const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &g, Tensor &state, py::object scale) {
+        return gpu::linear_attention_step(q, k, v, g, state, scale.is_none() ? std::nullopt : std::optional<float>(scale.cast<float>()));
+    }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("g"), py::arg("state"), py::arg("scale") = py::none(),
+          "linear_attention_step(q, k, v, g, state, scale=None): T steps of the recurrence of linear_attention, token by token: q, k, v "
+          "[B, H, T, D], g [B, H, T] -> o [B, H, T, D]; state, float [B, H, D, D], is updated in place. The generation half of the inference "
+          "path: state comes from linear_attention(..., return_state=True) over the prompt, then one call per new token (or per handful of "
+          "speculative tokens). Not differentiable; can be captured into a graph.");
     m.def("gemm_sym", [](const Tensor &x, float alpha, py::object d, float beta, float gamma) {
         return gpu::gemm_sym(x, alpha, d.is_none() ? Tensor() : d.cast<Tensor>(), beta, gamma);
     }, py::arg("x"), py::arg("alpha") = 1.0f, py::arg("d") = py::none(), py::arg("beta") = 0.0f, py::arg("gamma") = 0.0f);

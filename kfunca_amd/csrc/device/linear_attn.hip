@@ -14,6 +14,12 @@
 // with an XOR swizzle on the 16-byte chunk; a fragment whose contraction index runs along a tile's columns is one ds_read_b128, one
 // whose contraction index runs along the rows is two ds_read_b64_tr_b16 (l_frag_row / l_frag_col). No atomics, no workspace for the
 // forward, nothing read back: results are reproducible to the bit and the calls can be captured.
+//
+// The three walks also exist as state variants (template flag ST; kf_linear_attn_state_fwd / _bwd): the carried state starts from h0
+// (the carried dS from d_hT) instead of zero, the walk's last carry step is done too and the accumulators leave as hT (d_h0), and the
+// ascending walk forms <d_hT, hT>, the constant every dg_r gains when a gradient arrives through the final state. The state moves in
+// and out at the two ends of a walk, through tiles that are free there. kf_linear_attn_step is the token-by-token recurrence, a
+// bandwidth kernel without matrix instructions (lin_step_kernel).
 #include <math.h>
 
 #include "common.h"
@@ -36,6 +42,8 @@ struct LinArgs {
     const float *g;
     char *o, *dq, *dk, *dv;
     float *wa, *wb, *dg;
+    const float *h0, *d_hT; // [B, H, Dk, Dv] f32 or null (state variants only)
+    float *hT, *d_h0, *wc;  // wc: <d_hT, hT> per (b, h), null without d_hT; the step kernel's state is hT and its T is S
     int64_t S;
     float scale;
 };
@@ -185,12 +193,35 @@ __device__ __forceinline__ float l_half_sum(float x) {
     return x;
 }
 
+// state variants: the f32 state [D][ld] in memory (null: zeros) -> the accumulator blocks (db[i], dvb), each lane its own elements
+template <int N> __device__ __forceinline__ void l_state_in(l_f32x16 (&st)[N], const int (&db)[N], int dvb, const float *src, int ld) {
+    const int lane = threadIdx.x & 63, xl = lane & 31, hl = lane >> 5;
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) st[i][e] = src ? src[(32 * db[i] + l_row(e, hl)) * ld + 32 * dvb + xl] : 0.f;
+}
+// the accumulator blocks -> an LDS image [rows][W] f32 over tiles nobody reads any more -> memory, 16 bytes a lane along whole rows
+template <int N, int W> __device__ __forceinline__ void l_state_out(const l_f32x16 (&st)[N], const int (&db)[N], int dvb, float *img, int rows, float *dst, int ld) {
+    const int lane = threadIdx.x & 63, xl = lane & 31, hl = lane >> 5;
+    __syncthreads(); // the last reads of the tiles under the image
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) img[(32 * db[i] + l_row(e, hl)) * W + 32 * dvb + xl] = st[i][e];
+    __syncthreads();
+    for (int at = threadIdx.x; at < rows * (W / 4); at += 256) {
+        const int r = at / (W / 4), c4 = at % (W / 4);
+        *(float4 *)(dst + (int64_t)r * ld + 4 * c4) = *(const float4 *)(img + r * W + 4 * c4);
+    }
+}
+
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------
 // Wave w: the P block and the O block of query rows 32 (w >> 1) (key / Dv columns 32 (w & 1)), and the state blocks of Dv columns
 // 32 (w & 1), Dk rows 32 ((w >> 1) + 2 i). LDS: Q[2] K[2] V-slice[2] | P | state copy [64 dv][Dk] | G.
 template <int D> constexpr int l_fwd_lds() { return 2 * (2 * L_C * D * 2 + L_PT) + L_PT + 64 * D * 2 + L_G; }
 
-template <bool BF, int D>
+template <bool BF, int D, bool ST>
 __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int RB = D * 2, QT = L_C * RB, NS = D / 64, NST = D / 64;
@@ -219,6 +250,11 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) st[i][e] = 0.f;
     }
+    if constexpr (ST) { // this slice of h0 and its 16-bit copy for the first chunk's Q S_prev; the chunk's first barrier publishes it
+        l_state_in<NST>(st, db, cbk, a.h0 ? a.h0 + bh * D * D + slice * 64 : nullptr, D);
+#pragma unroll
+        for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], cbk);
+    }
     stage(0);
     for (int c = 0; c < nc; ++c) {
         const int p = c & 1, valid = (int)(S - (int64_t)c * L_C < L_C ? S - (int64_t)c * L_C : L_C);
@@ -238,7 +274,7 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
 #pragma unroll
         for (int ks = 0; ks < D / 16; ++ks) acc = l_mma<BF>(l_frag_row<RB>(tQ, 32 * tb, 16 * ks), l_frag_row<RB>(tK, 32 * cbk, 16 * ks), acc);
         l_mask_store<BF>(acc, smem + oP, tb, cbk, gt, gs, a.scale);
-        if (c > 0) { // the carried state, through its 16-bit copy; the row scaling stays in f32
+        if (ST || c > 0) { // the carried state, through its 16-bit copy; the row scaling stays in f32
 #pragma unroll
             for (int ks = 0; ks < D / 16; ++ks) out = l_mma<BF>(l_frag_row<RB>(tQ, 32 * tb, 16 * ks), l_frag_row<RB>(tS, 32 * cbk, 16 * ks), out);
 #pragma unroll
@@ -252,12 +288,16 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
             const int t = 32 * tb + l_row(e, hl);
             if (t < valid) *(uint16_t *)(o + ((int64_t)c * L_C + t) * RB + (slice * 64 + 32 * cbk + xl) * 2) = (uint16_t)l_cvt16<BF>(out[e]);
         }
-        if (c + 1 < nc) {
+        if (c + 1 < nc || (ST && a.hT)) {
             l_state_update<BF, RB, 128, NST>(st, tK, tV, db, cbk, dec, kdv);
+            if (c + 1 < nc) {
 #pragma unroll
-            for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], cbk);
+                for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], cbk);
+            }
         }
     }
+    // hT: the image [Dk][64] f32 is exactly the two Q tiles, last read before the last chunk's barrier, with no DMA under way
+    if (ST && a.hT) l_state_out<NST, 64>(st, db, cbk, (float *)(smem + oQ), D, a.hT + bh * D * D + slice * 64, D);
 }
 
 // ---- backward, ascending: dQ and a_t ---------------------------------------------------------------------------------------------------
@@ -266,7 +306,7 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(const LinArgs a) {
 // LDS: K[2] V[2] dO[2] | M | state copy [Dv][Dk] | G | a_t halves.
 template <int D> constexpr int l_asc_lds() { return 6 * L_C * D * 2 + L_PT + D * D * 2 + L_G + 2 * L_C * 4; }
 
-template <bool BF, int D>
+template <bool BF, int D, bool ST>
 __global__ __launch_bounds__(256) void lin_bwd_asc_kernel(const LinArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int RB = D * 2, QT = L_C * RB, NQ = D / 64, NST = D == 128 ? 4 : 1;
@@ -295,6 +335,11 @@ __global__ __launch_bounds__(256) void lin_bwd_asc_kernel(const LinArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) st[i][e] = 0.f;
     }
+    if constexpr (ST) {
+        l_state_in<NST>(st, db, sdv, a.h0 ? a.h0 + bh * D * D : nullptr, D);
+#pragma unroll
+        for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], sdv);
+    }
 #pragma unroll
     for (int i = 0; i < NQ; ++i) qb[i] = cbk * NQ + i;
     stage(0);
@@ -320,7 +365,7 @@ __global__ __launch_bounds__(256) void lin_bwd_asc_kernel(const LinArgs a) {
 #pragma unroll
         for (int ks = 0; ks < D / 16; ++ks) acc = l_mma<BF>(l_frag_row<RB>(tO, 32 * tb, 16 * ks), l_frag_row<RB>(tV, 32 * cbk, 16 * ks), acc);
         l_mask_store<BF>(acc, smem + oM, tb, cbk, gt, gs, a.scale);
-        if (c > 0) { // dO S_prev^T: k runs over Dv, the rows of the state copy
+        if (ST || c > 0) { // dO S_prev^T: k runs over Dv, the rows of the state copy
 #pragma unroll
             for (int ks = 0; ks < D / 16; ++ks) {
                 const l_u32x4 fa = l_frag_row<RB>(tO, 32 * tb, 16 * ks);
@@ -360,11 +405,27 @@ __global__ __launch_bounds__(256) void lin_bwd_asc_kernel(const LinArgs a) {
         }
         __syncthreads();
         if ((int)threadIdx.x < valid) a.wa[bh * S + (int64_t)c * L_C + threadIdx.x] = asum[threadIdx.x] + asum[L_C + threadIdx.x];
-        if (c + 1 < nc) {
+        if (c + 1 < nc || (ST && a.d_hT)) {
             l_state_update<BF, RB, RB, NST>(st, tK, tV, db, sdv, dec, kdv);
+            if (c + 1 < nc) {
 #pragma unroll
-            for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], sdv);
+                for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], sdv);
+            }
         }
+    }
+    if (ST && a.d_hT) { // <d_hT, hT>: each lane over its own elements, the wave by shuffles, the four waves in order
+        const float *dh = a.d_hT + bh * D * D;
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NST; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) s += st[i][e] * dh[(32 * db[i] + l_row(e, hl)) * D + 32 * sdv + xl];
+        s = l_half_sum(s);
+        s += __shfl_xor(s, 32);
+        __syncthreads(); // the a_t halves are read
+        if (lane == 0) asum[wid] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) a.wc[bh] = ((asum[0] + asum[1]) + asum[2]) + asum[3];
     }
 }
 
@@ -376,7 +437,7 @@ __global__ __launch_bounds__(256) void lin_bwd_asc_kernel(const LinArgs a) {
 template <int D> constexpr int l_desc_nbuf() { return D == 64 ? 2 : 1; }
 template <int D> constexpr int l_desc_lds() { return l_desc_nbuf<D>() * 4 * L_C * D * 2 + 2 * L_PT + D * D * 2 + L_G + 2 * L_C * 4; }
 
-template <bool BF, int D>
+template <bool BF, int D, bool ST>
 __global__ __launch_bounds__(256) void lin_bwd_desc_kernel(const LinArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int RB = D * 2, QT = L_C * RB, NQ = D / 64, NST = D == 128 ? 4 : 1, NBUF = l_desc_nbuf<D>();
@@ -407,6 +468,11 @@ __global__ __launch_bounds__(256) void lin_bwd_desc_kernel(const LinArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) st[i][e] = 0.f;
     }
+    if constexpr (ST) { // the carried dS starts from d_hT
+        l_state_in<NST>(st, db, sdv, a.d_hT ? a.d_hT + bh * D * D : nullptr, D);
+#pragma unroll
+        for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], sdv);
+    }
 #pragma unroll
     for (int i = 0; i < NQ; ++i) cb[i] = cbk * NQ + i;
     stage(nc - 1, 0);
@@ -434,7 +500,7 @@ __global__ __launch_bounds__(256) void lin_bwd_desc_kernel(const LinArgs a) {
         }
         l_mask_store<BF>(accp, smem + oP, tb, cbk, gt, gs, a.scale);
         l_mask_store<BF>(accm, smem + oM, tb, cbk, gt, gs, a.scale);
-        if (it > 0) { // V dS^T (k over Dv, the copy's rows) and K dS (k over Dk, the copy's columns)
+        if (ST || it > 0) { // V dS^T (k over Dv, the copy's rows) and K dS (k over Dk, the copy's columns)
 #pragma unroll
             for (int ks = 0; ks < D / 16; ++ks) {
                 const l_u32x4 fv = l_frag_row<RB>(tV, 32 * tb, 16 * ks), fk = l_frag_row<RB>(tK, 32 * tb, 16 * ks);
@@ -486,25 +552,29 @@ __global__ __launch_bounds__(256) void lin_bwd_desc_kernel(const LinArgs a) {
         }
         __syncthreads();
         if ((int)threadIdx.x < valid) a.wb[bh * S + (int64_t)c * L_C + threadIdx.x] = bsum[threadIdx.x] + bsum[L_C + threadIdx.x];
-        if (c > 0) {
+        if (c > 0 || (ST && a.d_h0)) {
             float qdv[4][8];
             l_kvec(G + 128, qdv);
             l_state_update<BF, RB, RB, NST>(st, tQ, tO, db, sdv, dec, qdv);
+            if (c > 0) {
 #pragma unroll
-            for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], sdv);
-            if (NBUF == 1) {
-                __syncthreads(); // the last read of this chunk's tiles
-                stage(c - 1, 0);
+                for (int i = 0; i < NST; ++i) l_state_store<BF, RB>(st[i], smem + oS, db[i], sdv);
+                if (NBUF == 1) {
+                    __syncthreads(); // the last read of this chunk's tiles
+                    stage(c - 1, 0);
+                }
             }
         }
     }
+    // d_h0 = the carry step past chunk 0; its image [Dk][Dv] f32 lies over the chunk tiles (64 KiB at D = 128: all four of them)
+    if (ST && a.d_h0) l_state_out<NST, D>(st, db, sdv, (float *)smem, D, a.d_h0 + bh * D * D, D);
 }
 
-// dg_r = sum_{t >= r} (a_t - b_t): one wave per (b, h) walks the sequence downwards in blocks of 64, a suffix scan inside the block
+// dg_r = sum_{t >= r} (a_t - b_t) (+ <d_hT, hT>, the carry's start, when a gradient came through the final state): one wave per (b, h) walks the sequence downwards in blocks of 64, a suffix scan inside the block
 __global__ __launch_bounds__(64) void lin_dg_kernel(const LinArgs a) {
     const int64_t S = a.S, base = (int64_t)blockIdx.x * S;
     const int lane = threadIdx.x;
-    float carry = 0.f;
+    float carry = a.wc ? a.wc[blockIdx.x] : 0.f;
     for (int64_t blk = (S + 63) / 64 - 1; blk >= 0; --blk) {
         const int64_t t = blk * 64 + lane;
         float x = t < S ? a.wa[base + t] - a.wb[base + t] : 0.f;
@@ -518,7 +588,79 @@ __global__ __launch_bounds__(64) void lin_dg_kernel(const LinArgs a) {
     }
 }
 
-int lin_check(const char *who, int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale) {
+// ---- the recurrence, token by token ----------------------------------------------------------------------------------------------------
+// S <- exp(g_t) S + k_t v_t^T, o_t = scale q_t S for t = 0 .. T - 1 on a state in memory: at T = 1 the call moves 2 Dk Dv 4 bytes a head
+// beside a few hundred bytes of operands, so the design is the state's traffic. One workgroup per (b, h, 64 state columns): columns
+// need no reduction across workgroups. Lane (rg = tid >> 4, cp = tid & 15) owns rows rg Dk / 16 .. of the 16-byte pack of columns
+// 4 cp ..: Dk / 16 float4 registers (32 floats at D = 128), loaded once, all loads in flight together, kept across the T steps and
+// stored once. The operands of up to L_TB steps are widened to f32 in LDS (with exp(g_t)) ahead of the steps; a step is then two
+// broadcast LDS reads a row, a multiply and a fused multiply-add a state element, the lane's partial o over its rows, and the sum over
+// the 16 row groups through LDS in the order 0 .. 15 (two parities: one barrier a step), scale, one rounding to 16 bits.
+constexpr int L_TB = 16;
+template <int D> constexpr int l_step_lds() { return (L_TB * (2 * D + 64) + L_TB + 2 * 16 * 64) * 4; }
+
+template <bool BF, int D>
+__global__ __launch_bounds__(256) void lin_step_kernel(const LinArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int R = D / 16, NS = D / 64;
+    float *sq = (float *)smem, *sk = sq + L_TB * D, *sv = sk + L_TB * D, *se = sv + L_TB * 64, *red = se + L_TB;
+    const int tid = threadIdx.x, cp = tid & 15, rg = tid >> 4;
+    const int64_t bh = blockIdx.x / NS, T = a.S;
+    const int slice = blockIdx.x % NS;
+    float *sp = a.hT + bh * D * D + rg * R * D + slice * 64 + 4 * cp;
+    float4 s[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) s[j] = *(const float4 *)(sp + j * D);
+    const uint16_t *q = (const uint16_t *)a.q + bh * T * D, *k = (const uint16_t *)a.k + bh * T * D, *v = (const uint16_t *)a.v + bh * T * D + slice * 64;
+    uint16_t *o = (uint16_t *)a.o + bh * T * D + slice * 64;
+    const float *g = a.g + bh * T;
+    for (int64_t t0 = 0; t0 < T; t0 += L_TB) {
+        const int nb = (int)(T - t0 < L_TB ? T - t0 : L_TB);
+        __syncthreads(); // the steps before have read their operands
+        for (int i = tid; i < nb * D; i += 256) {
+            sq[i] = l_f32<BF>(q[t0 * D + i]);
+            sk[i] = l_f32<BF>(k[t0 * D + i]);
+        }
+        for (int i = tid; i < nb * 64; i += 256) sv[i] = l_f32<BF>(v[(t0 + (i >> 6)) * D + (i & 63)]);
+        if (tid < nb) se[tid] = expf(g[t0 + tid]);
+        __syncthreads();
+        for (int t = 0; t < nb; ++t) {
+            const float e = se[t];
+            const float4 vv = *(const float4 *)(sv + t * 64 + 4 * cp);
+            float kk[R], qq[R];
+#pragma unroll
+            for (int j = 0; j < R; j += 4) {
+                *(float4 *)(kk + j) = *(const float4 *)(sk + t * D + rg * R + j);
+                *(float4 *)(qq + j) = *(const float4 *)(sq + t * D + rg * R + j);
+            }
+            float4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                s[j].x = fmaf(kk[j], vv.x, e * s[j].x);
+                s[j].y = fmaf(kk[j], vv.y, e * s[j].y);
+                s[j].z = fmaf(kk[j], vv.z, e * s[j].z);
+                s[j].w = fmaf(kk[j], vv.w, e * s[j].w);
+                acc.x = fmaf(qq[j], s[j].x, acc.x);
+                acc.y = fmaf(qq[j], s[j].y, acc.y);
+                acc.z = fmaf(qq[j], s[j].z, acc.z);
+                acc.w = fmaf(qq[j], s[j].w, acc.w);
+            }
+            float *rp = red + (t & 1) * (16 * 64);
+            *(float4 *)(rp + rg * 64 + 4 * cp) = acc;
+            __syncthreads();
+            if (tid < 64) {
+                float x = rp[tid];
+#pragma unroll
+                for (int r = 1; r < 16; ++r) x += rp[r * 64 + tid];
+                o[(t0 + t) * D + tid] = (uint16_t)l_cvt16<BF>(x * a.scale);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) *(float4 *)(sp + j * D) = s[j];
+}
+
+int lin_check(const char *who,int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale) {
     KF_REQUIRE(B > 0 && H > 0 && S > 0 && Dk > 0 && Dv > 0, KF_ERR_INVALID, "%s: bad extents B %lld H %lld S %lld Dk %lld Dv %lld", who, (long long)B,
                (long long)H, (long long)S, (long long)Dk, (long long)Dv);
     KF_REQUIRE(isfinite(scale) && scale != 0.f, KF_ERR_INVALID, "%s: scale must be finite and not zero", who);
@@ -529,7 +671,63 @@ int lin_check(const char *who, int dtype, int64_t B, int64_t H, int64_t S, int64
     return KF_OK;
 }
 bool al16(const void *p) { return p && ((uintptr_t)p & 15u) == 0; }
-size_t lin_ws_bytes(int64_t B, int64_t H, int64_t S) { return (size_t)((2 * B * H * S * 4 + 15) / 16 * 16); }
+bool al16_or_null(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+// a_t and b_t; with a state, one more float per (b, h) behind them
+size_t lin_ws_bytes(int64_t B, int64_t H, int64_t S, bool state) { return (size_t)(((2 * B * H * S + (state ? B * H : 0)) * 4 + 15) / 16 * 16); }
+
+// the stateless entries are these with null states: the kernels are then the instantiations without the state flag
+int lin_fwd(const char *who, const char *label, int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q,
+            const void *k, const void *v, const float *g, const float *h0, void *o, float *hT, void *stream) {
+    KF_REQUIRE(q && k && v && g && o, KF_ERR_INVALID, "%s: null operand", who);
+    const int rc = lin_check(who, dtype, B, H, S, Dk, Dv, scale);
+    if (rc != KF_OK) return rc;
+    KF_REQUIRE(al16(q) && al16(k) && al16(v) && al16(g) && al16(o), KF_ERR_INVALID, "%s: an operand is not aligned to 16 bytes", who);
+    KF_REQUIRE(al16_or_null(h0) && al16_or_null(hT), KF_ERR_INVALID, "%s: a state is not aligned to 16 bytes", who);
+    hipStream_t st = as_stream(stream);
+    LinArgs a{};
+    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.g = g; a.o = (char *)o;
+    a.h0 = h0; a.hT = hT;
+    a.S = S; a.scale = scale;
+    const bool bf = dtype == KF_BF16, big = Dk == 128;
+    const dim3 grid((unsigned)(B * H * (Dv / 64)));
+    KF_PROF(label, st);
+    return with_flags([&](auto BF, auto BIG, auto ST) {
+        constexpr int D = decltype(BIG)::value ? 128 : 64;
+        return launch(lin_fwd_kernel<decltype(BF)::value, D, decltype(ST)::value>, grid, dim3(256), (size_t)l_fwd_lds<D>(), st, a);
+    }, bf, big, h0 || hT);
+}
+
+int lin_bwd(const char *who, const char *label, bool state_entry, int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale,
+            const void *q, const void *k, const void *v, const float *g, const float *h0, const void *d_o, const float *d_hT, void *dq, void *dk,
+            void *dv, float *dg, float *d_h0, void *workspace, size_t workspace_bytes, void *stream) {
+    KF_REQUIRE(q && k && v && g && d_o && dq && dk && dv && dg, KF_ERR_INVALID, "%s: null operand", who);
+    const int rc = lin_check(who, dtype, B, H, S, Dk, Dv, scale);
+    if (rc != KF_OK) return rc;
+    KF_REQUIRE(al16(q) && al16(k) && al16(v) && al16(g) && al16(d_o) && al16(dq) && al16(dk) && al16(dv) && al16(dg), KF_ERR_INVALID,
+               "%s: an operand is not aligned to 16 bytes", who);
+    KF_REQUIRE(al16_or_null(h0) && al16_or_null(d_hT) && al16_or_null(d_h0), KF_ERR_INVALID, "%s: a state is not aligned to 16 bytes", who);
+    KF_REQUIRE(!d_h0 || h0, KF_ERR_INVALID, "%s: d_h0 without h0", who);
+    const size_t need = lin_ws_bytes(B, H, S, state_entry);
+    KF_REQUIRE(workspace && workspace_bytes >= need, KF_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
+               workspace ? workspace_bytes : (size_t)0, need);
+    KF_REQUIRE(al16(workspace), KF_ERR_INVALID, "%s: workspace is not aligned to 16 bytes", who);
+    hipStream_t st = as_stream(stream);
+    LinArgs a{};
+    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.g = g; a.d_o = (const char *)d_o;
+    a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv; a.dg = dg;
+    a.wa = (float *)workspace; a.wb = a.wa + B * H * S;
+    a.h0 = h0; a.d_hT = d_hT; a.d_h0 = d_h0; a.wc = d_hT ? a.wb + B * H * S : nullptr;
+    a.S = S; a.scale = scale;
+    const bool bf = dtype == KF_BF16, big = Dk == 128;
+    const dim3 grid((unsigned)(B * H));
+    KF_PROF(label, st);
+    const int r2 = with_flags([&](auto BF, auto BIG, auto ST) {
+        constexpr int D = decltype(BIG)::value ? 128 : 64;
+        const int r = launch(lin_bwd_asc_kernel<decltype(BF)::value, D, decltype(ST)::value>, grid, dim3(256), (size_t)l_asc_lds<D>(), st, a);
+        return r != KF_OK ? r : launch(lin_bwd_desc_kernel<decltype(BF)::value, D, decltype(ST)::value>, grid, dim3(256), (size_t)l_desc_lds<D>(), st, a);
+    }, bf, big, h0 || d_hT);
+    return r2 != KF_OK ? r2 : launch(lin_dg_kernel, grid, dim3(64), 0, st, a);
+}
 
 } // namespace
 } // namespace kf
@@ -538,58 +736,63 @@ using namespace kf;
 
 extern "C" int kf_linear_attn_fwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
                                   const void *v, const float *g, void *o, void *stream) {
-    const char *who = "kf_linear_attn_fwd";
-    KF_REQUIRE(q && k && v && g && o, KF_ERR_INVALID, "%s: null operand", who);
-    const int rc = lin_check(who, dtype, B, H, S, Dk, Dv, scale);
+    return lin_fwd("kf_linear_attn_fwd", dtype == KF_BF16 ? "linear_attn_fwd_bf16" : "linear_attn_fwd_f16", dtype, B, H, S, Dk, Dv, scale, q, k, v, g,
+                   nullptr, o, nullptr, stream);
+}
+
+extern "C" int kf_linear_attn_state_fwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                                        const void *v, const float *g, const float *h0, void *o, float *hT, void *stream) {
+    return lin_fwd("kf_linear_attn_state_fwd", dtype == KF_BF16 ? "linear_attn_state_fwd_bf16" : "linear_attn_state_fwd_f16", dtype, B, H, S, Dk, Dv,
+                   scale, q, k, v, g, h0, o, hT, stream);
+}
+
+extern "C" int kf_linear_attn_step(int dtype, int64_t B, int64_t H, int64_t T, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                                   const void *v, const float *g, float *state, void *o, void *stream) {
+    const char *who = "kf_linear_attn_step";
+    KF_REQUIRE(q && k && v && g && state && o, KF_ERR_INVALID, "%s: null operand", who);
+    const int rc = lin_check(who, dtype, B, H, T, Dk, Dv, scale);
     if (rc != KF_OK) return rc;
-    KF_REQUIRE(al16(q) && al16(k) && al16(v) && al16(g) && al16(o), KF_ERR_INVALID, "%s: an operand is not aligned to 16 bytes", who);
+    KF_REQUIRE(al16(q) && al16(k) && al16(v) && al16(g) && al16(state) && al16(o), KF_ERR_INVALID, "%s: an operand is not aligned to 16 bytes", who);
     hipStream_t st = as_stream(stream);
     LinArgs a{};
     a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.g = g; a.o = (char *)o;
-    a.S = S; a.scale = scale;
+    a.hT = state;
+    a.S = T; a.scale = scale;
     const bool bf = dtype == KF_BF16, big = Dk == 128;
     const dim3 grid((unsigned)(B * H * (Dv / 64)));
-    KF_PROF(bf ? "linear_attn_fwd_bf16" : "linear_attn_fwd_f16", st);
+    KF_PROF(bf ? "linear_attn_step_bf16" : "linear_attn_step_f16", st);
     return with_flags([&](auto BF, auto BIG) {
         constexpr int D = decltype(BIG)::value ? 128 : 64;
-        return launch(lin_fwd_kernel<decltype(BF)::value, D>, grid, dim3(256), (size_t)l_fwd_lds<D>(), st, a);
+        return launch(lin_step_kernel<decltype(BF)::value, D>, grid, dim3(256), (size_t)l_step_lds<D>(), st, a);
     }, bf, big);
 }
 
-extern "C" int kf_linear_attn_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, size_t *bytes) {
-    const char *who = "kf_linear_attn_bwd_workspace_bytes";
+static int lin_ws_entry(const char *who, bool state, int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, size_t *bytes) {
     KF_REQUIRE(bytes, KF_ERR_INVALID, "%s: null bytes", who);
     const int rc = lin_check(who, dtype, B, H, S, Dk, Dv, 1.f);
     if (rc != KF_OK) return rc;
-    *bytes = lin_ws_bytes(B, H, S);
+    *bytes = lin_ws_bytes(B, H, S, state);
     return KF_OK;
+}
+
+extern "C" int kf_linear_attn_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, size_t *bytes) {
+    return lin_ws_entry("kf_linear_attn_bwd_workspace_bytes", false, dtype, B, H, S, Dk, Dv, bytes);
+}
+
+extern "C" int kf_linear_attn_state_bwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, size_t *bytes) {
+    return lin_ws_entry("kf_linear_attn_state_bwd_workspace_bytes", true, dtype, B, H, S, Dk, Dv, bytes);
 }
 
 extern "C" int kf_linear_attn_bwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
                                   const void *v, const float *g, const void *d_o, void *dq, void *dk, void *dv, float *dg, void *workspace,
                                   size_t workspace_bytes, void *stream) {
-    const char *who = "kf_linear_attn_bwd";
-    KF_REQUIRE(q && k && v && g && d_o && dq && dk && dv && dg, KF_ERR_INVALID, "%s: null operand", who);
-    const int rc = lin_check(who, dtype, B, H, S, Dk, Dv, scale);
-    if (rc != KF_OK) return rc;
-    KF_REQUIRE(al16(q) && al16(k) && al16(v) && al16(g) && al16(d_o) && al16(dq) && al16(dk) && al16(dv) && al16(dg), KF_ERR_INVALID,
-               "%s: an operand is not aligned to 16 bytes", who);
-    KF_REQUIRE(workspace && workspace_bytes >= lin_ws_bytes(B, H, S), KF_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
-               workspace ? workspace_bytes : (size_t)0, lin_ws_bytes(B, H, S));
-    KF_REQUIRE(al16(workspace), KF_ERR_INVALID, "%s: workspace is not aligned to 16 bytes", who);
-    hipStream_t st = as_stream(stream);
-    LinArgs a{};
-    a.q = (const char *)q; a.k = (const char *)k; a.v = (const char *)v; a.g = g; a.d_o = (const char *)d_o;
-    a.dq = (char *)dq; a.dk = (char *)dk; a.dv = (char *)dv; a.dg = dg;
-    a.wa = (float *)workspace; a.wb = a.wa + B * H * S;
-    a.S = S; a.scale = scale;
-    const bool bf = dtype == KF_BF16, big = Dk == 128;
-    const dim3 grid((unsigned)(B * H));
-    KF_PROF(bf ? "linear_attn_bwd_bf16" : "linear_attn_bwd_f16", st);
-    const int r2 = with_flags([&](auto BF, auto BIG) {
-        constexpr int D = decltype(BIG)::value ? 128 : 64;
-        const int r = launch(lin_bwd_asc_kernel<decltype(BF)::value, D>, grid, dim3(256), (size_t)l_asc_lds<D>(), st, a);
-        return r != KF_OK ? r : launch(lin_bwd_desc_kernel<decltype(BF)::value, D>, grid, dim3(256), (size_t)l_desc_lds<D>(), st, a);
-    }, bf, big);
-    return r2 != KF_OK ? r2 : launch(lin_dg_kernel, grid, dim3(64), 0, st, a);
+    return lin_bwd("kf_linear_attn_bwd", dtype == KF_BF16 ? "linear_attn_bwd_bf16" : "linear_attn_bwd_f16", false, dtype, B, H, S, Dk, Dv, scale, q, k,
+                   v, g, nullptr, d_o, nullptr, dq, dk, dv, dg, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int kf_linear_attn_state_bwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                                        const void *v, const float *g, const float *h0, const void *d_o, const float *d_hT, void *dq, void *dk,
+                                        void *dv, float *dg, float *d_h0, void *workspace, size_t workspace_bytes, void *stream) {
+    return lin_bwd("kf_linear_attn_state_bwd", dtype == KF_BF16 ? "linear_attn_state_bwd_bf16" : "linear_attn_state_bwd_f16", true, dtype, B, H, S, Dk,
+                   Dv, scale, q, k, v, g, h0, d_o, d_hT, dq, dk, dv, dg, d_h0, workspace, workspace_bytes, stream);
 }

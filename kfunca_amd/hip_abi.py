@@ -527,6 +527,36 @@ def linear_attn_bwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, d_o, dq, dk, dv, 
     return ws
 
 
+def linear_attn_state_fwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, h0, o, hT, stream=None):
+    """kf_linear_attn_state_fwd: linear_attn_fwd from the state h0 (f32 [B, H, Dk, Dv] or None: zero), the final state to hT (or None)."""
+    check(lib().kf_linear_attn_state_fwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, h0, o, hT, stream))
+
+
+def linear_attn_state_bwd_workspace_bytes(dtype, B, H, S, Dk, Dv) -> int:
+    need = C.c_size_t(0)
+    check(lib().kf_linear_attn_state_bwd_workspace_bytes(dtype, B, H, S, Dk, Dv, C.byref(need)))
+    return need.value
+
+
+def linear_attn_state_bwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, h0, d_o, d_hT, dq, dk, dv, dg, d_h0, workspace=None, workspace_bytes=None,
+                          stream=None):
+    """kf_linear_attn_state_bwd: linear_attn_bwd with the gradient d_hT of the final state (or None) and d_h0 of the initial one (or None;
+    needs h0). Without a workspace, one of the queried size is made here and returned (keep it until the stream is synchronised)."""
+    ws = None
+    if workspace is None:
+        workspace_bytes = linear_attn_state_bwd_workspace_bytes(dtype, B, H, S, Dk, Dv)
+        ws = DevBuf(workspace_bytes)
+        workspace = ws.ptr
+    check(lib().kf_linear_attn_state_bwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, h0, d_o, d_hT, dq, dk, dv, dg, d_h0, workspace, workspace_bytes,
+                                         stream))
+    return ws
+
+
+def linear_attn_step(dtype, B, H, T, Dk, Dv, scale, q, k, v, g, state, o, stream=None):
+    """kf_linear_attn_step: T steps of the recurrence on `state` (f32 [B, H, Dk, Dv], updated in place); q, k, v, o [B, H, T, D]."""
+    check(lib().kf_linear_attn_step(dtype, B, H, T, Dk, Dv, scale, q, k, v, g, state, o, stream))
+
+
 def index_put(desc: IterDesc, sizes, strides_bytes, stream=None):
     n = len(sizes)
     a = (C.c_int64 * n)(*sizes)
