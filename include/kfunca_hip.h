@@ -1184,6 +1184,38 @@ int kf_linear_attn_state_bwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t
 int kf_linear_attn_step(int dtype, int64_t B, int64_t H, int64_t T, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
                         const void *v, const float *g, float *state, void *o, void *stream);
 
+/* ---- causal depthwise conv1d with a carried state (the short convolution of Mamba-2, Gated DeltaNet, ...) ----
+ *   pre[b, t, c] = bias[c] + sum_{j < K} w[j, c] z[b, t + j, c],  z[b] = h0[b] (K - 1 rows) then x[b] (S rows) along time
+ *   y = act(pre), act the identity (KF_CONV1D_ACT_NONE) or SiLU (KF_CONV1D_ACT_SILU);  hT[b] = the last K - 1 rows of z[b]
+ *   channel-last: x, y, dy, dx are [B, S, C] rows with leading dimensions in elements (>= C: a column slice of a wider projection row is
+ *   read in place); weight [K, C] tap-major, w[K - 1] on the current token (torch's conv1d.weight[:, 0, :].T with left padding K - 1);
+ *   bias [C]; h0, hT, d_h0, d_hT [B, K - 1, C]. weight, bias and the states are dense; one dtype (KF_BF16, KF_F16, KF_F32) for every
+ *   operand. K in {2, 3, 4}; any S >= 1 (S < K - 1: hT holds shifted rows of h0). bias, h0, hT, d_hT, d_h0, dbias may each be NULL (a
+ *   missing bias or h0 is zero). hT is copies of inputs, so it is exact, and hT of one call is h0 of the next. All arithmetic is f32
+ *   with one rounding at each store.
+ *   Backward, with dpre = dy act'(pre) and pre recomputed from x (the forward keeps nothing):
+ *   dz[b, m] = sum_j w[j] dpre[b, m - j] (0 <= m - j < S) + d_hT[b, m - S] (m >= S);  dx = dz rows K - 1 ..,  d_h0 = dz rows 0 .. K - 2
+ *   dw[j, c] = sum_{b, t} dpre[b, t, c] z[b, t + j, c],  dbias[c] = sum_{b, t} dpre[b, t, c], summed in f32 in one fixed order (per
+ *   wave, then the four waves of a workgroup, then the workgroups ascending) and rounded once. The workspace
+ *   (kf_causal_conv1d_bwd_workspace_bytes, 16-byte aligned) needs no initialisation. Nothing synchronises, allocates, uses atomics or
+ *   reads a value back: every entry can be captured and two calls give the same bits. Profile labels
+ *   causal_conv1d_fwd_{bf16,f16,f32}, causal_conv1d_bwd_{bf16,f16,f32}, causal_conv1d_wgrad_reduce.
+ *   Aliasing: with S <= KF_CONV1D_STEP_MAX (the rows one wave walks: one lane then reads and writes all of a channel pack) hT may be h0
+ *   and y may be x (ldy == ldx) - the decode step in place; any other overlap of an output with an operand is KF_ERR_INVALID.
+ * Every argument is checked before any device call, with the entry's name in kf_last_error(): KF_ERR_INVALID for a null x, weight, y,
+ * dy, dx or dw, a non-positive extent, an unknown act, a leading dimension below C, a base not aligned to 16 bytes, forbidden aliasing;
+ * KF_ERR_UNSUPPORTED for another dtype, K outside {2, 3, 4}, C or a leading dimension that is not a multiple of the 16-byte pack (8
+ * elements of 16 bits, 4 floats), B or ceil(S / 256) above 65535; KF_ERR_WORKSPACE for a missing, short or misaligned workspace.
+ */
+enum { KF_CONV1D_ACT_NONE = 0, KF_CONV1D_ACT_SILU = 1, KF_CONV1D_STEP_MAX = 64 };
+int kf_causal_conv1d_fwd(int dtype, int act, int64_t B, int64_t S, int64_t C, int64_t K, const void *x, int64_t ldx, const void *weight,
+                         const void *bias /* or NULL */, const void *h0 /* or NULL */, void *y, int64_t ldy, void *hT /* or NULL */, void *stream);
+int kf_causal_conv1d_bwd_workspace_bytes(int dtype, int64_t B, int64_t S, int64_t C, int64_t K, size_t *bytes);
+int kf_causal_conv1d_bwd(int dtype, int act, int64_t B, int64_t S, int64_t C, int64_t K, const void *x, int64_t ldx, const void *weight,
+                         const void *bias /* or NULL */, const void *h0 /* or NULL */, const void *dy, int64_t lddy,
+                         const void *d_hT /* or NULL */, void *dx, int64_t lddx, void *dw, void *dbias /* or NULL */,
+                         void *d_h0 /* or NULL */, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- collectives (RCCL over xGMI): the one exchange step of the batch-sharded path (§8e) ---- */
 #define KF_COMM_ID_BYTES 128
 int kf_comm_unique_id(char id[KF_COMM_ID_BYTES]);

@@ -11,6 +11,7 @@
 
 #include "allocator.h"
 #include "attn_full.h"
+#include "causal_conv1d.h"
 #include "comm.h"
 #include "device_api.h"
 #include "expert_linear.h"
@@ -359,6 +360,28 @@ PYBIND11_MODULE(_C, m) {
           "[B, H, T, D], g [B, H, T] -> o [B, H, T, D]; state, float [B, H, D, D], is updated in place. The generation half of the inference "
           "path: state comes from linear_attention(..., return_state=True) over the prompt, then one call per new token (or per handful of "
           "speculative tokens). Not differentiable; can be captured into a graph.");
+    m.def("causal_conv1d", [](const Tensor &x, const Tensor &weight, py::object bias, py::object activation, py::object initial_state,
+                              bool return_state) -> py::object {
+        auto r = gpu::causal_conv1d(x, weight, bias.is_none() ? Tensor() : bias.cast<Tensor>(), activation.is_none() ? "" : activation.cast<std::string>(),
+                                    initial_state.is_none() ? Tensor() : initial_state.cast<Tensor>(), return_state);
+        return return_state ? py::object(py::make_tuple(r.first, r.second)) : py::cast(r.first);
+    }, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(), py::arg("activation") = py::none(), py::arg("initial_state") = py::none(),
+          py::arg("return_state") = false,
+          "causal_conv1d(x, weight, bias=None, activation=None, initial_state=None, return_state=False): the causal depthwise convolution "
+          "(short conv) in front of a linear-time mixer, y[b, t, c] = act(bias[c] + sum_j weight[j, c] z[b, t + j, c]) with z = initial_state "
+          "then x along time. x [B, S, C] float, half or bfloat16, channel-last; it may be a last-dimension slice of a wider tensor (a packed "
+          "projection) and is then read in place. weight [K, C], K in {2, 3, 4}, weight[K - 1] on the current token (torch's "
+          "conv1d.weight[:, 0, :].T with left padding K - 1); activation None or \"silu\". initial_state [B, K - 1, C] (None: zeros); with "
+          "return_state the result is (y, state), state the last K - 1 input rows. Segments chained through the state give the bits of the "
+          "whole sequence. Differentiable in x, weight, bias and initial_state.");
+    m.def("causal_conv1d_step", [](const Tensor &x, const Tensor &weight, Tensor &state, py::object bias, py::object activation) {
+        return gpu::causal_conv1d_step(x, weight, bias.is_none() ? Tensor() : bias.cast<Tensor>(), state,
+                                       activation.is_none() ? "" : activation.cast<std::string>());
+    }, py::arg("x"), py::arg("weight"), py::arg("state"), py::arg("bias") = py::none(), py::arg("activation") = py::none(),
+          "causal_conv1d_step(x, weight, state, bias=None, activation=None): causal_conv1d for T <= 64 new tokens, x [B, T, C] -> y [B, T, C]; "
+          "state [B, K - 1, C], contiguous, is updated in place. The generation half of the inference path: state comes from "
+          "causal_conv1d(..., return_state=True) over the prompt, then one call per new token; the outputs have the bits of the one-shot "
+          "forward. Not differentiable; can be captured into a graph.");
     m.def("gemm_sym", [](const Tensor &x, float alpha, py::object d, float beta, float gamma) {
         return gpu::gemm_sym(x, alpha, d.is_none() ? Tensor() : d.cast<Tensor>(), beta, gamma);
     }, py::arg("x"), py::arg("alpha") = 1.0f, py::arg("d") = py::none(), py::arg("beta") = 0.0f, py::arg("gamma") = 0.0f);

@@ -37,6 +37,7 @@ CONSTANTS = (
     "ATTN_MASK_FULL", "ATTN_MASK_PREFIX", "ATTN_MASK_WINDOW", "ATTN_MASK_DOC",
     "MOE_SCORE_SOFTMAX", "MOE_SCORE_SIGMOID",
     "FP8_E4M3", "FP8_E5M2",
+    "CONV1D_ACT_NONE", "CONV1D_ACT_SILU", "CONV1D_STEP_MAX",
     "MAX_DIMS", "MAX_TENSORS", "COMM_ID_BYTES",
     "KF_OK", "KF_ERR_HIP", "KF_ERR_INVALID", "KF_ERR_UNSUPPORTED", "KF_ERR_INDEX_RANGE", "KF_ERR_WORKSPACE", "KF_ERR_COMM", "KF_ERR_OOM",
 )
@@ -555,6 +556,33 @@ def linear_attn_state_bwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, h0, d_o, d_
 def linear_attn_step(dtype, B, H, T, Dk, Dv, scale, q, k, v, g, state, o, stream=None):
     """kf_linear_attn_step: T steps of the recurrence on `state` (f32 [B, H, Dk, Dv], updated in place); q, k, v, o [B, H, T, D]."""
     check(lib().kf_linear_attn_step(dtype, B, H, T, Dk, Dv, scale, q, k, v, g, state, o, stream))
+
+
+def causal_conv1d_fwd(dtype, act, B, S, C, K, x, ldx, weight, bias, h0, y, ldy, hT, stream=None):
+    """kf_causal_conv1d_fwd: y = act(bias + sum_j weight[j] z[t + j]) over z = h0 (K - 1 rows or None: zeros) then x; x, y [B, S, C] rows with
+    leading dimensions in elements, weight [K, C], bias [C] or None; the last K - 1 rows of z to hT (or None)."""
+    check(lib().kf_causal_conv1d_fwd(dtype, act, B, S, C, K, x, ldx, weight, bias, h0, y, ldy, hT, stream))
+
+
+def causal_conv1d_bwd_workspace_bytes(dtype, B, S, C, K) -> int:
+    import ctypes   # (the parameter C, the ABI's name for the channels, hides the module's alias here)
+    need = ctypes.c_size_t(0)
+    check(lib().kf_causal_conv1d_bwd_workspace_bytes(dtype, B, S, C, K, ctypes.byref(need)))
+    return need.value
+
+
+def causal_conv1d_bwd(dtype, act, B, S, C, K, x, ldx, weight, bias, h0, dy, lddy, d_hT, dx, lddx, dw, dbias, d_h0, workspace=None,
+                      workspace_bytes=None, stream=None):
+    """kf_causal_conv1d_bwd: dx, dw and (each or None) dbias, d_h0 from x, dy and the gradient d_hT of the final state (or None). Without
+    a workspace, one of the queried size is made here and returned (keep it until the stream is synchronised)."""
+    ws = None
+    if workspace is None:
+        workspace_bytes = causal_conv1d_bwd_workspace_bytes(dtype, B, S, C, K)
+        ws = DevBuf(workspace_bytes)
+        workspace = ws.ptr
+    check(lib().kf_causal_conv1d_bwd(dtype, act, B, S, C, K, x, ldx, weight, bias, h0, dy, lddy, d_hT, dx, lddx, dw, dbias, d_h0, workspace,
+                                     workspace_bytes, stream))
+    return ws
 
 
 def index_put(desc: IterDesc, sizes, strides_bytes, stream=None):
