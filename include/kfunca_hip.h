@@ -1184,6 +1184,28 @@ int kf_linear_attn_state_bwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t
 int kf_linear_attn_step(int dtype, int64_t B, int64_t H, int64_t T, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
                         const void *v, const float *g, float *state, void *o, void *stream);
 
+/* ---- the gated delta rule, forward with a carried state and the decode step ----
+ *   S' = exp(g_t) S_{t-1},  u_t = beta_t (v_t - k_t S'),  S_t = S' + k_t^T u_t,  o_t = scale q_t S_t
+ *   (Gated DeltaNet; with g absent DeltaNet). q, k, v, o [B, H, S, D] contiguous, KF_BF16 or KF_F16; g (<= 0; NULL counts as 0) and beta
+ *   [B, H, S] float; h0, hT, state dense [B, H, Dk, Dv] float (h0 NULL: zero; hT NULL: not written; hT may be h0); Dk == Dv in {64, 128};
+ *   any S >= 1. The caller normalises k: the kernels neither normalise nor check. The forward runs in 64-step chunks: a chunk-parallel
+ *   kernel inverts each chunk's unit-lower-triangular system in f32 and leaves W and Ubar in the workspace
+ *   (kf_delta_rule_fwd_workspace_bytes = 2 B H ceil(S / 64) 64 D 2 bytes, 16-byte aligned, no initialisation needed), then one walk per
+ *   (b, h, 64 columns of Dv) carries the state in f32. kf_delta_rule_step is the recurrence token by token for t = 0 .. T - 1 on `state`,
+ *   updated in place (read once and written once whatever T is; all in f32, o rounded once). There is no backward yet. Nothing
+ *   synchronises, allocates, uses atomics or reads a value back: the entries can be captured and two calls give the same bits. Profile
+ *   labels delta_rule_prep_{bf16,f16}, delta_rule_fwd_{bf16,f16}, delta_rule_step_{bf16,f16}.
+ * Every argument is checked before any device call, with the entry's name in kf_last_error(): KF_ERR_INVALID for a null pointer (but g,
+ * h0, hT), a non-positive extent, a scale that is zero or not finite, a base not aligned to 16 bytes; KF_ERR_UNSUPPORTED for another
+ * dtype, Dk != Dv, a head size outside {64, 128} or B H ceil(S / 64) >= 2^31; KF_ERR_WORKSPACE for a missing, short or misaligned workspace.
+ */
+int kf_delta_rule_fwd_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, size_t *bytes);
+int kf_delta_rule_fwd(int dtype, int64_t B, int64_t H, int64_t S, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                      const void *v, const float *g /* or NULL */, const float *beta, const float *h0 /* or NULL */, void *o,
+                      float *hT /* or NULL */, void *workspace, size_t workspace_bytes, void *stream);
+int kf_delta_rule_step(int dtype, int64_t B, int64_t H, int64_t T, int64_t Dk, int64_t Dv, float scale, const void *q, const void *k,
+                       const void *v, const float *g /* or NULL */, const float *beta, float *state, void *o, void *stream);
+
 /* ---- causal depthwise conv1d with a carried state (the short convolution of Mamba-2, Gated DeltaNet, ...) ----
  *   pre[b, t, c] = bias[c] + sum_{j < K} w[j, c] z[b, t + j, c],  z[b] = h0[b] (K - 1 rows) then x[b] (S rows) along time
  *   y = act(pre), act the identity (KF_CONV1D_ACT_NONE) or SiLU (KF_CONV1D_ACT_SILU);  hT[b] = the last K - 1 rows of z[b]

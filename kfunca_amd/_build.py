@@ -34,7 +34,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rd
 # The older sources keep the flags their measured profiles were taken with; their results are held by their tests on every run.
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_HIP_FLAGS = {"gemm_sym.hip": NO_PACKED_F32, "muon.hip": NO_PACKED_F32, "linear_attn.hip": NO_PACKED_F32,
-                   "causal_conv1d.hip": NO_PACKED_F32}
+                   "causal_conv1d.hip": NO_PACKED_F32, "delta_rule.hip": NO_PACKED_F32}
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-sign-compare",
              f"-I{INCLUDE}", f"-I{CSRC / 'core'}"]
 

@@ -18,6 +18,7 @@
 #include "fp8.h"
 #include "glu.h"
 #include "linear_attn.h"
+#include "delta_rule.h"
 #include "linear_ce.h"
 #include "moe.h"
 #include "softmax.h"
@@ -360,7 +361,28 @@ PYBIND11_MODULE(_C, m) {
           "[B, H, T, D], g [B, H, T] -> o [B, H, T, D]; state, float [B, H, D, D], is updated in place. The generation half of the inference "
           "path: state comes from linear_attention(..., return_state=True) over the prompt, then one call per new token (or per handful of "
           "speculative tokens). Not differentiable; can be captured into a graph.");
-    m.def("causal_conv1d", [](const Tensor &x, const Tensor &weight, py::object bias, py::object activation, py::object initial_state,
+    m.def("gated_delta_rule", [](const Tensor &q, const Tensor &k, const Tensor &v, py::object g, const Tensor &beta, py::object scale,
+                                 py::object initial_state, bool return_state) -> py::object {
+        auto r = gpu::gated_delta_rule(q, k, v, g.is_none() ? Tensor() : g.cast<Tensor>(), beta,
+                                       scale.is_none() ? std::nullopt : std::optional<float>(scale.cast<float>()),
+                                       initial_state.is_none() ? Tensor() : initial_state.cast<Tensor>(), return_state);
+        return return_state ? py::object(py::make_tuple(r.first, r.second)) : py::cast(r.first);
+    }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("g"), py::arg("beta"), py::arg("scale") = py::none(), py::arg("initial_state") = py::none(),
+          py::arg("return_state") = false,
+          "gated_delta_rule(q, k, v, g, beta, scale=None, initial_state=None, return_state=False): S' = exp(g_t) S_{t-1}, "
+          "u_t = beta_t (v_t - k_t S'), S_t = S' + k_t^T u_t, o_t = scale q_t S_t (Gated DeltaNet; g=None: DeltaNet) in 64-step chunks on the "
+          "matrix cores. q, k, v [B, H, S, D] half or bfloat16 with D in {64, 128}; g [B, H, S] float, <= 0, or None; beta [B, H, S] float; the "
+          "caller normalises k; scale defaults to D ** -0.5. initial_state is S_0, float [B, H, D, D] (None: zero); with return_state the "
+          "result is (o, S_T). The backward is not implemented yet: the results carry no gradient node. A prefill with return_state=True "
+          "followed by gated_delta_rule_step calls is the inference path.");
+    m.def("gated_delta_rule_step", [](const Tensor &q, const Tensor &k, const Tensor &v, py::object g, const Tensor &beta, Tensor &state, py::object scale) {
+        return gpu::gated_delta_rule_step(q, k, v, g.is_none() ? Tensor() : g.cast<Tensor>(), beta, state,
+                                          scale.is_none() ? std::nullopt : std::optional<float>(scale.cast<float>()));
+    }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("g"), py::arg("beta"), py::arg("state"), py::arg("scale") = py::none(),
+          "gated_delta_rule_step(q, k, v, g, beta, state, scale=None): T steps of the recurrence of gated_delta_rule, token by token: q, k, v "
+          "[B, H, T, D], g (or None) and beta [B, H, T] -> o [B, H, T, D]; state, float [B, H, D, D], contiguous, is updated in place. The "
+          "generation half of the inference path. The backward is not implemented yet: not differentiable; can be captured into a graph.");
+    m.def("causal_conv1d", [](const Tensor &x,const Tensor &weight, py::object bias, py::object activation, py::object initial_state,
                               bool return_state) -> py::object {
         auto r = gpu::causal_conv1d(x, weight, bias.is_none() ? Tensor() : bias.cast<Tensor>(), activation.is_none() ? "" : activation.cast<std::string>(),
                                     initial_state.is_none() ? Tensor() : initial_state.cast<Tensor>(), return_state);

@@ -558,6 +558,30 @@ def linear_attn_step(dtype, B, H, T, Dk, Dv, scale, q, k, v, g, state, o, stream
     check(lib().kf_linear_attn_step(dtype, B, H, T, Dk, Dv, scale, q, k, v, g, state, o, stream))
 
 
+def delta_rule_fwd_workspace_bytes(dtype, B, H, S, Dk, Dv) -> int:
+    need = C.c_size_t(0)
+    check(lib().kf_delta_rule_fwd_workspace_bytes(dtype, B, H, S, Dk, Dv, C.byref(need)))
+    return need.value
+
+
+def delta_rule_fwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, beta, h0, o, hT, workspace=None, workspace_bytes=None, stream=None):
+    """kf_delta_rule_fwd: the gated delta rule S_t = e^{g_t} S_{t-1} + k_t^T beta_t (v_t - k_t e^{g_t} S_{t-1}), o_t = scale q_t S_t from the
+    state h0 (f32 [B, H, Dk, Dv] or None: zero), the final state to hT (or None); g [B, H, S] f32 or None (0), beta [B, H, S] f32. Without
+    a workspace, one of the queried size is made here and returned (keep it until the stream is synchronised)."""
+    ws = None
+    if workspace is None:
+        workspace_bytes = delta_rule_fwd_workspace_bytes(dtype, B, H, S, Dk, Dv)
+        ws = DevBuf(workspace_bytes)
+        workspace = ws.ptr
+    check(lib().kf_delta_rule_fwd(dtype, B, H, S, Dk, Dv, scale, q, k, v, g, beta, h0, o, hT, workspace, workspace_bytes, stream))
+    return ws
+
+
+def delta_rule_step(dtype, B, H, T, Dk, Dv, scale, q, k, v, g, beta, state, o, stream=None):
+    """kf_delta_rule_step: T steps of the gated delta rule on `state` (f32 [B, H, Dk, Dv], updated in place); q, k, v, o [B, H, T, D]."""
+    check(lib().kf_delta_rule_step(dtype, B, H, T, Dk, Dv, scale, q, k, v, g, beta, state, o, stream))
+
+
 def causal_conv1d_fwd(dtype, act, B, S, C, K, x, ldx, weight, bias, h0, y, ldy, hT, stream=None):
     """kf_causal_conv1d_fwd: y = act(bias + sum_j weight[j] z[t + j]) over z = h0 (K - 1 rows or None: zeros) then x; x, y [B, S, C] rows with
     leading dimensions in elements, weight [K, C], bias [C] or None; the last K - 1 rows of z to hT (or None)."""
